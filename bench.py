@@ -1,10 +1,17 @@
 """Headline benchmark: fp64 generalized Lomb-Scargle, N=1e5 unevenly sampled points x 1e6 trial
 frequencies per GPU (BASELINE.json configs[1]); prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N --steps K --warmup W]                  # one process, N devices
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]   # one process, N devices
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W      # one rank per GPU
-    python bench.py --loopback N                                     # N logical slots on ONE device (testing)
+    python bench.py --loopback N --full                              # N logical slots on ONE device (testing)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (``value``, ``ms_per_step``, the
+``roofline`` block priced from the committed PMC summary and this run's HIP-event times).  Everything measured
+beyond that takes ``--full``: the same-run clock probe, the kernel time and end-to-end call of the plan path, the
+FFT path, the other configs (``extras``), the CPU baselines, and with N > 1 the sharded extras and the
+strong-scaling entries.  ``--dump-outputs DIR`` writes the power array of the last timed step to
+``DIR/power.npy`` (float64; the inputs are seeded, so two builds can be compared output for output).
 
 A step = one pass of the hot path over resident inputs: the weights prologue + direct-sum scan + fused
 epilogue (``pdc_gls_scan_dev``) writing power[nf] in HBM.  With N > 1 each GPU scans its own
@@ -1232,6 +1239,75 @@ def strong_scaling_dist(cabi, lib, torch, dist, dev, rank, world, coll):
     return out
 
 
+def headline_roofline(n, slab_nf, kernel_s, kernel_all_ms, clock):
+    """The line's ``roofline`` block: the committed PMC summary priced against this run's kernel time."""
+    launch_pairs = float(n) * float(slab_nf)
+    kernel_ms_now = kernel_s * 1e3
+    algorithmic = launch_pairs * FLOP_PER_PAIR / kernel_s / 1e12
+    fr, blk = two_fracs("gls_scan_kernel", kernel_ms_now, algorithmic / PEAK_FP64_VECTOR_TFLOPS,
+                        "50 flop/pair vs 78.6 TFLOP/s")
+    why = fr.get("executed_issue_note")
+    algo_bytes = 24.0 * n + 8.0 * slab_nf
+    if blk:
+        # the issue fraction priced by instruction type (valu_issue_block); `achieved` = that fraction of the peak
+        frac = blk["frac"]
+        achieved = frac * PEAK_FP64_VECTOR_TFLOPS
+        traffic = blk.get("hbm_bytes")
+    else:
+        achieved = frac = traffic = None
+    return {"bound": "valu",
+            "achieved": None if achieved is None else round(achieved, 3),
+            "peak": PEAK_FP64_VECTOR_TFLOPS, "unit": "TFLOP/s", "frac": frac,
+            "achieved_is": "issue slots: frac x 78.6 (every fp64 / int64 VALU instruction priced at its 4 "
+                           "issue cycles) - NOT flops; the flops are achieved_flops_TFLOPs",
+            "achieved_flops_TFLOPs": (executed_flops(blk, kernel_ms_now) or {}).get("TFLOPs"),
+            "achieved_flops": executed_flops(blk, kernel_ms_now),
+            "traffic": traffic,
+            "kernel": "gls_scan_kernel (+ prologue kernels, <0.1%)",
+            "kernel_ms": round(kernel_ms_now, 4),
+            "kernel_ms_is": "median of the HIP-event times of the timed steps",
+            "kernel_ms_all": kernel_all_ms,
+            "effective_clock_GHz": clock.get("effective_clock_GHz"),
+            "frac_at_effective_clock": None if (frac is None or not clock.get("effective_clock_GHz"))
+            else round(frac * (CLOCK_HZ / 1e9) / clock["effective_clock_GHz"], 4),
+            "clock_probe": clock,
+            **fr,
+            "valu_issue": blk,
+            "algorithmic": {"flop_per_pair": FLOP_PER_PAIR,
+                            "achieved_TFLOPs": round(algorithmic, 3),
+                            "ratio_to_direct_evaluation_roofline": round(
+                                algorithmic / PEAK_FP64_VECTOR_TFLOPS, 4),
+                            "bytes_per_launch": algo_bytes},
+            "note": "fp64 vector-ALU bound (software sincos + rotation recurrences; no fp64 "
+                    "transcendental unit, not a contraction).  achieved/frac = EXECUTED "
+                    "issue: VALU issue cycles per launch (fp64/int64 instructions x 4 cycles, all "
+                    "others x 2, from the typed rocprofv3 counters) / 1024 SIMDs / 2.4 GHz / "
+                    "HIP-event time, `achieved` = that fraction of the 78.6 TFLOP/s peak; "
+                    "`algorithmic` prices SURVEY 8d's 50 flop/pair of a direct "
+                    "evaluation and may exceed the roofline; traffic = HBM-side bytes per "
+                    "launch (FETCH_SIZE x 2 + WRITE_SIZE, separate PMC passes) vs "
+                    "24 N + 8 nf algorithmic"
+                    + ("" if blk else f"; executed-issue figures unavailable: {why}")}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, **arrays):
+    """``out_dir/<name>.npy`` (float64) for every array, at most DUMP_LIMIT_BYTES in all: an array over its share is
+    replaced by a fixed seeded sample of its elements, their indices in ``<name>_index.npy``."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (2 * len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64).ravel()
+        if a.nbytes > share:
+            keep = share // (a.itemsize + 8)
+            idx = np.sort(np.random.default_rng(20241008).choice(a.size, keep, replace=False))
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def clock_probe(lib, cabi, dev, stream, iters=10_000, reps=3):
     """The clock this box sustains under fp64 load, measured in THIS run right after the timed steps: a fixed count
     of v_fma_f64 (pdc_clock_probe: 16 independent chains per lane, 4 waves on every SIMD) / HIP-event time, at 4 issue
@@ -1332,6 +1408,11 @@ def main():
                     help="take the one-process multi-device plan path even with one GPU (testing)")
     ap.add_argument("--force-sharded-extras", action="store_true",
                     help="run the N > 1 extras even with one rank / one slot (testing)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline: clock probe, FFT path, extras, CPU baselines, "
+                         "and with N > 1 the plan's kernel time, the sharded extras and the strong-scaling entries")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the power array of the last timed step to DIR/power.npy (float64)")
     ap.add_argument("--loopback", type=int, default=0, metavar="N",
                     help="N logical slots on ONE device through the plan path (testing the N > 1 code on a 1-GPU box); "
                          "the all-gather runs as device-to-device copies; `value` is not a scaling figure")
@@ -1485,13 +1566,34 @@ def main():
     if dist_mode:
         elapsed = coll.max(elapsed)
 
-    # same-run clock evidence: what this box sustains under fp64 load, right after the timed steps
-    try:
-        clock = clock_probe(lib, _cabi, dev, None if plan_mode else stream)
-    except Exception as exc:
-        clock = {"effective_clock_GHz": None, "error": f"{type(exc).__name__}: {exc}"}
+    # what the last timed step computed, read back before anything else runs on the device (the FFT path of
+    # --full writes into the same buffer)
+    got = None
+    if rank == 0:
+        if plan_mode:
+            got = plan.download(0)
+            if n_slots > 1:      # every slot must hold the same gathered array
+                other = plan.download(n_slots - 1)
+                assert np.array_equal(got, other, equal_nan=True), "all-gather left the devices with different arrays"
+        elif dist_mode:
+            got = powers[(counter[0] - 1) % 2].cpu().numpy()
+        else:
+            got = power_buf.to_array(np.float64, nf_total)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, power=got)
 
-    if plan_mode:
+    if args.full:
+        # same-run clock evidence: what this box sustains under fp64 load, right after the timed steps
+        try:
+            clock = clock_probe(lib, _cabi, dev, None if plan_mode else stream)
+        except Exception as exc:
+            clock = {"effective_clock_GHz": None, "error": f"{type(exc).__name__}: {exc}"}
+    else:
+        clock = {"effective_clock_GHz": None, "note": "the clock probe runs with --full"}
+
+    if plan_mode and not args.full:
+        kernel_all_ms, end_to_end_s = [], None
+    elif plan_mode:
         # kernel time of one slab scan on device 0, measured outside the timed region (the plan keeps
         # one event pair; reading it per step would serialise the double buffering)
         for _ in range(3):
@@ -1512,10 +1614,10 @@ def main():
             ms = C.c_float()
             _cabi.check(lib.pdc_event_elapsed_ms(dev, a, b, C.byref(ms)))
             kernel_all_ms.append(round(ms.value, 4))
-    kernel_s = float(np.median(kernel_all_ms)) / 1e3
+    kernel_s = float(np.median(kernel_all_ms)) / 1e3 if kernel_all_ms else None
 
     sharded = None
-    if (n_slots > 1 or args.force_sharded_extras) and not args.no_extras:
+    if args.full and (n_slots > 1 or args.force_sharded_extras) and not args.no_extras:
         # (informational: a failure here must not cost the headline line - every rank runs the same code, so an
         # exception raised before a collective is raised on all of them)
         try:
@@ -1538,31 +1640,8 @@ def main():
         sharded = dict(sharded or {}, **strong)
 
     if rank == 0:
-        if plan_mode:
-            got = plan.download(0)
-            if n_slots > 1:      # every slot must hold the same gathered array
-                other = plan.download(n_slots - 1)
-                assert np.array_equal(got, other, equal_nan=True), "all-gather left the devices with different arrays"
-        elif dist_mode:
-            got = powers[(counter[0] - 1) % 2].cpu().numpy()
-        else:
-            got = power_buf.to_array(np.float64, nf_total)
         pairs_per_step = float(n) * float(nf_total)
         value = pairs_per_step * args.steps / elapsed / 1e9
-        launch_pairs = float(n) * float(slab_nf)
-        kernel_ms_now = kernel_s * 1e3
-        algorithmic = launch_pairs * FLOP_PER_PAIR / kernel_s / 1e12
-        fr, blk = two_fracs("gls_scan_kernel", kernel_ms_now, algorithmic / PEAK_FP64_VECTOR_TFLOPS,
-                            "50 flop/pair vs 78.6 TFLOP/s")
-        why = fr.get("executed_issue_note")
-        algo_bytes = 24.0 * n + 8.0 * slab_nf
-        if blk:
-            # the issue fraction priced by instruction type (valu_issue_block); `achieved` = that fraction of the peak
-            frac = blk["frac"]
-            achieved = frac * PEAK_FP64_VECTOR_TFLOPS
-            traffic = blk.get("hbm_bytes")
-        else:
-            achieved = frac = traffic = None
         out = {
             "metric": "Lomb-Scargle Gpair/s (sample x freq), fp64, N=1e5 x 1e6 per GPU",
             "value": round(value, 2), "unit": "Gpair/s", "n_gpus": n_gpus, "steps": args.steps,
@@ -1582,44 +1661,13 @@ def main():
                        "launcher": "one process, N devices (pdc_gls_plan_*, ncclCommInitAll)" if plan_mode
                                    else ("one rank per GPU (torch.distributed over RCCL)" if dist_mode
                                          else "one process, one device")},
-            "roofline": {"bound": "valu",
-                         "achieved": None if achieved is None else round(achieved, 3),
-                         "peak": PEAK_FP64_VECTOR_TFLOPS, "unit": "TFLOP/s", "frac": frac,
-                         "achieved_is": "issue slots: frac x 78.6 (every fp64 / int64 VALU instruction priced at its 4 "
-                                        "issue cycles) - NOT flops; the flops are achieved_flops_TFLOPs",
-                         "achieved_flops_TFLOPs": (executed_flops(blk, kernel_ms_now) or {}).get("TFLOPs"),
-                         "achieved_flops": executed_flops(blk, kernel_ms_now),
-                         "traffic": traffic,
-                         "kernel": "gls_scan_kernel (+ prologue kernels, <0.1%)",
-                         "kernel_ms": round(kernel_ms_now, 4),
-                         "kernel_ms_is": "median of the HIP-event times of the timed steps",
-                         "kernel_ms_all": kernel_all_ms,
-                         "effective_clock_GHz": clock.get("effective_clock_GHz"),
-                         "frac_at_effective_clock": None if (frac is None or not clock.get("effective_clock_GHz"))
-                         else round(frac * (CLOCK_HZ / 1e9) / clock["effective_clock_GHz"], 4),
-                         "clock_probe": clock,
-                         **fr,
-                         "valu_issue": blk,
-                         "algorithmic": {"flop_per_pair": FLOP_PER_PAIR,
-                                         "achieved_TFLOPs": round(algorithmic, 3),
-                                         "ratio_to_direct_evaluation_roofline": round(
-                                             algorithmic / PEAK_FP64_VECTOR_TFLOPS, 4),
-                                         "bytes_per_launch": algo_bytes},
-                         "note": "fp64 vector-ALU bound (software sincos + rotation recurrences; no fp64 "
-                                 "transcendental unit, not a contraction).  achieved/frac = EXECUTED "
-                                 "issue: VALU issue cycles per launch (fp64/int64 instructions x 4 cycles, all "
-                                 "others x 2, from the typed rocprofv3 counters) / 1024 SIMDs / 2.4 GHz / "
-                                 "HIP-event time, `achieved` = that fraction of the 78.6 TFLOP/s peak; "
-                                 "`algorithmic` prices SURVEY 8d's 50 flop/pair of a direct "
-                                 "evaluation and may exceed the roofline; traffic = HBM-side bytes per "
-                                 "launch (FETCH_SIZE x 2 + WRITE_SIZE, separate PMC passes) vs "
-                                 "24 N + 8 nf algorithmic"
-                                 + ("" if blk else f"; executed-issue figures unavailable: {why}")},
+            "roofline": None if kernel_s is None else headline_roofline(n, slab_nf, kernel_s, kernel_all_ms, clock),
             "peak_bin": int(np.nanargmax(got)),
         }
         if plan_mode:
             out["rccl"] = {"ranks_in_communicator": plan_info["rccl_ranks"], "exchange": plan_info["exchange"],
                            "slots": plan_info["n_slots"], "init_error": plan_info.get("init_error")}
+        if plan_mode and end_to_end_s is not None:
             out["end_to_end_sharded"] = {
                 "ms": round(end_to_end_s * 1e3, 3),
                 "Gpair_per_s": round(pairs_per_step / end_to_end_s / 1e9, 1),
@@ -1641,7 +1689,7 @@ def main():
                                                                                                     if loopback else ""))
             else:
                 out["strong_scaling"] = None
-        if n_slots == 1 and not dist_mode and not plan_mode:
+        if args.full and n_slots == 1 and not dist_mode and not plan_mode:
             # informational: the reference's own algorithm on the device (Tier F), same workload
             wb = lib.pdc_gls_fft_work_bytes(n, nf_total)
             fwork = _cabi.DeviceBuffer(wb, dev)
@@ -1661,7 +1709,7 @@ def main():
             if not args.no_extras:
                 out["extras"] = extra_configs(lib, _cabi, dev, stream, t, y, dy, f0, delta, nf_total,
                                                with_cpu=not args.no_cpu_baseline)
-        if not args.no_cpu_baseline and n_gpus == 1 and n_slots == 1:
+        if args.full and not args.no_cpu_baseline and n_gpus == 1 and n_slots == 1:
             base, p_fft = cpu_baseline(t, y, dy, freq, df, fmin)
             out["cpu_baseline"] = base
             out["peak_bin_matches_cpu_reference_path"] = bool(

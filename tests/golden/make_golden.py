@@ -87,8 +87,47 @@ def model_golden(GLS):
     save("g9_model", **out)
 
 
+def pins_golden(spectral, phase):
+    # G10 - what tests/test_oracle_vs_reference.py pins the oracle to bit for bit: the reference's two
+    # known-answer tests, the whole GLS call over four argument sets x fit_mean, the `_trig_sum` seam, the
+    # PDM call and the StringLength per-period seam (inputs: that test's seeded `curve`)
+    def curve(n, seed):
+        rng = np.random.default_rng(seed)
+        t = np.sort(rng.uniform(0, n, n))
+        dy = rng.uniform(0.05, 0.2, n)
+        return t, 1 + 0.5 * np.sin(2 * np.pi * t / 17.0) + dy * rng.standard_normal(n), dy
+
+    out = {}
+    ls = spectral.GLS(n=1)(TSeries(np.arange(0, 2.5 + 0.1, 0.1)))
+    out["known_grid_frequency"] = ls.frequency
+    sine = TSeries(values=np.sin((np.arange(100) / 100) * 20 * np.pi))
+    ls = spectral.GLS()(sine)
+    out["known_sine_frequency"], out["known_sine_power"] = ls.frequency, ls.values
+    out["known_sine_period"] = np.array(ls.period_at_highest_peak)
+    t, y, dy = curve(700, 3)
+    for i, kw in enumerate([dict(), dict(n=3.5), dict(fmin=0.01, fmax=0.4), dict(psd=True)]):
+        for fit_mean in (True, False):
+            ref = spectral.GLS(**kw)(TSeries(t, y), err=dy, fit_mean=fit_mean)
+            out[f"gls_frequency_{i}_fm{int(fit_mean)}"] = ref.frequency
+            out[f"gls_power_{i}_fm{int(fit_mean)}"] = ref.values
+    t, y, dy = curve(500, 4)
+    for tag, tt in (("t", t), ("shifted", t + 1234.5)):
+        out["trig_S_" + tag], out["trig_C_" + tag] = spectral._trig_sum(tt, dy, 0.001, 300, 0.0005)
+    t, y, _ = curve(600, 5)
+    res = phase.PDM(nb=4, nc=3, n_periods=40, cores=1)(TSeries(t, y))
+    out["pdm_frequency"], out["pdm_theta"] = res.frequency, res.values
+    sl = phase.StringLength(cores=1)
+    sl.m = TSeries(t, (y - np.nanmax(y)) / (2 * (np.nanmax(y) - np.nanmin(y))) + 0.25)     # phase.py:65-66
+    out["sl_periods"] = np.array([0.7, 3.3, 17.0, 250.0])
+    out["sl_ell"] = np.array([sl._stringlength(p) for p in out["sl_periods"]])
+    save("g10_reference_pins", **out)
+
+
 def main():
     spectral, phase = refstub.load()
+    if "--only-g10" in sys.argv:
+        pins_golden(spectral, phase)
+        return
     GLS = spectral.GLS
     model_golden(GLS)
     if "--only-g9" in sys.argv:
@@ -211,6 +250,8 @@ def main():
     elle = np.array([sl._stringlength(p) for p in pe])
     save("g8_stringlength", t=t, y=y, m=m, periods=periods, ell=ell,
          t_even=te, m_even=me, periods_even=pe, ell_even=elle)
+
+    pins_golden(spectral, phase)
 
 
 if __name__ == "__main__":

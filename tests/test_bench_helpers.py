@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 import bench
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -88,3 +90,17 @@ def test_fft_path_roofline_counts_passes_and_reads_the_traffic(tmp_path, monkeyp
     path.write_text(json.dumps(summ))
     r = bench.fft_path_roofline(100_000, 1_000_000, 0.5)
     assert r["traffic"] is None and "stale" in r["traffic_note"]
+
+
+def test_dump_outputs_keeps_small_arrays_whole_and_samples_large_ones_the_same_way(tmp_path):
+    small = np.linspace(0.0, 1.0, 1_000_000)                  # C2's power array: 8 MB, written whole
+    bench.dump_outputs(str(tmp_path / "a"), power=small)
+    assert np.array_equal(np.load(tmp_path / "a" / "power.npy"), small)
+    assert not (tmp_path / "a" / "power_index.npy").exists()
+    big = np.arange(8_000_000, dtype=np.float64) * 0.5        # loopback 8: 64 MB, a seeded sample under the limit
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), power=big)
+    got, idx = np.load(tmp_path / "b" / "power.npy"), np.load(tmp_path / "b" / "power_index.npy")
+    assert got.dtype == idx.dtype == np.float64 and got.nbytes + idx.nbytes <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(got, big[idx.astype(np.int64)]) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(got, np.load(tmp_path / "c" / "power.npy"))

@@ -63,7 +63,8 @@ def test_integration_md_binding_snippet_runs_against_the_built_library(built, mo
         if name != "pdc_last_error":        # same argument list as the package's own binding
             assert len(getattr(ns["_lib"], name).argtypes) == len(_cabi.PROTOTYPES[name][1]), name
     t = np.arange(8.0)
-    calls = [lambda: ns["gls_power"](t, np.ones(8), None, 0.1 + 0.1 * np.arange(4), True, False),
+    # (a constant signal has no periodogram - 0/0 in every bin, as upstream - so GLS gets a varying one)
+    calls = [lambda: ns["gls_power"](t, np.cos(t), None, 0.1 + 0.1 * np.arange(4), True, False),
              lambda: ns["trig_sum"](t, np.ones(8), 0.1, 4, 0.05),
              lambda: ns["pdm_thetas"](t, np.cos(t), [2.0, 3.0], 5, 2, 0.5),
              lambda: ns["string_lengths"](t, np.cos(t) / 4, [2.0, 3.0])]

@@ -96,6 +96,10 @@ def _fallback_worker(rank, world, port, out_dir):
     import bench
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
+    if torch.cuda.is_available():
+        # with a GPU the RCCL group could be built (or one rank could fail alone and leave the other waiting in
+        # it): every rank takes the injected failure instead
+        os.environ["PDC_FORCE_RCCL_FAIL"] = "1"
     backend, err = bench.init_dist(torch, dist, rank)           # no GPU here: the RCCL group cannot be built
     coll = bench.Coll(torch, dist, backend)
     send = torch.full((5,), float(rank + 1), dtype=torch.float64)

@@ -6,7 +6,7 @@
 # WRITE_SIZE 2) - see /opt/skills/guides/MI355X_MICROARCH.md.
 set -u
 out=$1; shift
-args=${*:---steps 3 --warmup 1 --no-cpu-baseline}
+args=${*:---full --steps 3 --warmup 1 --no-cpu-baseline}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$out"
 pass() {
@@ -26,7 +26,7 @@ pass l2    TCP_TCC_READ_REQ_sum TCC_REQ_sum TCC_HIT_sum TCC_MISS_sum
 rocprofv3 --kernel-trace --stats -d "$out/stats" -o run --output-format csv -- python3 bench.py $args > "$out/stats.log" 2>&1
 # the headline workload alone, 20 timed steps + 3 warm-up, so that the statistics of gls_scan_kernel are
 # the C2 launch's; the bench line of THIS run (same lease, same process) is kept beside the trace
-rocprofv3 --kernel-trace --stats -d "$out/stats_c2" -o run --output-format csv -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > "$out/stats_c2.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$out/stats_c2" -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras > "$out/stats_c2.log" 2>&1
 grep '^{"metric"' "$out/stats_c2.log" | tail -1 > "$out/bench_under_kernel_trace.json"
 python3 tools/kernel_median.py "$out/stats_c2/run_kernel_trace.csv" "$out/bench_c2_kernel_median.json"
 python3 tools/pmc_summary.py "$out" --out "$out/pmc_summary.json" --command "rocprofv3 --pmc <set> --kernel-trace -- python3 bench.py $args"
