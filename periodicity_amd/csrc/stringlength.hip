@@ -2714,6 +2714,61 @@ __global__ __launch_bounds__(256) void sl_link_kernel(StreamArgs a) {
 #include "timesort.inc"
 #include "supersmoother.inc"
 
+// ---- switches: environment variables, read once per process (A/B runs; tests set them in a child process) ----------
+//   name                  default  effect
+//   PDC_SL_STREAM         on       0: no streamed kernels
+//   PDC_SL_STREAM_MIN     262144   smallest N that takes the streamed kernels (stream_takes)
+//   PDC_SL_STREAM_GROUPS  rule     1 / 2 / 4 / 8 / 16: workgroups per period in the streamed histogram / partition /
+//                                  boundary kernels
+//   PDC_SL_STREAM_BATCH   rule     > 0: periods per streamed batch
+//   PDC_SL_STREAM_DEBUG   off      1: the streamed geometry and the periods left to the general kernel, on stderr
+//   PDC_SL_SLICES         on       0: the streamed kernels' lists mode only; no one-cycle pre-pass, no time sort
+//   PDC_SL_TIMESORT       on       0: samples out of order take the lists mode instead of the time sort
+//   PDC_SL_GENERAL        off      1: the general kernel takes every period
+//   PDC_SL_FAST_SLICES    16       most LDS slices of the fast kernels (above: the general kernel / the Supersmoother's
+//                                  other sorts)
+//   PDC_SL_DUO            on       0: no two-workgroups-per-CU kernel
+//   PDC_SL_QUAD           on       0: no four-workgroups-per-CU instance of it
+//   PDC_SL_P17            on       0: no 17- / 18-bit slices (StringLength; the Supersmoother's sort keeps them)
+//   PDC_SS_FASTSORT       on       0: the Supersmoother does not sort with the fast kernels
+//   PDC_SS_BATCH          rule     > 0: periods per Supersmoother batch
+//   PDC_SS_SUBMAX         rule     >= 8: largest sub-batch of the tiled smoother
+//   PDC_SS_SB             rule     a multiple of 8 below the rule's: sub-batch of the tiled smoother
+//   PDC_SS_SEG / _SEG34   rule     1 .. ss2::kSegMax: segments per period in its first two / last two sweeps
+// An "on" switch is off for a value that starts with '0', an "off" one on for a value that starts with '1'.
+struct Knobs {
+    bool slices, timesort, general_only, stream_debug, duo, quad, p17, ss_fastsort;
+    int64_t stream_min, stream_batch, ss_batch, ss_submax;
+    int stream_groups, fast_slices, ss_sb, ss_seg, ss_seg34;
+    Knobs() {
+        auto off = [](const char *name) { const char *e = getenv(name); return e && e[0] == '0'; };
+        auto one = [](const char *name) { const char *e = getenv(name); return e && e[0] == '1'; };
+        auto i64 = [](const char *name, int64_t def) { const char *e = getenv(name); return e ? (int64_t)atoll(e) : def; };
+        auto i32 = [](const char *name, int def) { const char *e = getenv(name); return e ? atoi(e) : def; };
+        stream_min = off("PDC_SL_STREAM") ? (int64_t)1 << 62 : i64("PDC_SL_STREAM_MIN", 262144);
+        stream_groups = i32("PDC_SL_STREAM_GROUPS", 0);
+        stream_batch = i64("PDC_SL_STREAM_BATCH", 0);
+        stream_debug = one("PDC_SL_STREAM_DEBUG");
+        slices = !off("PDC_SL_SLICES");
+        timesort = !off("PDC_SL_TIMESORT") && slices;
+        general_only = one("PDC_SL_GENERAL");
+        fast_slices = i32("PDC_SL_FAST_SLICES", 16);
+        duo = !off("PDC_SL_DUO");
+        quad = !off("PDC_SL_QUAD");
+        p17 = !off("PDC_SL_P17");
+        ss_fastsort = !off("PDC_SS_FASTSORT");
+        ss_batch = i64("PDC_SS_BATCH", 0);
+        ss_submax = i64("PDC_SS_SUBMAX", 0);
+        ss_sb = i32("PDC_SS_SB", 0);
+        ss_seg = i32("PDC_SS_SEG", 0);
+        ss_seg34 = i32("PDC_SS_SEG34", 0);
+    }
+};
+const Knobs &knobs() {
+    static const Knobs k;
+    return k;
+}
+
 int64_t pad_pow2(int64_t n) {
     int64_t p = 2;
     while (p < n) p <<= 1;
@@ -2730,16 +2785,6 @@ int64_t grid_for(int64_t n_periods) {
 
 // ranges: one per window of every slice, plus one per slice / oversized bucket
 int64_t range_slots(int64_t n) { return (n / kWin + n / 8192 + 64 + 3) & ~(int64_t)3; }   // (multiple of 4: keeps every array 16-byte aligned)
-
-// (the smaller of the two slice capacities: above it the kernel may need the per-period partition)
-bool may_need_partition(int64_t n) { return n > Lds<unsigned>::capacity; }
-
-int64_t scratch_bytes(int64_t n, int64_t n_periods, int64_t partition) {
-    return grid_for(n_periods > 0 ? n_periods : 1) * (pad_pow2(n) * 12 + range_slots(n) * 44 + partition) + 512;
-}
-
-// AoS (t, m) records + flags of the fast path, placed behind the general scratch
-int64_t fast_table_bytes(int64_t n) { return ((n * 16 + 255) & ~(int64_t)255) + 256; }
 
 // ---- periods of ONE cycle, whatever kernels take the rest ---------------------------------------------------
 // A period that outlasts the samples (p > baseline: the last ten of the reference's grid, phase.py:67-68 with dphi =
@@ -2808,14 +2853,6 @@ __global__ __launch_bounds__(kBlock) void sl_onecycle_kernel(OneArgs a) {
 }
 }  // namespace onecycle
 
-// skip[n_periods], list[n_periods], the flags of sl_tame_kernel + the count
-int64_t onecycle_bytes(int64_t n_periods) { return ((n_periods + 255) & ~(int64_t)255) + ((n_periods * 4 + 255) & ~(int64_t)255) + 512; }
-
-// workspace of the two-workgroups-per-CU kernel, behind the (t, m) table: the marks for the one-workgroup
-// kernel and the ticket counter
-int64_t duo_bytes(int64_t n_periods) { return ((n_periods + 255) & ~(int64_t)255) + 256; }
-
-
 // ---- streamed path: batch geometry and workspace ---------------------------------------------------------
 // PDC_SL_STREAM_MIN: smallest N that takes the streamed kernels.  Default 262 144 = where the several-slice kernel's
 // bit-plane indices end (same box, reference grid, ms streamed / ms several slices: N = 250 000 x 1000 3.0 / 3.1, x 4096
@@ -2824,17 +2861,8 @@ int64_t duo_bytes(int64_t n_periods) { return ((n_periods + 255) & ~(int64_t)255
 // kernels that give a period to one workgroup lost 0.9 ms and more per call to the ten longest periods of the
 // reference's grid, and the streamed kernels looked better for few periods at any N: a rule by period count was
 // measured, built and withdrawn the same day.)  PDC_SL_STREAM=0 switches the streamed kernels off (A/B, tests).
-int64_t stream_min_n() {
-    static const int64_t v = [] {
-        const char *on = getenv("PDC_SL_STREAM");
-        if (on && on[0] == '0') return (int64_t)1 << 62;
-        const char *e = getenv("PDC_SL_STREAM_MIN");
-        return e ? (int64_t)atoll(e) : (int64_t)262144;
-    }();
-    return v;
-}
 constexpr int64_t kStreamMaxN = (int64_t)(stream::kS1Max - 2) * stream::kMinFill;
-bool stream_takes(int64_t n, int64_t) { return n >= stream_min_n() && n >= 4096 && n <= kStreamMaxN; }
+bool stream_takes(int64_t n) { return n >= knobs().stream_min && n >= 4096 && n <= kStreamMaxN; }
 
 struct StreamShape {
     int s1, batch, groups, tiles_w;
@@ -2855,19 +2883,18 @@ StreamShape stream_shape(int64_t n, int64_t n_periods, bool lists = true) {
     // workgroups, the sort kernel few and long launches; lists mode, 16 / 8 / 4 groups: 37.3 / 35.3 / 35.2 ms at N = 1e6)
     int groups = 1;
     while (groups < 4 && tiles / (2 * groups) >= 16) groups *= 2;
-    static const int env_groups = [] { const char *e = getenv("PDC_SL_STREAM_GROUPS"); return e ? atoi(e) : 0; }();
+    const int env_groups = knobs().stream_groups;
     if (env_groups == 1 || env_groups == 2 || env_groups == 4 || env_groups == 8 || env_groups == 16) groups = env_groups;
     while ((int64_t)h.s1 * groups * 4 > 128 * 1024 && groups > 1) groups /= 2;   // (the bin table kernel's LDS)
     h.groups = groups;
     h.tiles_w = (int)((tiles + groups - 1) / groups);
-    static const int64_t env_batch = [] { const char *e = getenv("PDC_SL_STREAM_BATCH"); return e ? (int64_t)atoll(e) : (int64_t)0; }();
     const int64_t list_bytes = (int64_t)h.s1 * stream::kCap * 20;                 // one period's lists
     const double scale = work_scale();                                            // (< 1 under a workspace budget)
     int64_t batch = (int64_t)((double)((int64_t)12 << 30) * scale) / list_bytes / 32 * 32;
     batch = batch > 384 ? 384 : (batch < 32 ? (scale < 1.0 ? (int64_t)((double)((int64_t)12 << 30) * scale) / list_bytes : 32) : batch);
     if (!lists) batch = (int64_t)(384.0 * scale);
     batch = batch < 1 ? 1 : batch;
-    if (env_batch > 0) batch = env_batch;
+    if (knobs().stream_batch > 0) batch = knobs().stream_batch;
     batch = batch > n_periods ? n_periods : batch;
     batch = batch < 1 ? 1 : (batch > stream::kBatchMax ? stream::kBatchMax : batch);   // (the sort kernel keeps a prefix over the batch's periods in LDS)
     h.batch = (int)batch;
@@ -2900,9 +2927,6 @@ StreamShape stream_shape(int64_t n, int64_t n_periods, bool lists = true) {
     h.o_rtot = h.o_rhist + up((int64_t)256 * h.ts_tiles * 4);
     h.total = h.o_rtot + 1024;
     return h;
-}
-int64_t stream_bytes(int64_t n, int64_t n_periods, bool lists = true) {
-    return stream_takes(n, n_periods) && n_periods > 0 ? stream_shape(n, n_periods, lists).total : 0;
 }
 
 template <int KMAX, int BLK = duo::kB, int NBL = fast::kNB>
@@ -2948,8 +2972,7 @@ stream::StreamArgs stream_args(const StreamShape &h, char *area, const double *d
     sa.ncyc = reinterpret_cast<int *>(area + h.o_ncyc);
     sa.cyc0 = reinterpret_cast<double *>(area + h.o_cyc0);
     sa.bnd = reinterpret_cast<unsigned *>(area + h.o_bnd);
-    static const bool slices = [] { const char *e = getenv("PDC_SL_SLICES"); return !(e && e[0] == '0'); }();
-    sa.slices = slices ? 1 : 0;
+    sa.slices = knobs().slices ? 1 : 0;
     sa.direct = sa.slices;
     sa.no_lists = 0;
     sa.sorted = nullptr;
@@ -2969,24 +2992,16 @@ stream::StreamArgs stream_args(const StreamShape &h, char *area, const double *d
 constexpr int kHintLists = 1;     // the workspace holds the streamed kernels' bin lists
 constexpr int kHintOrdered = 2;   // t is non-decreasing: no time sort to launch
 
-// PDC_SL_TIMESORT=0: samples in any order take the lists mode as up to round 4 (A/B, tests)
-bool timesort_on() {
-    static const bool on = [] {
-        const char *e = getenv("PDC_SL_TIMESORT"), *s = getenv("PDC_SL_SLICES");
-        return !(e && e[0] == '0') && !(s && s[0] == '0');
-    }();
-    return on;
-}
-
 // The streamed kernels' intake: sl_tame_kernel looks at t (tame? in order?) and writes the (t, m) records; samples that
 // may be in any order are copied, ordered by time on the device if the kernel found them out of order (timesort.inc -
 // every launch of it returns at once otherwise) and the kernels downstream read the copies (sa.t / sa.m).
+// PDC_SL_TIMESORT=0: samples in any order take the lists mode as up to round 4 (A/B, tests).
 int stream_intake(hipStream_t st, const StreamShape &h, char *area, const double *d_t, const double *d_m, int64_t n, int hints,
                   stream::StreamArgs &sa) {
     unsigned *bad = const_cast<unsigned *>(sa.bad_t);
     fast::rec_t *tm = const_cast<fast::rec_t *>(sa.tm);
     PDC_HIP(hipMemsetAsync(area + h.o_bad, 0, 256, st));
-    if ((hints & kHintOrdered) != 0 || !timesort_on()) {
+    if ((hints & kHintOrdered) != 0 || !knobs().timesort) {
         hipLaunchKernelGGL(stream::sl_tame_kernel, dim3(512), dim3(256), 0, st, d_t, d_m, tm, static_cast<double *>(nullptr),
                            static_cast<double *>(nullptr), n, bad);
         PDC_HIP(hipGetLastError());
@@ -3053,7 +3068,136 @@ int stream_allow_lds(const StreamShape &h) {
     return PDC_OK;
 }
 
-// ---- Supersmoother: workspace -----------------------------------------------------------------------------
+// ---- the StringLength workspace: one area after the other, byte offsets from its base ------------------------------
+// The general / fast kernels' scratch for `grid` resident workgroups (every sub-array [grid][..]), the fast kernels'
+// AoS (t, m) records + flags, the duo kernel's marks + tickets, the one-cycle marks / list / flags, the streamed
+// kernels' area (StreamShape h, from o_stream).  sort = true: the Supersmoother's sort with the fast kernels' EMIT
+// instances - the same pieces for a batch of periods, no duo or streamed area, a dummy length per period at the end.
+struct SlLayout {
+    int64_t grid, n_pad, nr_pad;
+    int64_t wg_scratch;                                             // one workgroup's share of the scratch
+    int64_t o_gkeys, o_rsum, o_gidx, o_rcnt, o_rlen, o_gorder, o_ghist;
+    int64_t o_rec, o_flags;                                         // (t, m) table
+    int64_t o_todo, o_ticket;                                       // duo
+    int64_t o_skip, o_list, o_bad, o_count;                         // one-cycle (o_bad: sl_tame_kernel's flags)
+    int64_t o_ell;                                                  // (sort) dummy lengths
+    int64_t o_stream;
+    bool streamed;
+    StreamShape h;
+    int64_t total;
+};
+SlLayout sl_layout(int64_t n, int64_t n_periods, bool lists, bool sort = false) {
+    auto up = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
+    SlLayout l{};
+    l.grid = grid_for(n_periods > 0 ? n_periods : 1);
+    l.n_pad = pad_pow2(n);
+    l.nr_pad = range_slots(n);
+    // (above the smaller of the two slice capacities the kernels may need the per-period partition: gorder, ghist)
+    const bool partition = n > Lds<unsigned>::capacity;
+    int64_t w = 0;
+    auto sub = [&](int64_t bytes) { const int64_t o = l.grid * w; w += bytes; return o; };
+    l.o_gkeys = sub(l.n_pad * 8);
+    l.o_rsum = sub(l.nr_pad * 32);
+    l.o_gidx = sub(l.n_pad * 4);
+    l.o_rcnt = sub(l.nr_pad * 4);
+    l.o_rlen = sub(l.nr_pad * 8);
+    l.o_gorder = sub(partition ? l.n_pad * 4 : 0);
+    l.o_ghist = sub(partition ? kBucketsLarge * 4 : 0);
+    l.wg_scratch = w;
+    l.o_rec = l.grid * w + 512;
+    l.o_flags = l.o_rec + up(n * 16);
+    int64_t at = l.o_flags + 256;
+    if (!sort) {
+        l.o_todo = at;
+        l.o_ticket = l.o_todo + up(n_periods);
+        at = l.o_ticket + 256;
+    }
+    l.o_skip = at;
+    l.o_list = l.o_skip + up(n_periods);
+    l.o_bad = l.o_list + up(n_periods * 4);
+    l.o_count = l.o_bad + (sort ? 0 : 256);   // (the Supersmoother brings its own sl_tame_kernel flags)
+    at = l.o_bad + 512;
+    if (sort) {
+        l.o_ell = at;
+        l.total = l.o_ell + up(n_periods * 8) + 256;
+        return l;
+    }
+    l.o_stream = at;
+    l.streamed = stream_takes(n) && n_periods > 0;
+    if (l.streamed) l.h = stream_shape(n, n_periods, lists);
+    l.total = l.o_stream + (l.streamed ? l.h.total : 0);
+    return l;
+}
+
+template <typename T>
+T *ptr(char *base, int64_t offset) { return reinterpret_cast<T *>(base + offset); }
+
+SlArgs sl_args(const SlLayout &l, char *base, const double *t, const double *m, const double *periods, int64_t n,
+               int64_t n_periods, double *ell) {
+    SlArgs a;
+    a.t = t;
+    a.m = m;
+    a.periods = periods;
+    a.n = n;
+    a.n_periods = n_periods;
+    a.ell = ell;
+    a.n_pad = l.n_pad;
+    a.nr_pad = l.nr_pad;
+    a.gkeys = ptr<unsigned long long>(base, l.o_gkeys);
+    a.rsum = ptr<double>(base, l.o_rsum);
+    a.gidx = ptr<unsigned>(base, l.o_gidx);
+    a.rcnt = ptr<int>(base, l.o_rcnt);
+    a.gorder = ptr<unsigned>(base, l.o_gorder);
+    a.ghist = ptr<unsigned>(base, l.o_ghist);
+    return a;
+}
+
+fast::FastArgs fast_args(const SlLayout &l, char *base, const double *t, const double *m, const double *periods, int64_t n,
+                         int64_t n_periods, double *ell) {
+    fast::FastArgs f{};
+    f.t = t;
+    f.m = m;
+    f.periods = periods;
+    f.n = n;
+    f.n_periods = n_periods;
+    f.ell = ell;
+    f.n_pad = l.n_pad;
+    f.nr_pad = l.nr_pad;
+    f.gkeys = ptr<unsigned long long>(base, l.o_gkeys);
+    f.rsum = ptr<double>(base, l.o_rsum);
+    f.gidx = ptr<unsigned>(base, l.o_gidx);
+    f.rcnt = ptr<int>(base, l.o_rcnt);
+    f.rlen = ptr<double>(base, l.o_rlen);
+    f.gbucket = ptr<unsigned short>(base, l.o_gorder);   // (the general kernel's grouping area: [grid][n_pad] words)
+    f.ghist = ptr<unsigned>(base, l.o_ghist);
+    f.rec = ptr<const fast::rec_t>(base, l.o_rec);
+    f.flags = ptr<const unsigned>(base, l.o_flags);
+    f.slice_cap = fast::FL<unsigned>::capacity;
+    return f;
+}
+
+onecycle::OneArgs onecycle_args(const SlLayout &l, char *base, const double *t, const double *m, const double *periods,
+                                int64_t n, int64_t n_periods, const unsigned *bad, double *ell) {
+    onecycle::OneArgs o;
+    o.t = t;
+    o.m = m;
+    o.periods = periods;
+    o.n = n;
+    o.n_periods = n_periods;
+    o.bad = bad;
+    o.skip = ptr<unsigned char>(base, l.o_skip);
+    o.list = ptr<unsigned>(base, l.o_list);
+    o.count = ptr<unsigned>(base, l.o_count);
+    o.ell = ell;
+    return o;
+}
+
+// once per call: the AoS (t, m) table + its flags
+void launch_prep(hipStream_t st, const SlLayout &l, char *base, const double *d_t, const double *d_m, int64_t n) {
+    hipLaunchKernelGGL(fast::sl_prep_kernel, dim3(1), dim3(kBlock), 0, st, d_t, d_m, (int)n, ptr<fast::rec_t>(base, l.o_rec),
+                       ptr<unsigned>(base, l.o_flags));
+}
+
 template <int KMAX, typename IdxT = unsigned short, int NB = fast::kNB, bool MULTI = false, int PL = 0, bool EMIT = false>
 int launch_fast(const fast::FastArgs &a, int64_t grid, hipStream_t st) {
     constexpr bool P17 = PL > 0;
@@ -3067,107 +3211,79 @@ int launch_fast(const fast::FastArgs &a, int64_t grid, hipStream_t st) {
     return PDC_OK;
 }
 
-// ---- the one-workgroup-per-period kernels as a SORT (EMIT instances of sl_fast_kernel): the Supersmoother's sorted
-// curves below the streamed kernels' range.  Workspace per batch: the kernels' scratch for grid_for(batch)
-// workgroups, the (t, y) table, the one-cycle marks, a dummy length per period.
-bool fast_sort_takes(int64_t n) {
-    static const int max_slices = [] { const char *e = getenv("PDC_SL_FAST_SLICES"); return e ? atoi(e) : 16; }();
-    static const bool on = [] { const char *e = getenv("PDC_SS_FASTSORT"); return !(e && e[0] == '0'); }();
-    return on && n >= 64 && n < stream_min_n() && n <= max_slices * (int64_t)fast::FL<unsigned>::capacity;
-}
-int64_t fast_sort_bytes(int64_t n, int64_t batch) {
-    const int64_t partition = may_need_partition(n) ? pad_pow2(n) * 4 + kBucketsLarge * 4 : 0;
-    return scratch_bytes(n, batch, partition) + fast_table_bytes(n) + onecycle_bytes(batch) + ((batch * 8 + 255) & ~(int64_t)255) + 256;
-}
-// once per call: the AoS (t, y) table + its flags
-void fast_sort_prepare(hipStream_t st, const double *d_t, const double *d_y, int64_t n, int64_t batch, void *work) {
-    const int64_t partition = may_need_partition(n) ? pad_pow2(n) * 4 + kBucketsLarge * 4 : 0;
-    char *table = static_cast<char *>(work) + scratch_bytes(n, batch, partition);
-    hipLaunchKernelGGL(fast::sl_prep_kernel, dim3(1), dim3(kBlock), 0, st, d_t, d_y, (int)n, reinterpret_cast<fast::rec_t *>(table),
-                       reinterpret_cast<unsigned *>(table + ((n * 16 + 255) & ~(int64_t)255)));
-}
-// one batch: periods d_periods[0 .. bc) -> sorted[q][n]; skip_out = the one-cycle marks (those rows are NOT written here)
-int fast_sort_batch(hipStream_t st, const double *d_t, const double *d_y, int64_t n, const double *d_periods, int64_t bc,
-                    int64_t batch, const unsigned *bad, fast::rec_t *sorted, void *work, const unsigned char **skip_out) {
-    const int64_t grid = grid_for(bc);
-    const int64_t n_pad = pad_pow2(n), nr_pad = range_slots(n);
-    const int64_t gridc = grid_for(batch);            // (the layout is that of a full batch)
-    const int64_t partition = may_need_partition(n) ? n_pad * 4 + kBucketsLarge * 4 : 0;
-    fast::FastArgs f;
-    f.t = d_t;
-    f.m = d_y;
-    f.periods = d_periods;
-    f.n = n;
-    f.n_periods = bc;
-    f.n_pad = n_pad;
-    f.nr_pad = nr_pad;
-    f.gkeys = reinterpret_cast<unsigned long long *>(work);
-    f.rsum = reinterpret_cast<double *>(f.gkeys + gridc * n_pad);
-    f.gidx = reinterpret_cast<unsigned *>(f.rsum + gridc * nr_pad * 4);
-    f.rcnt = reinterpret_cast<int *>(f.gidx + gridc * n_pad);
-    f.rlen = reinterpret_cast<double *>(f.rcnt + gridc * nr_pad);
-    unsigned *gorder = reinterpret_cast<unsigned *>(f.rlen + gridc * nr_pad);
-    f.ghist = gorder + (may_need_partition(n) ? gridc * n_pad : 0);
-    f.gbucket = reinterpret_cast<unsigned short *>(gorder);
-    char *table = static_cast<char *>(work) + scratch_bytes(n, batch, partition);
-    f.rec = reinterpret_cast<const fast::rec_t *>(table);
-    f.flags = reinterpret_cast<const unsigned *>(table + ((n * 16 + 255) & ~(int64_t)255));
-    char *oc = table + fast_table_bytes(n);
-    onecycle::OneArgs o;
-    o.t = d_t;
-    o.m = d_y;
-    o.periods = d_periods;
-    o.n = n;
-    o.n_periods = bc;
-    o.bad = bad;
-    o.skip = reinterpret_cast<unsigned char *>(oc);
-    o.list = reinterpret_cast<unsigned *>(oc + ((batch + 255) & ~(int64_t)255));
-    o.count = reinterpret_cast<unsigned *>(oc + ((batch + 255) & ~(int64_t)255) + ((batch * 4 + 255) & ~(int64_t)255));
-    o.ell = nullptr;
-    PDC_HIP(hipMemsetAsync(o.count, 0, 256, st));
-    hipLaunchKernelGGL(onecycle::sl_onecycle_mark_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, o);
-    f.ell = reinterpret_cast<double *>(oc + onecycle_bytes(batch));
-    f.todo = nullptr;
-    f.todo_count = nullptr;
-    f.skip = o.skip;
-    f.sorted = sorted;
-    f.slice_cap = fast::FL<unsigned>::capacity;
-    *skip_out = o.skip;
+// The instance of sl_fast_kernel for f.n samples (EMIT: the Supersmoother's sort).  p17 = false keeps the 17- / 18-bit
+// slices out (PDC_SL_P17=0, StringLength only).
+template <bool EMIT>
+int launch_fast_for(fast::FastArgs f, int64_t grid, hipStream_t st, bool p17) {
+    const int64_t n = f.n;
     const int k = (int)((n + kBlock - 1) / kBlock);
     if (n > fast::kCapacity && n < 65536) {
+        // (sample indices still fit 16 bits: slices of 52 112 instead of 23 976 - two slices, not three)
         f.slice_cap = fast::FL<unsigned short>::capacity;
-        PDC_TRY((launch_fast<4, unsigned short, fast::kNBLarge, true, 0, true>(f, grid, st)));
-    } else if (n > fast::kCapacity && n < 131072) {
-        f.slice_cap = fast::kCapacity17;
-        PDC_TRY((launch_fast<4, unsigned, fast::kNBLarge, true, 1, true>(f, grid, st)));
-    } else if (n > fast::kCapacity && n < 262144) {
-        f.slice_cap = fast::kCapacity18;
-        PDC_TRY((launch_fast<4, unsigned, fast::kNBLarge, true, 2, true>(f, grid, st)));
-    } else if (n > fast::kCapacity) {
-        PDC_TRY((launch_fast<4, unsigned, fast::kNBLarge, true, 0, true>(f, grid, st)));
-    } else if (k <= 8) {
-        PDC_TRY((launch_fast<8, unsigned short, fast::kNB, false, 0, true>(f, grid, st)));
-    } else if (k <= 20) {
-        PDC_TRY((launch_fast<20, unsigned short, fast::kNB, false, 0, true>(f, grid, st)));
-    } else if (k <= 36) {
-        PDC_TRY((launch_fast<36, unsigned short, fast::kNB, false, 0, true>(f, grid, st)));
-    } else {
-        PDC_TRY((launch_fast<fast::kKMax, unsigned short, fast::kNB, false, 0, true>(f, grid, st)));
+        return launch_fast<4, unsigned short, fast::kNBLarge, true, 0, EMIT>(f, grid, st);
     }
+    if (n > fast::kCapacity && n < 262144 && p17) {
+        // (17- / 18-bit sample indices: 16 bits per entry + one / two bit planes - slices of ~45 000 / ~42 700)
+        f.slice_cap = n < 131072 ? fast::kCapacity17 : fast::kCapacity18;
+        return n < 131072 ? launch_fast<4, unsigned, fast::kNBLarge, true, 1, EMIT>(f, grid, st)
+                          : launch_fast<4, unsigned, fast::kNBLarge, true, 2, EMIT>(f, grid, st);
+    }
+    if (n > fast::kCapacity) return launch_fast<4, unsigned, fast::kNBLarge, true, 0, EMIT>(f, grid, st);
+    if (k <= 8) return launch_fast<8, unsigned short, fast::kNB, false, 0, EMIT>(f, grid, st);
+    if (k <= 20) return launch_fast<20, unsigned short, fast::kNB, false, 0, EMIT>(f, grid, st);
+    if (k <= 36) return launch_fast<36, unsigned short, fast::kNB, false, 0, EMIT>(f, grid, st);
+    return launch_fast<fast::kKMax, unsigned short, fast::kNB, false, 0, EMIT>(f, grid, st);
+}
+
+// the general kernel: what the others leave (a.todo) or every period
+int launch_general(const SlArgs &a, int64_t grid, hipStream_t st) {
+    if (a.n < 65536) {
+        using L = Lds<unsigned short>;
+        const int64_t slice = a.n < L::capacity ? a.n : L::capacity;
+        const size_t lds = (size_t)L::fixed + (size_t)((slice + 7) & ~(int64_t)7) * 2;
+        PDC_TRY(allow_dynamic_lds((const void *)sl_scan_kernel<unsigned short, kBuckets>, (int)lds));
+        hipLaunchKernelGGL((sl_scan_kernel<unsigned short, kBuckets>), dim3((unsigned)grid), dim3(kBlock), lds, st, a);
+    } else {
+        using L = Lds<unsigned>;
+        const size_t lds = (size_t)L::fixed + (size_t)L::capacity * 4;
+        PDC_TRY(allow_dynamic_lds((const void *)sl_scan_kernel<unsigned, kBucketsLarge>, (int)lds));
+        hipLaunchKernelGGL((sl_scan_kernel<unsigned, kBucketsLarge>), dim3((unsigned)grid), dim3(kBlock), lds, st, a);
+    }
+    PDC_HIP(hipGetLastError());
     return PDC_OK;
+}
+
+// ---- the one-workgroup-per-period kernels as a SORT (EMIT instances of sl_fast_kernel): the Supersmoother's sorted
+// curves below the streamed kernels' range.  Workspace per batch: sl_layout(n, batch, .., true).
+bool fast_sort_takes(int64_t n) {
+    const Knobs &k = knobs();
+    return k.ss_fastsort && n >= 64 && n < k.stream_min && n <= k.fast_slices * (int64_t)fast::FL<unsigned>::capacity;
+}
+// one batch: periods d_periods[0 .. bc) -> sorted[q][n]; skip_out = the one-cycle marks (those rows are NOT written here)
+int fast_sort_batch(hipStream_t st, const SlLayout &l, char *base, const double *d_t, const double *d_y, int64_t n,
+                    const double *d_periods, int64_t bc, const unsigned *bad, fast::rec_t *sorted, const unsigned char **skip_out) {
+    const onecycle::OneArgs o = onecycle_args(l, base, d_t, d_y, d_periods, n, bc, bad, nullptr);
+    PDC_HIP(hipMemsetAsync(o.count, 0, 256, st));
+    hipLaunchKernelGGL(onecycle::sl_onecycle_mark_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, st, o);
+    fast::FastArgs f = fast_args(l, base, d_t, d_y, d_periods, n, bc, ptr<double>(base, l.o_ell));
+    f.skip = o.skip;
+    f.sorted = sorted;
+    *skip_out = o.skip;
+    return launch_fast_for<true>(f, grid_for(bc), st, true);   // (the layout is that of a full batch)
 }
 
 struct SsShape {
     StreamShape h;
+    SlLayout fs;   // (fastsort) the sort's area, at the workspace's start
     bool streamed, tiled, fastsort;
     int batch, grid_ss, grid_fb, sb, seg, seg_len, seg34, seg_len34;
-    int64_t stride, n_pad, o_sorted, o_scratch, o_gk, o_gi, o_bad, o_sm, o_arec, o_srec, o_flag, o_part, o_fast, total;
+    int64_t stride, n_pad, o_sorted, o_scratch, o_gk, o_gi, o_bad, o_sm, o_arec, o_srec, o_flag, o_part, total;
 };
 SsShape ss_shape(int64_t n, int64_t n_periods, bool lists = true) {
     auto up = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
-    SsShape z;
+    const Knobs &k = knobs();
+    SsShape z{};
     z.fastsort = fast_sort_takes(n);
-    z.o_fast = 0;
     z.streamed = !z.fastsort && n >= 4096 && n <= kStreamMaxN;
     z.tiled = n >= ss2::kMinN && n <= ss2::kMaxN;
     // the sorted batch - 16 bytes a point and period - stays within 2 GB (batches of >= 8 periods)
@@ -3176,23 +3292,20 @@ SsShape ss_shape(int64_t n, int64_t n_periods, bool lists = true) {
     cap = cap < 8 ? 8 : cap;
     // (the bin lists of the streamed sort take ~49 bytes per point and period: ~350 MB of them - 136 periods at
     // n = 5e4 -, but at least one full sub-batch of the smoother, and the streamed kernels' own 384 from n = 18 000 down)
-    static const int64_t env_cap = [] { const char *e = getenv("PDC_SS_BATCH"); return e ? (int64_t)atoll(e) : (int64_t)0; }();
     int64_t sub = (int64_t)((double)((int64_t)3 << 29) * scale) / (72 * (n > 0 ? n : 1)) / 8 * 8;     // the smoother's sub-batch (below)
-    static const int64_t env_submax = [] { const char *e = getenv("PDC_SS_SUBMAX"); return e ? (int64_t)atoll(e) : (int64_t)0; }();
-    const int64_t sub_max = env_submax >= 8 ? env_submax : (n >= 40000 ? ss2::kSubBatch : (n >= 10000 ? 128 : 384));
+    const int64_t sub_max = k.ss_submax >= 8 ? k.ss_submax : (n >= 40000 ? ss2::kSubBatch : (n >= 10000 ? 128 : 384));
     sub = sub < 8 ? 8 : (sub > sub_max ? sub_max : sub);
     int64_t list_cap = (int64_t)(7000000.0 * scale) / (n > 0 ? n : 1);
     list_cap = list_cap < sub ? sub : (list_cap > 384 ? 384 : list_cap / sub * sub);
     if (z.fastsort) {
         // (no lists: one workgroup per period - 256 periods a launch fill the CUs - within ~600 MB of sorted curves
         // + the kernels' per-workgroup scratch, and at least one sub-batch of the smoother)
-        const int64_t partition = may_need_partition(n) ? pad_pow2(n) * 4 + kBucketsLarge * 4 : 0;
-        const int64_t per = 16 * n + pad_pow2(n) * 12 + range_slots(n) * 44 + partition;
+        const int64_t per = 16 * n + sl_layout(n, 1, false, true).wg_scratch;
         int64_t b = (int64_t)((double)((int64_t)600 << 20) * scale) / per;
         b = b > 256 ? 256 : b;
         list_cap = b / sub * sub > 0 ? b / sub * sub : sub;
     }
-    if (env_cap > 0) list_cap = env_cap;
+    if (k.ss_batch > 0) list_cap = k.ss_batch;
     cap = cap < list_cap ? cap : list_cap;
     int64_t at = 0;
     if (z.streamed) {
@@ -3200,13 +3313,12 @@ SsShape ss_shape(int64_t n, int64_t n_periods, bool lists = true) {
         z.batch = z.h.batch;
         at = up(z.h.total);
     } else {
-        z.h = StreamShape{};
         int64_t b = n_periods < 512 ? n_periods : 512;
         b = b < cap ? b : cap;
         z.batch = (int)(b < 1 ? 1 : b);
         if (z.fastsort) {
-            z.o_fast = 0;
-            at = (fast_sort_bytes(n, z.batch) + 255) & ~(int64_t)255;
+            z.fs = sl_layout(n, z.batch, false, true);
+            at = up(z.fs.total);
         }
     }
     z.stride = (n + n / 2 + 24 + 7) & ~(int64_t)7;   // (prefix arrays run over the curve extended by a quarter on either side)
@@ -3225,9 +3337,7 @@ SsShape ss_shape(int64_t n, int64_t n_periods, bool lists = true) {
     // tiled smoother: sub-batches of <= 64 periods from n = 4e4 on (short curves take more per launch - a period of
     // 4096 points is three tiles), 72 bytes of intermediates per point and period within 1.5 GB
     int64_t sb = sub < z.batch ? sub : (z.batch + 7) / 8 * 8;
-    static const int env_sb = [] { const char *e = getenv("PDC_SS_SB"); return e ? atoi(e) : 0; }();
-    static const int env_seg = [] { const char *e = getenv("PDC_SS_SEG"); return e ? atoi(e) : 0; }();
-    if (env_sb >= 8 && env_sb % 8 == 0 && env_sb < sb) sb = env_sb;
+    if (k.ss_sb >= 8 && k.ss_sb % 8 == 0 && k.ss_sb < sb) sb = k.ss_sb;
     z.sb = (int)sb;
     const int64_t tiles = (n + ss2::kSegUnit - 1) / ss2::kSegUnit;
     // one workgroup per CU in the first two sweeps: 256 / sub-batch segments, at least 4 (measured at n = 5e4, 64
@@ -3235,11 +3345,10 @@ SsShape ss_shape(int64_t n, int64_t n_periods, bool lists = true) {
     // directly, ~15 us of a workgroup's ~60), 16 at n = 1e6 where a sub-batch is 16 periods
     int seg_rule = (int)((256 + sb - 1) / sb);
     seg_rule = seg_rule < 4 ? 4 : (seg_rule > ss2::kSegMax ? ss2::kSegMax : seg_rule);
-    const int seg_max = env_seg >= 1 && env_seg <= ss2::kSegMax ? env_seg : seg_rule;
+    const int seg_max = k.ss_seg >= 1 && k.ss_seg <= ss2::kSegMax ? k.ss_seg : seg_rule;
     z.seg = (int)(tiles < seg_max ? (tiles < 1 ? 1 : tiles) : seg_max);
     z.seg_len = (int)((tiles + z.seg - 1) / z.seg * ss2::kSegUnit);
-    static const int env_seg34 = [] { const char *e = getenv("PDC_SS_SEG34"); return e ? atoi(e) : 0; }();
-    const int seg34_max = env_seg34 >= 1 && env_seg34 <= ss2::kSegMax ? env_seg34 : z.seg;
+    const int seg34_max = k.ss_seg34 >= 1 && k.ss_seg34 <= ss2::kSegMax ? k.ss_seg34 : z.seg;
     z.seg34 = (int)(tiles < seg34_max ? (tiles < 1 ? 1 : tiles) : seg34_max);
     z.seg_len34 = (int)((tiles + z.seg34 - 1) / z.seg34 * ss2::kSegUnit);
     z.o_sorted = at;
@@ -3256,19 +3365,13 @@ SsShape ss_shape(int64_t n, int64_t n_periods, bool lists = true) {
     return z;
 }
 
-
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
 int64_t stringlength_work_bytes(int64_t n, int64_t n_periods, bool lists) {
     if (n < 0 || n_periods < 0) return -1;
-    const int64_t partition = may_need_partition(n) ? pad_pow2(n) * 4 + kBucketsLarge * 4 : 0;
-    return scratch_bytes(n, n_periods, partition) + fast_table_bytes(n) + duo_bytes(n_periods) + onecycle_bytes(n_periods) +
-           stream_bytes(n, n_periods, lists);
+    return sl_layout(n, n_periods, lists).total;
+}
+// kind 3 = StringLength, 5 = Supersmoother
+int64_t sorted_scan_bytes(int kind, int64_t n, int64_t n_periods, bool lists) {
+    return kind == 5 ? ss_shape(n, n_periods, lists).total : stringlength_work_bytes(n, n_periods, lists);
 }
 
 // Host-side test for pdc_stringlength_scan (host arrays in hand): will EVERY period take the slices or the one-cycle
@@ -3279,9 +3382,8 @@ int64_t stringlength_work_bytes(int64_t n, int64_t n_periods, bool lists) {
 // first (timesort.inc), so the same test applies with the smallest / largest time stamp in place of the first / last -
 // unless some time stamp is not tame (NaN, infinite, beyond 1e+-150: no time sort, lists mode as it stands).
 bool host_all_slices(const double *t, int64_t n, const double *periods, int64_t n_periods, int64_t min_n, bool *ordered) {
-    static const bool on = [] { const char *e = getenv("PDC_SL_SLICES"); return !(e && e[0] == '0'); }();
     *ordered = false;
-    if (!on || n < min_n || n < 4096 || n > kStreamMaxN || n_periods < 1) return false;
+    if (!knobs().slices || n < min_n || n < 4096 || n > kStreamMaxN || n_periods < 1) return false;
     bool in_order = true, tame = true;
     double lo = t[0], hi = t[0];
     for (int64_t i = 0; i < n; ++i) {
@@ -3292,7 +3394,7 @@ bool host_all_slices(const double *t, int64_t n, const double *periods, int64_t 
         hi = v > hi ? v : hi;
     }
     *ordered = in_order;
-    if (!in_order && !(tame && timesort_on() && n >= stream_min_n())) return false;
+    if (!in_order && !(tame && knobs().timesort && n >= knobs().stream_min)) return false;
     const double s1 = (double)stream_shape(n, n_periods, false).s1;
     for (int64_t p = 0; p < n_periods; ++p) {
         const double period = periods[p];
@@ -3308,27 +3410,109 @@ int host_hints(const double *t, int64_t n, const double *periods, int64_t n_peri
     return (all_slices ? 0 : kHintLists) | (ordered ? kHintOrdered : 0);
 }
 
-int stringlength_scan_impl(int device, void *stream, const double *d_t, const double *d_m,
-                           int64_t n, const double *d_periods, int64_t n_periods, double *d_ell,
-                           void *work, int64_t work_bytes, int hints);
-}  // namespace
-
-extern "C" {
-
-int64_t pdc_stringlength_work_bytes(int64_t n, int64_t n_periods) {
-    WorkScale ws(work_budget(), [&] { return stringlength_work_bytes(n, n_periods, true); });   // (PDC_WORK_BUDGET_GB)
-    return ws.need;
+// PDC_SL_STREAM_DEBUG=1: the streamed geometry and the periods left to the general kernel, with their flag bits
+int stream_debug_dump(hipStream_t st, const StreamShape &h, const stream::StreamArgs &sa, int64_t n, int64_t n_periods,
+                      const double *d_periods) {
+    unsigned left = 0;
+    PDC_HIP(hipStreamSynchronize(st));
+    PDC_HIP(hipMemcpy(&left, sa.todo_count, 4, hipMemcpyDeviceToHost));
+    fprintf(stderr, "sl stream: n=%lld periods=%lld s1=%d groups=%d tiles_w=%d batch=%d -> %u periods left to the general kernel\n",
+            (long long)n, (long long)n_periods, h.s1, h.groups, h.tiles_w, h.batch, left);
+    if (left) {
+        std::vector<unsigned char> td((size_t)n_periods);
+        std::vector<double> pp((size_t)n_periods);
+        PDC_HIP(hipMemcpy(td.data(), sa.todo, (size_t)n_periods, hipMemcpyDeviceToHost));
+        PDC_HIP(hipMemcpy(pp.data(), d_periods, (size_t)n_periods * 8, hipMemcpyDeviceToHost));
+        for (int64_t p = 0, shown = 0; p < n_periods && shown < 16; ++p)
+            if (td[p]) {
+                fprintf(stderr, "   period %lld = %.17g: flag bits 0x%x\n", (long long)p, pp[p], td[p] & 0x7f);
+                ++shown;
+            }
+    }
+    return PDC_OK;
 }
 
-int pdc_stringlength_scan_dev(int device, void *stream, const double *d_t, const double *d_m,
-                              int64_t n, const double *d_periods, int64_t n_periods, double *d_ell,
-                              void *work, int64_t work_bytes) {
-    return stringlength_scan_impl(device, stream, d_t, d_m, n, d_periods, n_periods, d_ell, work, work_bytes, kHintLists);
+// ---- streamed path: histogram -> bin table -> partition -> sort every bin in LDS -> link, batch by batch ----
+int sl_streamed(int device, hipStream_t st, const SlLayout &l, char *base, SlArgs a, int hints) {
+    const StreamShape &h = l.h;
+    char *area = base + l.o_stream;
+    stream::StreamArgs sa = stream_args(h, area, a.t, a.m, a.periods, a.n, a.ell);
+    sa.no_lists = (hints & kHintLists) != 0 ? 0 : 1;
+    PDC_HIP(hipMemsetAsync(sa.todo_count, 0, 256, st));
+    PDC_TRY(stream_intake(st, h, area, a.t, a.m, a.n, hints, sa));
+    a.t = sa.t;     // (the general kernel's few periods see the samples the streamed kernels saw: one tie order)
+    a.m = sa.m;
+    PDC_TRY(stream_allow_lds(h));
+    for (int64_t p0 = 0; p0 < a.n_periods; p0 += h.batch) {
+        const int64_t bc = a.n_periods - p0 < h.batch ? a.n_periods - p0 : h.batch;
+        PDC_TRY(stream_sort_batch(device, st, h, sa, p0, bc));
+        hipLaunchKernelGGL(stream::sl_link_kernel, dim3((unsigned)((bc + 3) / 4)), dim3(256), 0, st, sa);
+        PDC_HIP(hipGetLastError());
+    }
+    if (knobs().stream_debug) PDC_TRY(stream_debug_dump(st, h, sa, a.n, a.n_periods, a.periods));
+    // the periods a coarse bucket was too heavy in (clustered phases): the general kernel, which sorts what LDS
+    // cannot hold
+    a.todo = sa.todo;
+    a.todo_count = sa.todo_count;
+    return launch_general(a, l.grid, st);
 }
 
-}  // extern "C"
+// ---- periods of one cycle: summed as the samples stand, passed over by the kernels behind (namespace onecycle) ----
+int sl_onecycle(hipStream_t st, const SlLayout &l, char *base, SlArgs &a) {
+    unsigned *flags = ptr<unsigned>(base, l.o_bad);
+    const onecycle::OneArgs o = onecycle_args(l, base, a.t, a.m, a.periods, a.n, a.n_periods, flags, a.ell);
+    PDC_HIP(hipMemsetAsync(flags, 0, 512, st));
+    hipLaunchKernelGGL(stream::sl_tame_kernel, dim3(a.n < 65536 ? 64 : 512), dim3(256), 0, st, a.t, a.m,
+                       static_cast<fast::rec_t *>(nullptr), static_cast<double *>(nullptr), static_cast<double *>(nullptr), a.n, flags);
+    hipLaunchKernelGGL(onecycle::sl_onecycle_mark_kernel, dim3((unsigned)((a.n_periods + 255) / 256)), dim3(256), 0, st, o);
+    hipLaunchKernelGGL(onecycle::sl_onecycle_kernel, dim3(64), dim3(kBlock), 0, st, o);
+    a.skip = o.skip;
+    return PDC_OK;
+}
 
-namespace {
+// ---- the fast kernels: two (four) workgroups per CU when a period's permutation fits half (a quarter) of LDS, the
+// one-workgroup kernel for the rest and for larger N ----
+int sl_fast(int device, hipStream_t st, const SlLayout &l, char *base, const SlArgs &a) {
+    const Knobs &k = knobs();
+    const int64_t n = a.n;
+    fast::FastArgs f = fast_args(l, base, a.t, a.m, a.periods, n, a.n_periods, a.ell);
+    f.skip = a.skip;
+    launch_prep(st, l, base, a.t, a.m, n);
+    // PDC_SL_DUO=0 keeps the one-workgroup kernel (A/B, tests)
+    if (k.duo && n <= duo::kCapD) {
+        duo::DuoArgs d;
+        d.t = a.t;
+        d.m = a.m;
+        d.periods = a.periods;
+        d.rec = f.rec;
+        d.flags = f.flags;
+        d.n = (int)n;
+        d.n_periods = a.n_periods;
+        d.ell = a.ell;
+        d.todo = ptr<unsigned char>(base, l.o_todo);
+        d.skip = a.skip;
+        d.ticket = ptr<unsigned>(base, l.o_ticket);
+        d.rsum = f.rsum;
+        d.rcnt = f.rcnt;
+        d.rlen = f.rlen;
+        d.nr_pad = f.nr_pad;
+        const bool quad = k.quad && n <= duo::kCapQ;   // four 256-thread workgroups per CU
+        int64_t dgrid = (quad ? 4 : 2) * (int64_t)cu_count(device);
+        dgrid = dgrid < l.grid ? dgrid : l.grid;       // (the range scratch is laid out for `grid` workgroups)
+        PDC_HIP(hipMemsetAsync(d.ticket, 0, 8, st));
+        const int kd = (int)((n + duo::kB - 1) / duo::kB);
+        if (quad) PDC_TRY((launch_duo<16, 256, 512>(d, dgrid, st)));
+        else if (kd <= 16) PDC_TRY(launch_duo<16>(d, dgrid, st));
+        else if (kd <= 36) PDC_TRY(launch_duo<36>(d, dgrid, st));
+        else PDC_TRY(launch_duo<52>(d, dgrid, st));
+        f.todo = d.todo;   // the periods the duo kernel marked (clustered phases) go through the one-slice kernel
+        f.todo_count = d.ticket + 1;
+    }
+    PDC_TRY(launch_fast_for<false>(f, l.grid, st, k.p17));
+    PDC_HIP(hipGetLastError());
+    return PDC_OK;
+}
+
 int stringlength_scan_impl(int device, void *stream, const double *d_t, const double *d_m,
                            int64_t n, const double *d_periods, int64_t n_periods, double *d_ell,
                            void *work, int64_t work_bytes, int hints) {
@@ -3344,271 +3528,20 @@ int stringlength_scan_impl(int device, void *stream, const double *d_t, const do
                 (long long)ws.need);
     if (n_periods == 0) return PDC_OK;
     PDC_TRY(use_device(device));
-    const int64_t grid = grid_for(n_periods);
-    SlArgs a;
-    a.t = d_t;
-    a.m = d_m;
-    a.periods = d_periods;
-    a.n = n;
-    a.n_periods = n_periods;
-    a.ell = d_ell;
-    a.n_pad = pad_pow2(n);
-    a.nr_pad = range_slots(n);
-    a.gkeys = reinterpret_cast<unsigned long long *>(work);
-    a.rsum = reinterpret_cast<double *>(a.gkeys + grid * a.n_pad);
-    a.gidx = reinterpret_cast<unsigned *>(a.rsum + grid * a.nr_pad * 4);
-    a.rcnt = reinterpret_cast<int *>(a.gidx + grid * a.n_pad);
-    double *rlen = reinterpret_cast<double *>(a.rcnt + grid * a.nr_pad);   // [grid][nr_pad] (fast kernels)
-    a.gorder = reinterpret_cast<unsigned *>(rlen + grid * a.nr_pad);
-    a.ghist = a.gorder + (may_need_partition(n) ? grid * a.n_pad : 0);
+    const Knobs &k = knobs();
+    const SlLayout l = sl_layout(n, n_periods, lists);
+    char *base = static_cast<char *>(work);
+    SlArgs a = sl_args(l, base, d_t, d_m, d_periods, n, n_periods, d_ell);
     hipStream_t st = (hipStream_t)stream;
-    static const bool general_only = [] { const char *e = getenv("PDC_SL_GENERAL"); return e && e[0] == '1'; }();
-    if (!general_only && stream_takes(n, n_periods)) {
-        // ---- streamed path: histogram -> bin table -> partition -> sort every bin in LDS -> link, batch by batch ----
-        const StreamShape h = stream_shape(n, n_periods, lists);
-        const int64_t partition = may_need_partition(n) ? pad_pow2(n) * 4 + kBucketsLarge * 4 : 0;
-        char *area = static_cast<char *>(work) + scratch_bytes(n, n_periods, partition) + fast_table_bytes(n) +
-                     duo_bytes(n_periods) + onecycle_bytes(n_periods);
-        stream::StreamArgs sa = stream_args(h, area, d_t, d_m, d_periods, n, d_ell);
-        sa.no_lists = lists ? 0 : 1;
-        PDC_HIP(hipMemsetAsync(sa.todo_count, 0, 256, st));
-        PDC_TRY(stream_intake(st, h, area, d_t, d_m, n, hints, sa));
-        a.t = sa.t;     // (the general kernel's few periods see the samples the streamed kernels saw: one tie order)
-        a.m = sa.m;
-        PDC_TRY(stream_allow_lds(h));
-        for (int64_t p0 = 0; p0 < n_periods; p0 += h.batch) {
-            const int64_t bc = n_periods - p0 < h.batch ? n_periods - p0 : h.batch;
-            PDC_TRY(stream_sort_batch(device, st, h, sa, p0, bc));
-            hipLaunchKernelGGL(stream::sl_link_kernel, dim3((unsigned)((bc + 3) / 4)), dim3(256), 0, st, sa);
-            PDC_HIP(hipGetLastError());
-        }
-        static const bool dbg = [] { const char *e = getenv("PDC_SL_STREAM_DEBUG"); return e && e[0] == '1'; }();
-        if (dbg) {
-            unsigned left = 0;
-            PDC_HIP(hipStreamSynchronize(st));
-            PDC_HIP(hipMemcpy(&left, sa.todo_count, 4, hipMemcpyDeviceToHost));
-            fprintf(stderr, "sl stream: n=%lld periods=%lld s1=%d groups=%d tiles_w=%d batch=%d -> %u periods left to the general kernel\n",
-                    (long long)n, (long long)n_periods, h.s1, h.groups, h.tiles_w, h.batch, left);
-            if (left) {
-                std::vector<unsigned char> td((size_t)n_periods);
-                std::vector<double> pp((size_t)n_periods);
-                PDC_HIP(hipMemcpy(td.data(), sa.todo, (size_t)n_periods, hipMemcpyDeviceToHost));
-                PDC_HIP(hipMemcpy(pp.data(), d_periods, (size_t)n_periods * 8, hipMemcpyDeviceToHost));
-                for (int64_t p = 0, shown = 0; p < n_periods && shown < 16; ++p)
-                    if (td[p]) {
-                        fprintf(stderr, "   period %lld = %.17g: flag bits 0x%x\n", (long long)p, pp[p], td[p] & 0x7f);
-                        ++shown;
-                    }
-            }
-        }
-        // the periods a coarse bucket was too heavy in (clustered phases): the general kernel, which sorts what LDS
-        // cannot hold
-        a.todo = sa.todo;
-        a.todo_count = sa.todo_count;
-        if (n < 65536) {
-            using L = Lds<unsigned short>;
-            const int64_t slice = n < L::capacity ? n : L::capacity;
-            const size_t lds = (size_t)L::fixed + (size_t)((slice + 7) & ~(int64_t)7) * 2;
-            PDC_TRY(allow_dynamic_lds((const void *)sl_scan_kernel<unsigned short, kBuckets>, (int)lds));
-            hipLaunchKernelGGL((sl_scan_kernel<unsigned short, kBuckets>), dim3((unsigned)grid), dim3(kBlock), lds, st, a);
-        } else {
-            using L = Lds<unsigned>;
-            const size_t lds = (size_t)L::fixed + (size_t)L::capacity * 4;
-            PDC_TRY(allow_dynamic_lds((const void *)sl_scan_kernel<unsigned, kBucketsLarge>, (int)lds));
-            hipLaunchKernelGGL((sl_scan_kernel<unsigned, kBucketsLarge>), dim3((unsigned)grid), dim3(kBlock), lds, st, a);
-        }
-        PDC_HIP(hipGetLastError());
-        return PDC_OK;
-    }
-    // ---- periods of one cycle: summed as the samples stand, passed over by the kernels below (namespace onecycle) ----
-    static const bool onecycle_on = [] { const char *e = getenv("PDC_SL_SLICES"); return !(e && e[0] == '0'); }();
-    if (onecycle_on && n >= 2) {
-        const int64_t partition = may_need_partition(n) ? pad_pow2(n) * 4 + kBucketsLarge * 4 : 0;
-        char *oc = static_cast<char *>(work) + scratch_bytes(n, n_periods, partition) + fast_table_bytes(n) + duo_bytes(n_periods);
-        onecycle::OneArgs o;
-        o.t = d_t;
-        o.m = d_m;
-        o.periods = d_periods;
-        o.n = n;
-        o.n_periods = n_periods;
-        o.skip = reinterpret_cast<unsigned char *>(oc);
-        o.list = reinterpret_cast<unsigned *>(oc + ((n_periods + 255) & ~(int64_t)255));
-        unsigned *flags = reinterpret_cast<unsigned *>(oc + ((n_periods + 255) & ~(int64_t)255) + ((n_periods * 4 + 255) & ~(int64_t)255));
-        o.bad = flags;
-        o.count = flags + 64;
-        o.ell = d_ell;
-        PDC_HIP(hipMemsetAsync(flags, 0, 512, st));
-        hipLaunchKernelGGL(stream::sl_tame_kernel, dim3(n < 65536 ? 64 : 512), dim3(256), 0, st, d_t, d_m,
-                           static_cast<fast::rec_t *>(nullptr), static_cast<double *>(nullptr), static_cast<double *>(nullptr), n, flags);
-        hipLaunchKernelGGL(onecycle::sl_onecycle_mark_kernel, dim3((unsigned)((n_periods + 255) / 256)), dim3(256), 0, st, o);
-        hipLaunchKernelGGL(onecycle::sl_onecycle_kernel, dim3(64), dim3(kBlock), 0, st, o);
-        a.skip = o.skip;
-    }
+    if (!k.general_only && l.streamed) return sl_streamed(device, st, l, base, a, hints);
+    if (k.slices && n >= 2) PDC_TRY(sl_onecycle(st, l, base, a));
     // beyond ~16 slices the general kernel (one-off grouping of the indices in global scratch) is ahead: the
     // fast kernel's per-slice passes over the bucket ids and its 16-byte gathers (table > L2) grow with N
     // (x 2048 periods: N = 3.3e5 20.5 against 23.2 ms, N = 4.5e5 39.3 against 35.3 ms); PDC_SL_FAST_SLICES moves it
-    static const int max_slices = [] { const char *e = getenv("PDC_SL_FAST_SLICES"); return e ? atoi(e) : 16; }();
-    if (n >= 1 && !general_only && n <= max_slices * (int64_t)fast::FL<unsigned>::capacity) {
-        fast::FastArgs f;
-        f.t = d_t;
-        f.m = d_m;
-        f.periods = d_periods;
-        f.n = n;
-        f.n_periods = n_periods;
-        f.ell = d_ell;
-        f.gkeys = a.gkeys;
-        f.gidx = a.gidx;
-        f.rsum = a.rsum;
-        f.rcnt = a.rcnt;
-        f.rlen = rlen;
-        f.n_pad = a.n_pad;
-        f.nr_pad = a.nr_pad;
-        f.ghist = a.ghist;
-        f.gbucket = reinterpret_cast<unsigned short *>(a.gorder);   // (the general kernel's grouping area: [grid][n_pad] words)
-        const int64_t partition = may_need_partition(n) ? pad_pow2(n) * 4 + kBucketsLarge * 4 : 0;
-        char *table = static_cast<char *>(work) + scratch_bytes(n, n_periods, partition);
-        f.rec = reinterpret_cast<const fast::rec_t *>(table);
-        f.flags = reinterpret_cast<const unsigned *>(table + ((n * 16 + 255) & ~(int64_t)255));
-        hipLaunchKernelGGL(fast::sl_prep_kernel, dim3(1), dim3(kBlock), 0, st, d_t, d_m, (int)n,
-                           reinterpret_cast<fast::rec_t *>(table), const_cast<unsigned *>(f.flags));
-        const int k = (int)((n + kBlock - 1) / kBlock);
-        f.slice_cap = fast::FL<unsigned>::capacity;
-        f.todo = nullptr;
-        f.todo_count = nullptr;
-        f.skip = a.skip;
-        f.sorted = nullptr;
-        // Two workgroups per CU (sl_duo_kernel) whenever a period's permutation fits half of LDS;
-        // PDC_SL_DUO=0 keeps the one-workgroup kernel (A/B, tests)
-        static const bool duo_on = [] { const char *e = getenv("PDC_SL_DUO"); return !(e && e[0] == '0'); }();
-        if (duo_on && n <= duo::kCapD) {
-            duo::DuoArgs d;
-            d.t = d_t;
-            d.m = d_m;
-            d.periods = d_periods;
-            d.rec = f.rec;
-            d.flags = f.flags;
-            d.n = (int)n;
-            d.n_periods = n_periods;
-            d.ell = d_ell;
-            char *area = table + fast_table_bytes(n);
-            unsigned char *todo = reinterpret_cast<unsigned char *>(area);
-            d.todo = todo;
-            d.skip = a.skip;
-            d.ticket = reinterpret_cast<unsigned *>(area + ((n_periods + 255) & ~(int64_t)255));
-            d.rsum = a.rsum;
-            d.rcnt = a.rcnt;
-            d.rlen = rlen;
-            d.nr_pad = a.nr_pad;
-            static const bool quad_on = [] { const char *e = getenv("PDC_SL_QUAD"); return !(e && e[0] == '0'); }();
-            const bool quad = quad_on && n <= duo::kCapQ;   // four 256-thread workgroups per CU
-            int64_t dgrid = (quad ? 4 : 2) * (int64_t)cu_count(device);
-            dgrid = dgrid < grid ? dgrid : grid;       // (the range scratch is laid out for `grid` workgroups)
-            PDC_HIP(hipMemsetAsync(d.ticket, 0, 8, st));
-            const int kd = (int)((n + duo::kB - 1) / duo::kB);
-            if (quad) PDC_TRY((launch_duo<16, 256, 512>(d, dgrid, st)));
-            else if (kd <= 16) PDC_TRY(launch_duo<16>(d, dgrid, st));
-            else if (kd <= 36) PDC_TRY(launch_duo<36>(d, dgrid, st));
-            else PDC_TRY(launch_duo<52>(d, dgrid, st));
-            f.todo = todo;   // the periods the duo kernel marked (clustered phases) go through the one-slice kernel
-            f.todo_count = d.ticket + 1;
-        }
-        if (n > fast::kCapacity && n < 65536) {
-            // (sample indices still fit 16 bits: slices of 52 112 instead of 23 976 - two slices, not three)
-            f.slice_cap = fast::FL<unsigned short>::capacity;
-            PDC_TRY((launch_fast<4, unsigned short, fast::kNBLarge, true>(f, grid, st)));
-        } else if (n > fast::kCapacity && n < 262144) {
-            // (17- / 18-bit sample indices: 16 bits per entry + one / two bit planes - slices of ~45 000 / ~42 700)
-            static const bool p17_on = [] { const char *e = getenv("PDC_SL_P17"); return !(e && e[0] == '0'); }();
-            if (p17_on && n < 131072) {
-                f.slice_cap = fast::kCapacity17;
-                PDC_TRY((launch_fast<4, unsigned, fast::kNBLarge, true, 1>(f, grid, st)));
-            } else if (p17_on) {
-                f.slice_cap = fast::kCapacity18;
-                PDC_TRY((launch_fast<4, unsigned, fast::kNBLarge, true, 2>(f, grid, st)));
-            } else {
-                PDC_TRY((launch_fast<4, unsigned, fast::kNBLarge, true>(f, grid, st)));
-            }
-        } else if (n > fast::kCapacity) PDC_TRY((launch_fast<4, unsigned, fast::kNBLarge, true>(f, grid, st)));
-        else if (k <= 8) PDC_TRY(launch_fast<8>(f, grid, st));
-        else if (k <= 20) PDC_TRY(launch_fast<20>(f, grid, st));
-        else if (k <= 36) PDC_TRY(launch_fast<36>(f, grid, st));
-        else PDC_TRY(launch_fast<fast::kKMax>(f, grid, st));
-    } else if (n < 65536) {
-        using L = Lds<unsigned short>;
-        const int64_t slice = n < L::capacity ? n : L::capacity;
-        const size_t lds = (size_t)L::fixed + (size_t)((slice + 7) & ~(int64_t)7) * 2;
-        PDC_TRY(allow_dynamic_lds((const void *)sl_scan_kernel<unsigned short, kBuckets>, (int)lds));
-        hipLaunchKernelGGL((sl_scan_kernel<unsigned short, kBuckets>), dim3((unsigned)grid), dim3(kBlock), lds, st, a);
-    } else {
-        using L = Lds<unsigned>;
-        const size_t lds = (size_t)L::fixed + (size_t)L::capacity * 4;
-        PDC_TRY(allow_dynamic_lds((const void *)sl_scan_kernel<unsigned, kBucketsLarge>, (int)lds));
-        hipLaunchKernelGGL((sl_scan_kernel<unsigned, kBucketsLarge>), dim3((unsigned)grid), dim3(kBlock), lds, st, a);
-    }
-    PDC_HIP(hipGetLastError());
-    return PDC_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int pdc_stringlength_scan(const double *t, const double *m, int64_t n, const double *periods,
-                          int64_t n_periods, double *ell_out, int device) {
-    PDC_REQUIRE(t && m && (periods || n_periods == 0) && (ell_out || n_periods == 0),
-                "stringlength: NULL argument");
-    PDC_REQUIRE(n >= 0 && n_periods >= 0, "stringlength: negative size");
-    PDC_TRY(use_device(device));
-    DeviceLock lock(device);
-    // (time-ordered samples and periods that all take the slices / one-cycle modes: no lists in the workspace)
-    const int hints = host_hints(t, n, periods, n_periods, stream_min_n());
-    // (the workspace fitted to PDC_WORK_BUDGET_GB and to what the device has free right now)
-    WorkScale ws(host_work_budget(device), [&] { return stringlength_work_bytes(n, n_periods, (hints & kHintLists) != 0); });
-    PDC_REQUIRE_FITS(ws, "stringlength");
-    const int64_t wb = ws.need;
-    void *d_t, *d_m, *d_p, *d_e, *d_w;
-    PDC_TRY(cached(device, SLOT_IN0, n * 8, &d_t));
-    PDC_TRY(cached(device, SLOT_IN1, n * 8, &d_m));
-    PDC_TRY(cached(device, SLOT_IN2, n_periods * 8, &d_p));
-    PDC_TRY(cached(device, SLOT_OUT0, n_periods * 8, &d_e));
-    PDC_TRY(cached(device, SLOT_WORK, wb, &d_w));
-    hipStream_t st = nullptr;
-    PDC_TRY(host_stream(device, &st));
-    PDC_HIP(hipMemcpyAsync(d_t, t, n * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_m, m, n * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_p, periods, n_periods * 8, hipMemcpyHostToDevice, st));
-    PDC_TRY(stringlength_scan_impl(device, st, (double *)d_t, (double *)d_m, n, (double *)d_p,
-                                   n_periods, (double *)d_e, d_w, wb, hints));
-    PDC_HIP(hipMemcpyAsync(ell_out, d_e, n_periods * 8, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipStreamSynchronize(st));
-    return PDC_OK;
+    if (n >= 1 && !k.general_only && n <= k.fast_slices * (int64_t)fast::FL<unsigned>::capacity) return sl_fast(device, st, l, base, a);
+    return launch_general(a, l.grid, st);
 }
 
-// ---- Supersmoother period search (spectral.py:8, a TODO upstream; Friedman 1984 + Reimann 1994) -----------------
-int64_t pdc_supersmoother_work_bytes(int64_t n, int64_t n_periods) {
-    if (n < 0 || n_periods < 0) return -1;
-    WorkScale ws(work_budget(), [&] { return ss_shape(n, n_periods).total; });   // (PDC_WORK_BUDGET_GB)
-    return ws.need;
-}
-
-}  // extern "C"
-
-namespace {
-int supersmoother_scan_impl(int device, void *stream, const double *d_t, const double *d_y, int64_t n,
-                            const double *d_periods, int64_t n_periods, double alpha, double *d_stat, void *work,
-                            int64_t work_bytes, int hints);
-}
-
-extern "C" {
-
-int pdc_supersmoother_scan_dev(int device, void *stream, const double *d_t, const double *d_y, int64_t n,
-                               const double *d_periods, int64_t n_periods, double alpha, double *d_stat, void *work,
-                               int64_t work_bytes) {
-    return supersmoother_scan_impl(device, stream, d_t, d_y, n, d_periods, n_periods, alpha, d_stat, work, work_bytes, kHintLists);
-}
-
-}  // extern "C"
-
-namespace {
 int supersmoother_scan_impl(int device, void *stream, const double *d_t, const double *d_y, int64_t n,
                             const double *d_periods, int64_t n_periods, double alpha, double *d_stat, void *work,
                             int64_t work_bytes, int hints) {
@@ -3651,7 +3584,7 @@ int supersmoother_scan_impl(int device, void *stream, const double *d_t, const d
     fa.n_pad = z.n_pad;
     fa.flag = z.streamed ? sa.flag : nullptr;
     fa.skip8 = nullptr;
-    if (z.fastsort) fast_sort_prepare(st, d_t, d_y, n, z.batch, base + z.o_fast);
+    if (z.fastsort) launch_prep(st, z.fs, base, d_t, d_y, n);
     fa.gkeys = reinterpret_cast<unsigned long long *>(base + z.o_gk);
     fa.gidx = reinterpret_cast<unsigned *>(base + z.o_gi);
     fa.sorted = sorted;
@@ -3684,7 +3617,7 @@ int supersmoother_scan_impl(int device, void *stream, const double *d_t, const d
         if (z.fastsort) {
             // one workgroup per period sorts it in LDS (the StringLength kernels' EMIT instances) and writes the sorted
             // curve; the periods that outlast the samples are marked and written as they stand
-            PDC_TRY(fast_sort_batch(st, d_t, d_y, n, d_periods + p0, bc, z.batch, bad, sorted, base + z.o_fast, &fa.skip8));
+            PDC_TRY(fast_sort_batch(st, z.fs, base, d_t, d_y, n, d_periods + p0, bc, bad, sorted, &fa.skip8));
             hipLaunchKernelGGL(ss::ss_direct_kernel, dim3((unsigned)(bc * 8)), dim3(kBlock), 0, st, fa);
         } else {
             if (z.streamed) PDC_TRY(stream_sort_batch(device, st, z.h, sa, p0, bc));
@@ -3731,41 +3664,8 @@ int supersmoother_scan_impl(int device, void *stream, const double *d_t, const d
     }
     return PDC_OK;
 }
+
 }  // namespace
-
-extern "C" {
-
-int pdc_supersmoother_scan(const double *t, const double *y, int64_t n, const double *periods, int64_t n_periods,
-                           double alpha, double *stat_out, int device) {
-    PDC_REQUIRE(t && y && (periods || n_periods == 0) && (stat_out || n_periods == 0), "supersmoother: NULL argument");
-    PDC_REQUIRE(n >= 0 && n_periods >= 0, "supersmoother: negative size");
-    PDC_TRY(use_device(device));
-    DeviceLock lock(device);
-    // (time-ordered samples and periods that all take the slices mode: no lists in the workspace, as pdc_stringlength_scan)
-    const int hints = host_hints(t, n, periods, n_periods, 4096);
-    // (the workspace fitted to PDC_WORK_BUDGET_GB and to what the device has free right now)
-    WorkScale ws(host_work_budget(device), [&] { return ss_shape(n, n_periods, (hints & kHintLists) != 0).total; });
-    PDC_REQUIRE_FITS(ws, "supersmoother");
-    const int64_t wb = ws.need;
-    void *d_t, *d_y, *d_p, *d_s, *d_w;
-    PDC_TRY(cached(device, SLOT_IN0, n * 8, &d_t));
-    PDC_TRY(cached(device, SLOT_IN1, n * 8, &d_y));
-    PDC_TRY(cached(device, SLOT_IN2, n_periods * 8, &d_p));
-    PDC_TRY(cached(device, SLOT_OUT0, n_periods * 8, &d_s));
-    PDC_TRY(cached(device, SLOT_WORK, wb, &d_w));
-    hipStream_t st = nullptr;
-    PDC_TRY(host_stream(device, &st));
-    PDC_HIP(hipMemcpyAsync(d_t, t, n * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_y, y, n * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_p, periods, n_periods * 8, hipMemcpyHostToDevice, st));
-    PDC_TRY(supersmoother_scan_impl(device, st, (double *)d_t, (double *)d_y, n, (double *)d_p, n_periods, alpha,
-                                    (double *)d_s, d_w, wb, hints));
-    PDC_HIP(hipMemcpyAsync(stat_out, d_s, n_periods * 8, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipStreamSynchronize(st));
-    return PDC_OK;
-}
-
-}  // extern "C"
 
 // The two scans that sort every period by phase, for callers that hold the HOST arrays too (the phase plan of
 // multi.hip): when the host sees that every period will take the slices / one-cycle modes of the streamed kernels the
@@ -3773,12 +3673,12 @@ int pdc_supersmoother_scan(const double *t, const double *y, int64_t n, const do
 // do for themselves.  kind 3 = StringLength, 5 = Supersmoother (alpha).
 namespace pdc {
 int sorted_scan_hints(int kind, const double *t, int64_t n, const double *periods, int64_t n_periods) {
-    return host_hints(t, n, periods, n_periods, kind == 5 ? (int64_t)4096 : stream_min_n());
+    return host_hints(t, n, periods, n_periods, kind == 5 ? (int64_t)4096 : knobs().stream_min);
 }
 int64_t sorted_scan_work_bytes(int kind, int64_t n, int64_t n_periods, int hints) {
     const bool lists = (hints & kHintLists) != 0;
     if (n < 0 || n_periods < 0) return -1;
-    WorkScale ws(work_budget(), [&] { return kind == 5 ? ss_shape(n, n_periods, lists).total : stringlength_work_bytes(n, n_periods, lists); });
+    WorkScale ws(work_budget(), [&] { return sorted_scan_bytes(kind, n, n_periods, lists); });
     return ws.need;   // (may still exceed the budget: the scan itself then says so - PDC_REQUIRE_FITS)
 }
 int sorted_scan_dev(int kind, int device, void *stream, const double *d_t, const double *d_v, int64_t n, const double *d_periods,
@@ -3788,3 +3688,67 @@ int sorted_scan_dev(int kind, int device, void *stream, const double *d_t, const
 }
 }  // namespace pdc
 
+namespace {
+// numpy in, numpy out: stage in, scan, stage out on the device's host stream, with the workspace fitted to
+// PDC_WORK_BUDGET_GB and to what the device has free right now
+int sorted_scan_host(int kind, const double *t, const double *v, int64_t n, const double *periods, int64_t n_periods,
+                     double alpha, double *out, int device) {
+    const char *what = kind == 5 ? "supersmoother" : "stringlength";
+    PDC_REQUIRE(t && v && (periods || n_periods == 0) && (out || n_periods == 0), "%s: NULL argument", what);
+    PDC_REQUIRE(n >= 0 && n_periods >= 0, "%s: negative size", what);
+    PDC_TRY(use_device(device));
+    DeviceLock lock(device);
+    // (time-ordered samples and periods that all take the slices / one-cycle modes: no lists in the workspace)
+    const int hints = sorted_scan_hints(kind, t, n, periods, n_periods);
+    WorkScale ws(host_work_budget(device), [&] { return sorted_scan_bytes(kind, n, n_periods, (hints & kHintLists) != 0); });
+    PDC_REQUIRE_FITS(ws, what);
+    const int64_t wb = ws.need;
+    void *d_t, *d_v, *d_p, *d_o, *d_w;
+    PDC_TRY(cached(device, SLOT_IN0, n * 8, &d_t));
+    PDC_TRY(cached(device, SLOT_IN1, n * 8, &d_v));
+    PDC_TRY(cached(device, SLOT_IN2, n_periods * 8, &d_p));
+    PDC_TRY(cached(device, SLOT_OUT0, n_periods * 8, &d_o));
+    PDC_TRY(cached(device, SLOT_WORK, wb, &d_w));
+    hipStream_t st = nullptr;
+    PDC_TRY(host_stream(device, &st));
+    PDC_HIP(hipMemcpyAsync(d_t, t, n * 8, hipMemcpyHostToDevice, st));
+    PDC_HIP(hipMemcpyAsync(d_v, v, n * 8, hipMemcpyHostToDevice, st));
+    PDC_HIP(hipMemcpyAsync(d_p, periods, n_periods * 8, hipMemcpyHostToDevice, st));
+    PDC_TRY(sorted_scan_dev(kind, device, st, (double *)d_t, (double *)d_v, n, (double *)d_p, n_periods, alpha, (double *)d_o,
+                            d_w, wb, hints));
+    PDC_HIP(hipMemcpyAsync(out, d_o, n_periods * 8, hipMemcpyDeviceToHost, st));
+    PDC_HIP(hipStreamSynchronize(st));
+    return PDC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t pdc_stringlength_work_bytes(int64_t n, int64_t n_periods) { return sorted_scan_work_bytes(3, n, n_periods, kHintLists); }
+
+int pdc_stringlength_scan_dev(int device, void *stream, const double *d_t, const double *d_m,
+                              int64_t n, const double *d_periods, int64_t n_periods, double *d_ell,
+                              void *work, int64_t work_bytes) {
+    return stringlength_scan_impl(device, stream, d_t, d_m, n, d_periods, n_periods, d_ell, work, work_bytes, kHintLists);
+}
+
+int pdc_stringlength_scan(const double *t, const double *m, int64_t n, const double *periods,
+                          int64_t n_periods, double *ell_out, int device) {
+    return sorted_scan_host(3, t, m, n, periods, n_periods, 0.0, ell_out, device);
+}
+
+// ---- Supersmoother period search (spectral.py:8, a TODO upstream; Friedman 1984 + Reimann 1994) -----------------
+int64_t pdc_supersmoother_work_bytes(int64_t n, int64_t n_periods) { return sorted_scan_work_bytes(5, n, n_periods, kHintLists); }
+
+int pdc_supersmoother_scan_dev(int device, void *stream, const double *d_t, const double *d_y, int64_t n,
+                               const double *d_periods, int64_t n_periods, double alpha, double *d_stat, void *work,
+                               int64_t work_bytes) {
+    return supersmoother_scan_impl(device, stream, d_t, d_y, n, d_periods, n_periods, alpha, d_stat, work, work_bytes, kHintLists);
+}
+
+int pdc_supersmoother_scan(const double *t, const double *y, int64_t n, const double *periods, int64_t n_periods,
+                           double alpha, double *stat_out, int device) {
+    return sorted_scan_host(5, t, y, n, periods, n_periods, alpha, stat_out, device);
+}
+
+}  // extern "C"
