@@ -285,6 +285,61 @@ int pdc_gls_batch_peaks(const double *t, const double *y, const double *dy, cons
                         int64_t *count_out, int64_t *idx_out, double *height_out,
                         double *prominence_out, int64_t *half_lo_out, int64_t *half_hi_out, int device);
 
+/* ---- batches of light curves on their OWN grids ("ragged" grids; GLS.batch) ----------------------
+ * Replaces a survey's loop of GLS()(s) (spectral.py:88-132, each curve on the grid its own data give:
+ * df = 1/(baseline n), fmin = df/2, fmax = 0.5/median_dt, :88-97) followed by period_at_highest_peak /
+ * psort_by_* / periods_at_half_max on each result (core.py:944-978).
+ * Curve b owns samples [offsets[b], offsets[b+1]) of t, y and dy (dy NULL: unit errors for every curve)
+ * and the grid f0[b] + j*delta[b], j < nf_b = f_offsets[b+1] - f_offsets[b] (numpy's arange fill rule,
+ * two roundings); its bins are power[f_offsets[b] .. f_offsets[b+1]).  Weights, centring and epilogue are
+ * those of pdc_gls_scan per curve (bits may differ from it by rounding: another tile shape).
+ * offsets[0] == f_offsets[0] == 0, both non-decreasing; f0, delta finite, delta > 0; the grid in tiles of
+ * 1024 bins < 2^31 tiles.  An empty curve gives a NaN row (as pdc_gls_scan), an empty grid no bins
+ * (amax NaN, argmax -1).
+ * Curves are dealt to the `n_devices` listed device slots in contiguous groups balanced by
+ * sum n_b nf_b (a device may be listed more than once); per-slot buffers and streams are kept between
+ * calls (pdc_release frees them).  Each slot's share runs in groups of curves whose buffers fit
+ * PDC_WORK_BUDGET_GB and the slot's share of free device memory: results are bit-identical whatever the
+ * grouping; a budget too small for one curve is PDC_ERR_INVALID and the message names it.
+ *
+ * pdc_gls_scan_ragged: power_out [f_offsets[B]] and/or amax_out / argmax_out [B] (NaN-aware maximum and
+ * its bin within the curve's row: Signal.amax / argmax, core.py:202-215), any of them NULL.
+ *
+ * pdc_gls_ragged_peaks: the peak table of pdc_gls_batch_peaks on every curve's own row: count[B];
+ * idx / height / prominence / half_lo / half_hi [B][k] (k <= 1024), ranked and padded exactly as there,
+ * bins relative to the row; power_out as above, or NULL (the spectra then never leave HBM).  The scan
+ * writes a pitched copy [B][nf_max] whose tail bins [nf_b, nf_max) are NaN and pdc_peaks_topk_dev runs
+ * on it.  The pad keeps scipy's answers for the unpadded row: NaN compares false, so the last real bin
+ * still cannot be a peak and a flat top running into the pad is still none; the right-hand prominence
+ * walk stops at the pad as at the row's end; heights, counts and ranks are unchanged.  The one
+ * artefact is a sign flip of the pair (nf_b - 1, nf_b), which the half-maximum walk may report:
+ * half_lo >= nf_b - 1 is therefore returned as -1 (periods_at_half_max, core.py:975-977, looks only at
+ * pairs inside the row).
+ *
+ * pdc_gls_ragged_work_bytes / pdc_gls_scan_ragged_dev: ONE launch sequence on `device` / `stream`, no
+ * grouping: t, y, dy on the device; offsets, f0, delta, f_offsets on the HOST (the tile tables are built
+ * from them; the entry waits for their upload, and so for the stream's earlier work, before it returns -
+ * the launches themselves are not waited for).  d_power [f_offsets[B]], d_pitched [B][pitch] (its pad is
+ * the caller's), d_amax / d_argmax [B]: any may be NULL, not all.  work_bytes >=
+ * pdc_gls_ragged_work_bytes(offsets[B], B, f_offsets[B], 0, 0); k > 0 and nf_max size the group
+ * workspace of the peak entry (+ the pitched copy and the [B][k] table). */
+int pdc_gls_scan_ragged(const double *t, const double *y, const double *dy, const int64_t *offsets,
+                        int64_t n_curves, const double *f0, const double *delta, const int64_t *f_offsets,
+                        int fit_mean, int psd, double *power_out, double *amax_out, int64_t *argmax_out,
+                        const int *devices, int n_devices);
+int pdc_gls_ragged_peaks(const double *t, const double *y, const double *dy, const int64_t *offsets,
+                         int64_t n_curves, const double *f0, const double *delta, const int64_t *f_offsets,
+                         int fit_mean, int psd, int k, int by_prominence, int64_t *count_out,
+                         int64_t *idx_out, double *height_out, double *prominence_out,
+                         int64_t *half_lo_out, int64_t *half_hi_out, double *power_out,
+                         const int *devices, int n_devices);
+int64_t pdc_gls_ragged_work_bytes(int64_t n_total, int64_t n_curves, int64_t nf_total, int64_t nf_max, int k);
+int pdc_gls_scan_ragged_dev(int device, void *stream, const double *d_t, const double *d_y,
+                            const double *d_dy, const int64_t *offsets, int64_t n_curves,
+                            const double *f0, const double *delta, const int64_t *f_offsets,
+                            int fit_mean, int psd, double *d_power, double *d_pitched, int64_t pitch,
+                            double *d_amax, int64_t *d_argmax, void *work, int64_t work_bytes);
+
 /* ---- Phase Dispersion Minimization -----------------------------------------------------------
  * Replaces pool.map(PDM._pdm, periods) (phase.py:128-149, 185-187): theta_out[p] for every trial
  * period, bins phi in [k/m0, (k+nc)/m0) U [0, (k+nc-m0)/m0), m0 = nb*nc, phi = (t/period) % 1

@@ -81,6 +81,12 @@ PROTOTYPES = {
     "pdc_peaks_topk_dev": (_I, [_I, _VP, _VP, _L, _L, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pdc_gls_batch_peaks": (_I, [_VP, _VP, _VP, _VP, _L, _I, _D, _D, _L, _I, _I, _I, _I,
                                  _VP, _VP, _VP, _VP, _VP, _VP, _I]),
+    "pdc_gls_scan_ragged": (_I, [_VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _I]),
+    "pdc_gls_ragged_peaks": (_I, [_VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _I, _I, _I, _I,
+                                  _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I]),
+    "pdc_gls_ragged_work_bytes": (_L, [_L, _L, _L, _L, _I]),
+    "pdc_gls_scan_ragged_dev": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _I, _I,
+                                     _VP, _VP, _L, _VP, _VP, _VP, _L]),
     "pdc_pdm_scan": (_I, [_VP, _VP, _L, _VP, _L, _I, _I, _D, _VP, _I]),
     "pdc_pdm_scan_dev": (_I, [_I, _VP, _VP, _VP, _L, _VP, _L, _I, _I, _D, _VP]),
     "pdc_aov_scan": (_I, [_VP, _VP, _L, _VP, _L, _I, _VP, _I]),
@@ -506,6 +512,57 @@ def gls_batch_peaks(t, y, dy, offsets, f0, delta, nf, k=1, by_prominence=False, 
                                     int(bool(by_prominence)), _ptr(out["count"]), _ptr(out["indices"]),
                                     _ptr(out["heights"]), _ptr(out["prominences"]), _ptr(out["half_lo"]),
                                     _ptr(out["half_hi"]), dev))
+    return out
+
+
+def _ragged_inputs(t, y, dy, offsets, f0, delta, f_offsets):
+    t, y = _f64(t, "t"), _f64(y, "y")
+    dy = None if dy is None else _f64(dy, "dy")
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    f_offsets = np.ascontiguousarray(f_offsets, dtype=np.int64)
+    f0, delta = _f64(f0, "f0"), _f64(delta, "delta")
+    nb = offsets.size - 1
+    if nb < 1 or f_offsets.size != nb + 1 or f0.size != nb or delta.size != nb:
+        raise ValueError("offsets / f_offsets need n_curves + 1 entries, f0 / delta n_curves")
+    if offsets[-1] != y.size or t.size != y.size or (dy is not None and dy.size != y.size):
+        raise ValueError("Input arrays have incompatible lengths.")
+    return t, y, dy, offsets, f0, delta, f_offsets, nb
+
+
+def _slots(device, devices):
+    if devices is not None and len(devices) > 0:
+        return np.ascontiguousarray(devices, dtype=np.int32)
+    return np.array([default_device() if device is None else device], dtype=np.int32)
+
+
+def gls_scan_ragged(t, y, dy, offsets, f0, delta, f_offsets, fit_mean=True, psd=False, want_power=True,
+                    want_peaks=False, device=None, devices=None):
+    """Batch of curves, each on its own grid ``f0[b] + j*delta[b]``, ``j < f_offsets[b+1] - f_offsets[b]``
+    (``pdc_gls_scan_ragged``): ``(power [f_offsets[-1]] | None, amax [B] | None, argmax [B] | None)``."""
+    t, y, dy, offsets, f0, delta, f_offsets, nb = _ragged_inputs(t, y, dy, offsets, f0, delta, f_offsets)
+    power = np.empty(int(f_offsets[-1]), dtype=np.float64) if want_power else None
+    amax = np.empty(nb, dtype=np.float64) if want_peaks else None
+    argmax = np.empty(nb, dtype=np.int64) if want_peaks else None
+    devs = _slots(device, devices)
+    check(lib().pdc_gls_scan_ragged(_ptr(t), _ptr(y), _ptr(dy), _ptr(offsets), nb, _ptr(f0), _ptr(delta),
+                                    _ptr(f_offsets), int(bool(fit_mean)), int(bool(psd)), _ptr(power), _ptr(amax),
+                                    _ptr(argmax), _ptr(devs), devs.size))
+    return power, amax, argmax
+
+
+def gls_ragged_peaks(t, y, dy, offsets, f0, delta, f_offsets, k=1, by_prominence=False, fit_mean=True, psd=False,
+                     want_power=False, device=None, devices=None):
+    """The peak table of :func:`gls_batch_peaks` on every curve's own grid (``pdc_gls_ragged_peaks``); with
+    ``want_power`` also the spectra (``"power"``, ``[f_offsets[-1]]``)."""
+    t, y, dy, offsets, f0, delta, f_offsets, nb = _ragged_inputs(t, y, dy, offsets, f0, delta, f_offsets)
+    out = _topk_outputs(nb, int(k))
+    out["power"] = np.empty(int(f_offsets[-1]), dtype=np.float64) if want_power else None
+    devs = _slots(device, devices)
+    check(lib().pdc_gls_ragged_peaks(_ptr(t), _ptr(y), _ptr(dy), _ptr(offsets), nb, _ptr(f0), _ptr(delta),
+                                     _ptr(f_offsets), int(bool(fit_mean)), int(bool(psd)), int(k),
+                                     int(bool(by_prominence)), _ptr(out["count"]), _ptr(out["indices"]),
+                                     _ptr(out["heights"]), _ptr(out["prominences"]), _ptr(out["half_lo"]),
+                                     _ptr(out["half_hi"]), _ptr(out["power"]), _ptr(devs), devs.size))
     return out
 
 

@@ -1,0 +1,825 @@
+// GLS over a batch of light curves that each keep their OWN frequency grid ("ragged" grids): GLS.batch.
+//
+// A survey runs GLS()(s) and period_at_highest_peak over a catalogue (reference spectral.py:88-132 per
+// curve, then core.py:944-978 on each result; its own batch is the bootstrap loop at spectral.py:140-152).
+// GLS builds each curve's grid from that curve's data - df = 1/(baseline n), fmin = df/2, fmax =
+// 0.5/median_dt (spectral.py:88-97) - so two curves almost never share one, and the shared-grid batch of
+// gls.hip does not apply.  Here curve b owns samples [offsets[b], offsets[b+1]) and bins
+// f0[b] + j delta[b], j < nf_b = f_offsets[b+1] - f_offsets[b] (numpy's arange fill rule), written to
+// power[f_offsets[b] + j].
+//
+// Decomposition
+//   gls_ragged_prep_kernel   one workgroup per curve: the weights, centring, YY and time origin t0 = t[0]
+//                            of gls_prep_kernel, and the same 48-byte record per sample, rotated by the
+//                            curve's own delta[b].
+//   gls_ragged_scan_kernel   one workgroup per (curve, tile of 1024 bins), found by a scalar binary search
+//                            in a tile prefix table.  The running sums, the rotation tables and the
+//                            three-term recurrence are those of gls_scan_kernel (K = 8, one wave per
+//                            64-lane column, two columns); the epilogue (gls_epilogue.h) is fused.  Tiles
+//                            are dispatched costliest curve first (cost ~ n_b), so that the long curves
+//                            do not run alone at the end of the launch.  Optionally also writes a pitched
+//                            [B][pitch] copy of the spectra (the caller fills the pad with NaN) for the
+//                            peak table of peaks.hip.
+//   gls_ragged_peak_kernel   NaN-aware max / argmax per curve from the per-tile partials (the rule of
+//                            gls_peak_kernel: first maximum on ties, -1 / NaN for a row without a finite bin).
+//
+// Designed for survey curves (1e2 - 1e4 samples, grids of ~2.5 N bins): no sample parts, no balanced pieces
+// (one huge curve has its own path in gls.hip).
+#include "pdc_internal.h"
+#include "gls_epilogue.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+using namespace pdc;
+
+namespace {
+
+constexpr int kRK = 8;                    // trial frequencies per thread
+constexpr int kRBlock = 128;              // two waves: one 64-lane column of frequencies each
+constexpr int kRCols = kRBlock / 64;
+constexpr int64_t kRTile = (int64_t)kRBlock * kRK;   // 1024 bins per tile
+constexpr int kRChunk = 64;               // samples per rotation-table chunk: two threads per sample = the block
+constexpr int kRPrepBlock = 256;
+
+struct RaggedPrepArgs {
+    const double *t, *y, *dy;      // dy may be NULL (unit errors)
+    const int64_t *offsets;        // [B + 1]
+    const double *delta;           // [B]
+    int fit_mean;
+    double *rec;                   // [n_total][6]
+    double *scal;                  // [B][4] = {YY, sum w, sum err^-2, t0}
+};
+
+struct RaggedArgs {
+    const double *rec, *scal;
+    const int64_t *offsets, *foff;   // [B + 1] samples, bins
+    const double *f0, *delta;        // [B]
+    const int64_t *ctile;            // [B + 1] tile prefix in curve order (where a tile's partial goes)
+    const int64_t *otile;            // [m + 1] tile prefix in dispatch order (curves with >= 1 tile only)
+    const int64_t *order;            // [m] curve at each dispatch position
+    int64_t m, tiles;
+    int psd;
+    double *power;                   // [nf_total] or nullptr
+    double *pitched;                 // [B][pitch] or nullptr
+    int64_t pitch;
+    double *blk_max;                 // [tiles] or nullptr
+    int64_t *blk_arg;
+};
+
+// ---- prologue: spectral.py:99-108, 120, per curve (gls_prep_kernel with the curve's own delta) ---------------
+__global__ __launch_bounds__(kRPrepBlock) void gls_ragged_prep_kernel(RaggedPrepArgs a) {
+    __shared__ double red[kRPrepBlock / 64];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const int64_t off = a.offsets[b];
+    const int64_t n = a.offsets[b + 1] - off;
+    const double *t = a.t + off;
+    const double *y = a.y + off;
+    const double *dy = a.dy ? a.dy + off : nullptr;
+    const double t0 = n > 0 ? t[0] : 0.0;
+    const double delta = a.delta[b];
+    double acc = 0.0;  // w = err**-2 ; w.sum()
+    for (int64_t i = tid; i < n; i += kRPrepBlock) {
+        const double e = dy ? dy[i] : 1.0;
+        acc += 1.0 / (e * e);
+    }
+    const double W = block_sum<kRPrepBlock>(acc, red);
+    double ybar = 0.0;
+    if (a.fit_mean) {  // np.dot(w / w.sum(), values)
+        acc = 0.0;
+        for (int64_t i = tid; i < n; i += kRPrepBlock) {
+            const double e = dy ? dy[i] : 1.0;
+            acc += (1.0 / (e * e)) / W * y[i];
+        }
+        ybar = block_sum<kRPrepBlock>(acc, red);
+    }
+    double yy = 0.0, wsum = 0.0;
+    double *rec = a.rec + off * 6;
+    for (int64_t i = tid; i < n; i += kRPrepBlock) {
+        const double tp = t[i] - t0;
+        const double e = dy ? dy[i] : 1.0;
+        const double w = (1.0 / (e * e)) / W;
+        const double yc = y[i] - ybar;
+        const double wy = w * yc;
+        yy += wy * yc;
+        wsum += w;
+        double sd, cd;
+        sincos_cycles(frac_product(delta, tp), sd, cd);
+        const double rw = sqrt(w);  // the scan carries sqrt(w) sin / sqrt(w) cos
+        double2 *r = reinterpret_cast<double2 *>(rec + i * 6);
+        r[0] = make_double2(rw * yc, rw);
+        r[1] = make_double2(cd, sd);
+        r[2] = make_double2(cd + cd, tp);
+    }
+    yy = block_sum<kRPrepBlock>(yy, red);
+    wsum = block_sum<kRPrepBlock>(wsum, red);
+    if (tid == 0) {
+        double *s = a.scal + b * 4;
+        s[0] = yy;
+        s[1] = wsum;
+        s[2] = W;
+        s[3] = t0;
+    }
+}
+
+// ---- the scan: gls_scan_kernel<K = 8, SPLIT = 1> with a (curve, tile) lookup per workgroup ------------------
+template <bool FIT_MEAN>
+__global__ __launch_bounds__(kRBlock) void gls_ragged_scan_kernel(RaggedArgs a) {
+    // per sample: {sin, cos} of theta_tile + 8 q Theta, q < 8 COLS, scaled by sqrt(w) | {sin, cos}(b Theta), b < 8
+    __shared__ double2 tab[kRChunk + 1][kRCols * 8 + 8 + 1];   // + 1 row: the read-ahead; + 1 column: bank spread
+    __shared__ double red_v[kRBlock / 64];
+    __shared__ long long red_i[kRBlock / 64];
+    const int tid = threadIdx.x;
+    const int64_t L = blockIdx.x;
+    if (L >= a.tiles) return;
+    // dispatch position: the p with otile[p] <= L < otile[p + 1] (every listed curve has >= 1 tile)
+    int64_t lo = 0, hi = a.m - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (a.otile[mid] <= L) lo = mid;
+        else hi = mid - 1;
+    }
+    const int64_t curve = a.order[lo];
+    const int64_t tile = L - a.otile[lo];
+    const int64_t off = a.offsets[curve];
+    const int64_t n = a.offsets[curve + 1] - off;
+    const int64_t fo = a.foff[curve];
+    const int64_t nf = a.foff[curve + 1] - fo;
+    const double f0 = a.f0[curve], delta = a.delta[curve];
+    const int col = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63;
+    const int64_t jt = tile * kRTile;
+    const int64_t jl = jt + (col * 64 + lane) * (int64_t)kRK;
+    // numpy's arange fill rule: start + i*delta, two roundings (no fma)
+    const double f_tile = __dadd_rn(f0, __dmul_rn((double)jt, delta));
+    const double kdelta = (double)kRK * delta;   // spacing of the threads' first frequencies (exact)
+
+    double Sh[kRK], Ch[kRK], S[kRK], C[kRK], SS[kRK], SC[kRK];
+#pragma unroll
+    for (int k = 0; k < kRK; ++k) Sh[k] = Ch[k] = S[k] = C[k] = SS[k] = SC[k] = 0.0;
+
+    auto rot = [](const double2 x, const double2 y) {
+        return make_double2(__builtin_fma(x.x, y.y, x.y * y.x), __builtin_fma(x.y, y.y, -(x.x * y.x)));
+    };
+    const int slot_a = col * 8 + (lane >> 3), slot_b = kRCols * 8 + (lane & 7);
+    for (int64_t base = 0; base < n; base += kRChunk) {
+        __syncthreads();  // everyone is done with the previous chunk's tables
+        // rotation tables, two threads per sample (see gls_scan_kernel): the even thread makes {sin, cos}(b Theta)
+        // and the tile's base phase (scaled by sqrt(w)), the odd one walks the base in steps of 8 Theta
+        {
+            const int il = tid >> 1;
+            const bool live = base + il < n;   // (rows past the end are never accumulated; they need finite input)
+            const double tp = live ? a.rec[(off + base + il) * 6 + 5] : 0.0;
+            const double sqw = live ? a.rec[(off + base + il) * 6 + 1] : 0.0;
+            double2 step1, cur;
+            if ((tid & 1) == 0) {
+                sincos_cycles(frac_product(kdelta, tp), step1.x, step1.y);
+                tab[il][kRCols * 8] = make_double2(0.0, 1.0);
+                tab[il][kRCols * 8 + 1] = step1;
+                cur = step1;
+#pragma unroll
+                for (int q = 2; q < 8; ++q) {
+                    cur = rot(cur, step1);
+                    tab[il][kRCols * 8 + q] = cur;
+                }
+                sincos_cycles(frac_product(f_tile, tp), cur.x, cur.y);
+                cur.x *= sqw;
+                cur.y *= sqw;
+            } else {
+                sincos_cycles(frac_product(8.0 * kdelta, tp), step1.x, step1.y);
+            }
+            double2 b0;
+            b0.x = __shfl_xor(cur.x, 1, 64);
+            b0.y = __shfl_xor(cur.y, 1, 64);
+            if (tid & 1) {
+                tab[il][0] = b0;
+#pragma unroll
+                for (int q = 1; q < kRCols * 8; ++q) {
+                    b0 = rot(b0, step1);
+                    tab[il][q] = b0;
+                }
+            }
+        }
+        __syncthreads();
+        const int cnt = (int)((n - base) < kRChunk ? (n - base) : kRChunk);
+        // software pipeline of gls_scan_kernel: record fields through the scalar cache (wave-uniform), two
+        // register sets that swap roles; the read-ahead touches one record past the curve (the workspace keeps
+        // two spare records after the last curve) and the padding table row
+        using d4 = double __attribute__((ext_vector_type(4)));
+        using cd4 = __attribute__((address_space(4))) const d4;
+        using cdbl = __attribute__((address_space(4))) const double;
+        const cd4 *srec = reinterpret_cast<const cd4 *>(reinterpret_cast<uintptr_t>(a.rec + (off + base) * 6));
+        struct Ahead {
+            d4 r;  // {sqrt(w) y, sqrt(w), cos, sin (2 pi delta t')}
+            double cd2;
+            double2 qa, qt;
+        };
+        auto fetch = [&](const int i) {
+            Ahead h;
+            h.qa = tab[i][slot_a];
+            h.qt = tab[i][slot_b];
+            const cd4 *rp = reinterpret_cast<const cd4 *>(reinterpret_cast<const cdbl *>(srec) + i * 6);
+            h.r = rp[0];
+            h.cd2 = reinterpret_cast<const cdbl *>(rp)[4];
+            return h;
+        };
+        auto accumulate = [&](const Ahead &h) {
+            const double2 seed = rot(h.qa, h.qt);
+            const double wy = h.r[0], w = h.r[1], cd = h.r[2], sd = h.r[3], cd2 = h.cd2;
+            double s = seed.x, c = seed.y;
+            double sp = 0.0, cp = 0.0;
+#pragma unroll
+            for (int k = 0; k < kRK; ++k) {
+                Sh[k] = __builtin_fma(wy, s, Sh[k]);
+                Ch[k] = __builtin_fma(wy, c, Ch[k]);
+                if (FIT_MEAN) {
+                    S[k] = __builtin_fma(w, s, S[k]);
+                    C[k] = __builtin_fma(w, c, C[k]);
+                }
+                SS[k] = __builtin_fma(s, s, SS[k]);
+                SC[k] = __builtin_fma(s, c, SC[k]);
+                if (k + 1 < kRK) {
+                    double sn, cn;
+                    if (k == 0) {   // first grid step: plane rotation by 2 pi delta t'
+                        cn = __builtin_fma(c, cd, -(s * sd));
+                        sn = __builtin_fma(s, cd, c * sd);
+                    } else {        // x[k+1] = 2 cos(theta) x[k] - x[k-1]
+                        cn = __builtin_fma(cd2, c, -cp);
+                        sn = __builtin_fma(cd2, s, -sp);
+                    }
+                    cp = c;
+                    sp = s;
+                    c = cn;
+                    s = sn;
+                }
+            }
+        };
+        Ahead A = fetch(0);
+        int i = 0;
+        for (; i + 1 < cnt; i += 2) {
+            __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): set A has arrived
+            Ahead B = fetch(i + 1);
+            __builtin_amdgcn_sched_barrier(0);
+            accumulate(A);
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_waitcnt(0xc07f);
+            A = fetch(i + 2);
+            __builtin_amdgcn_sched_barrier(0);
+            accumulate(B);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (i < cnt) accumulate(A);
+    }
+
+    // fused epilogue (spectral.py:113-132); the 2-omega sums from sin 2a = 2 sin a cos a, cos 2a = 1 - 2 sin^2 a
+    const double *sc = a.scal + curve * 4;
+    const double YY = sc[0], Wsum = sc[1], Werr = sc[2];
+    double best = 0.0;
+    long long best_j = -1;
+#pragma unroll
+    for (int k = 0; k < kRK; ++k) {
+        const int64_t j = jl + k;
+        if (j < nf) {
+            const double p = gls_power_from_sums<FIT_MEAN>(Sh[k], Ch[k], S[k], C[k], 2.0 * SC[k], Wsum - 2.0 * SS[k],
+                                                           YY, Werr, a.psd);
+            if (a.power) a.power[fo + j] = p;
+            if (a.pitched) a.pitched[curve * a.pitch + j] = p;
+            if (p == p && (best_j < 0 || p > best)) {
+                best = p;
+                best_j = j;
+            }
+        }
+    }
+    if (a.blk_max) {
+        // NaN-aware max with lowest-index ties (np.nanargmax): lanes hold ascending index ranges
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double ov = __shfl_down(best, o, 64);
+            const long long oj = __shfl_down(best_j, o, 64);
+            if (oj >= 0 && (best_j < 0 || ov > best || (ov == best && oj < best_j))) {
+                best = ov;
+                best_j = oj;
+            }
+        }
+        if (lane == 0) {
+            red_v[col] = best;
+            red_i[col] = best_j;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            for (int wv = 1; wv < kRBlock / 64; ++wv) {
+                if (red_i[wv] >= 0 && (best_j < 0 || red_v[wv] > best)) {
+                    best = red_v[wv];
+                    best_j = red_i[wv];
+                }
+            }
+            const int64_t at = a.ctile[curve] + tile;
+            a.blk_max[at] = best;
+            a.blk_arg[at] = best_j;
+        }
+    }
+}
+
+// per curve: the tile partials [ctile[b], ctile[b + 1]) folded in ascending order (gls_peak_kernel's rule)
+__global__ __launch_bounds__(64) void gls_ragged_peak_kernel(const double *blk_max, const int64_t *blk_arg,
+                                                             const int64_t *ctile, double *amax, int64_t *argmax) {
+    const int64_t curve = blockIdx.x;
+    const int64_t t0 = ctile[curve], t1 = ctile[curve + 1];
+    double best = 0.0;
+    long long best_j = -1;
+    for (int64_t i = t0 + threadIdx.x; i < t1; i += 64) {
+        const double v = blk_max[i];
+        const long long j = blk_arg[i];
+        if (j >= 0 && (best_j < 0 || v > best)) {
+            best = v;
+            best_j = j;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ov = __shfl_down(best, o, 64);
+        const long long oj = __shfl_down(best_j, o, 64);
+        if (oj >= 0 && (best_j < 0 || ov > best || (ov == best && oj < best_j))) {
+            best = ov;
+            best_j = oj;
+        }
+    }
+    if (threadIdx.x == 0) {
+        if (amax) amax[curve] = best_j >= 0 ? best : __builtin_nan("");
+        if (argmax) argmax[curve] = best_j;
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------
+int64_t up256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+int64_t tiles_of(int64_t nf) { return (nf + kRTile - 1) / kRTile; }
+
+// Workspace of one launch over B curves: records (+ two spare ones for the scan's read-ahead), per-curve scalars,
+// the metadata tables, the tile partials; with k > 0 also the NaN-padded [B][nf_max] copy and the [B][k] peak table.
+struct RaggedLayout {
+    int64_t rec, scal, meta, blk_max, blk_arg, pitched, table, total;
+};
+constexpr int kMetaArrays = 7;   // offsets | foff | ctile | otile | order (int64) | f0 | delta (double), B + 1 each
+
+RaggedLayout ragged_layout(int64_t n_total, int64_t n_curves, int64_t nf_total, int64_t nf_max, int k) {
+    const int64_t tiles_max = nf_total / kRTile + n_curves;   // >= sum of ceil(nf_b / 1024)
+    RaggedLayout w;
+    w.rec = 0;
+    w.scal = up256((n_total + 2) * 48);
+    w.meta = w.scal + up256(n_curves * 32);
+    w.blk_max = w.meta + up256(kMetaArrays * (n_curves + 1) * 8);
+    w.blk_arg = w.blk_max + up256(tiles_max * 8);
+    w.pitched = w.blk_arg + up256(tiles_max * 8);
+    w.table = w.pitched + (k > 0 ? up256(n_curves * nf_max * 8) : 0);
+    // count | idx | half_lo | half_hi | height | prominence
+    w.total = w.table + (k > 0 ? up256((n_curves + 5 * n_curves * (int64_t)k) * 8) : 0);
+    return w;
+}
+
+// Checks the host-side description of a batch; the same text for every entry point.
+int validate(const char *what, const int64_t *offsets, int64_t n_curves, const double *f0, const double *delta,
+             const int64_t *f_offsets) {
+    PDC_REQUIRE(offsets && f0 && delta && f_offsets, "%s: NULL argument", what);
+    PDC_REQUIRE(n_curves >= 1 && n_curves < ((int64_t)1 << 31), "%s: n_curves must be 1 .. 2^31 - 1 (got %lld)", what,
+                (long long)n_curves);
+    PDC_REQUIRE(offsets[0] == 0 && f_offsets[0] == 0, "%s: offsets[0] and f_offsets[0] must be 0", what);
+    int64_t tiles = 0;
+    for (int64_t b = 0; b < n_curves; ++b) {
+        PDC_REQUIRE(offsets[b + 1] >= offsets[b], "%s: offsets must be non-decreasing (curve %lld)", what, (long long)b);
+        PDC_REQUIRE(f_offsets[b + 1] >= f_offsets[b], "%s: f_offsets must be non-decreasing (curve %lld)", what,
+                    (long long)b);
+        PDC_REQUIRE(std::isfinite(f0[b]) && std::isfinite(delta[b]) && delta[b] > 0.0,
+                    "%s: curve %lld: f0 and delta must be finite and delta > 0 (f0 = %g, delta = %g)", what, (long long)b,
+                    f0[b], delta[b]);
+        tiles += tiles_of(f_offsets[b + 1] - f_offsets[b]);
+    }
+    PDC_REQUIRE(tiles < ((int64_t)1 << 31), "%s: %lld tiles of %lld bins: the grid is too large for one launch", what,
+                (long long)tiles, (long long)kRTile);
+    return PDC_OK;
+}
+
+// Every workgroup-visible launch of one group of curves.  Metadata come from the host (offsets, f_offsets rebased
+// to the group), the sample arrays and the workspace are on the device.
+int ragged_dev(int device, hipStream_t st, const double *d_t, const double *d_y, const double *d_dy,
+               const int64_t *offsets, int64_t n_curves, const double *f0, const double *delta, const int64_t *foff,
+               int fit_mean, int psd, double *d_power, double *d_pitched, int64_t pitch, double *d_amax,
+               int64_t *d_argmax, void *work, int64_t work_bytes, std::vector<int64_t> &meta, bool wait_meta) {
+    const int64_t n_total = offsets[n_curves], nf_total = foff[n_curves];
+    const RaggedLayout w = ragged_layout(n_total, n_curves, nf_total, 0, 0);   // (the pitched copy is the caller's)
+    PDC_REQUIRE(work && work_bytes >= w.total, "gls_ragged: workspace too small (%lld < %lld bytes)",
+                (long long)work_bytes, (long long)w.total);
+    PDC_REQUIRE(n_total == 0 || (d_t && d_y), "gls_ragged: t and y must not be NULL");
+    PDC_TRY(use_device(device));
+    char *base = static_cast<char *>(work);
+    // metadata: one upload; dispatch order = curves with >= 1 tile, most samples first (ties: curve order)
+    const int64_t B1 = n_curves + 1;
+    meta.assign((size_t)(kMetaArrays * B1), 0);
+    int64_t *m_off = meta.data(), *m_foff = m_off + B1, *m_ctile = m_foff + B1, *m_otile = m_ctile + B1,
+            *m_order = m_otile + B1;
+    double *m_f0 = reinterpret_cast<double *>(m_order + B1), *m_delta = m_f0 + B1;
+    std::vector<int64_t> ord;
+    ord.reserve((size_t)n_curves);
+    for (int64_t b = 0; b < n_curves; ++b) {
+        m_off[b] = offsets[b];
+        m_foff[b] = foff[b];
+        m_f0[b] = f0[b];
+        m_delta[b] = delta[b];
+        m_ctile[b + 1] = m_ctile[b] + tiles_of(foff[b + 1] - foff[b]);
+        if (foff[b + 1] > foff[b]) ord.push_back(b);
+    }
+    m_off[n_curves] = n_total;
+    m_foff[n_curves] = nf_total;
+    static const bool costly_first = [] { const char *e = getenv("PDC_RAGGED_ORDER"); return !(e && e[0] == '0'); }();
+    if (costly_first)
+        std::stable_sort(ord.begin(), ord.end(), [&](int64_t x, int64_t y) {
+            return offsets[x + 1] - offsets[x] > offsets[y + 1] - offsets[y];
+        });
+    const int64_t m = (int64_t)ord.size();
+    for (int64_t p = 0; p < m; ++p) {
+        m_order[p] = ord[(size_t)p];
+        m_otile[p + 1] = m_otile[p] + tiles_of(foff[ord[(size_t)p] + 1] - foff[ord[(size_t)p]]);
+    }
+    const int64_t tiles = m_ctile[n_curves];
+    int64_t *d_meta = reinterpret_cast<int64_t *>(base + w.meta);
+    PDC_HIP(hipMemcpyAsync(d_meta, meta.data(), (size_t)(kMetaArrays * B1 * 8), hipMemcpyHostToDevice, st));
+    if (wait_meta) PDC_HIP(hipStreamSynchronize(st));   // (`meta` goes when the caller returns)
+    const int64_t *d_off = d_meta, *d_foff = d_off + B1, *d_ctile = d_foff + B1, *d_otile = d_ctile + B1,
+                  *d_order = d_otile + B1;
+    const double *d_f0 = reinterpret_cast<const double *>(d_order + B1), *d_delta = d_f0 + B1;
+
+    RaggedPrepArgs p;
+    p.t = d_t;
+    p.y = d_y;
+    p.dy = d_dy;
+    p.offsets = d_off;
+    p.delta = d_delta;
+    p.fit_mean = fit_mean;
+    p.rec = reinterpret_cast<double *>(base + w.rec);
+    p.scal = reinterpret_cast<double *>(base + w.scal);
+    hipLaunchKernelGGL(gls_ragged_prep_kernel, dim3((unsigned)n_curves), dim3(kRPrepBlock), 0, st, p);
+    PDC_HIP(hipGetLastError());
+    const bool peaks = d_amax || d_argmax;
+    if (tiles > 0) {
+        RaggedArgs a;
+        a.rec = p.rec;
+        a.scal = p.scal;
+        a.offsets = d_off;
+        a.foff = d_foff;
+        a.f0 = d_f0;
+        a.delta = d_delta;
+        a.ctile = d_ctile;
+        a.otile = d_otile;
+        a.order = d_order;
+        a.m = m;
+        a.tiles = tiles;
+        a.psd = psd;
+        a.power = d_power;
+        a.pitched = d_pitched;
+        a.pitch = pitch;
+        a.blk_max = peaks ? reinterpret_cast<double *>(base + w.blk_max) : nullptr;
+        a.blk_arg = peaks ? reinterpret_cast<int64_t *>(base + w.blk_arg) : nullptr;
+        if (fit_mean) hipLaunchKernelGGL(gls_ragged_scan_kernel<true>, dim3((unsigned)tiles), dim3(kRBlock), 0, st, a);
+        else hipLaunchKernelGGL(gls_ragged_scan_kernel<false>, dim3((unsigned)tiles), dim3(kRBlock), 0, st, a);
+        PDC_HIP(hipGetLastError());
+    }
+    if (peaks) {
+        hipLaunchKernelGGL(gls_ragged_peak_kernel, dim3((unsigned)n_curves), dim3(64), 0, st,
+                           reinterpret_cast<const double *>(base + w.blk_max),
+                           reinterpret_cast<const int64_t *>(base + w.blk_arg), d_ctile, d_amax, d_argmax);
+        PDC_HIP(hipGetLastError());
+    }
+    return PDC_OK;
+}
+
+// ---- host entries: curves dealt to device slots, each slot's share processed in groups that fit its budget ----
+struct RBuf {
+    void *p = nullptr;
+    int64_t cap = 0;
+};
+
+struct RSlot {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    RBuf buf;               // inputs | power | amax | argmax | workspace of one group
+    std::vector<int64_t> meta;
+};
+
+std::mutex g_ragged_mutex;
+std::vector<int> g_ragged_devices;
+std::vector<RSlot> g_ragged_slots;
+
+int ensure_buf(RBuf &b, int64_t bytes) {   // (on the current device) grow-only
+    if (bytes < 256) bytes = 256;
+    if (b.cap >= bytes) return PDC_OK;
+    if (b.p) PDC_HIP(hipFree(b.p));
+    b.p = nullptr;
+    b.cap = 0;
+    PDC_TRY(device_alloc(&b.p, bytes + bytes / 8));
+    b.cap = bytes + bytes / 8;
+    return PDC_OK;
+}
+
+int free_slots() {
+    for (RSlot &s : g_ragged_slots) {
+        PDC_HIP(hipSetDevice(s.device));
+        if (s.stream) PDC_HIP(hipStreamDestroy(s.stream));
+        if (s.buf.p) PDC_HIP(hipFree(s.buf.p));
+    }
+    g_ragged_slots.clear();
+    g_ragged_devices.clear();
+    return PDC_OK;
+}
+
+// What one host call computes and where its results go (caller's host arrays, any may be NULL).
+struct RaggedJob {
+    const double *t, *y, *dy;
+    const int64_t *offsets, *foff;
+    const double *f0, *delta;
+    int fit_mean, psd, k, by_prominence;
+    double *power, *amax;
+    int64_t *argmax;
+    int64_t *count, *idx, *lo, *hi;
+    double *height, *prom;
+};
+
+// Bytes of the slot buffer for the group [c0, c1) whose longest grid has nf_max bins.
+struct GroupBytes {
+    int64_t in_t, in_y, in_dy, pow, amax, arg, work, total;
+};
+GroupBytes group_bytes(const RaggedJob &j, int64_t c0, int64_t c1, int64_t nf_max) {
+    const int64_t n = j.offsets[c1] - j.offsets[c0], nf = j.foff[c1] - j.foff[c0], B = c1 - c0;
+    GroupBytes g;
+    g.in_t = 0;
+    g.in_y = up256(n * 8);
+    g.in_dy = g.in_y + up256(n * 8);
+    g.pow = g.in_dy + (j.dy ? up256(n * 8) : 0);
+    g.amax = g.pow + (j.power ? up256(nf * 8) : 0);
+    g.arg = g.amax + (j.amax ? up256(B * 8) : 0);
+    g.work = g.arg + (j.argmax ? up256(B * 8) : 0);
+    g.total = g.work + ragged_layout(n, B, nf, nf_max, j.k).total;
+    return g;
+}
+int64_t nf_of(const RaggedJob &j, int64_t b) { return j.foff[b + 1] - j.foff[b]; }
+
+// Contiguous groups of [c0, c1) of at most `cap` bytes each (a curve that alone exceeds it is a group of its own);
+// *largest = the bytes of the largest group.
+std::vector<int64_t> make_groups(const RaggedJob &j, int64_t c0, int64_t c1, int64_t cap, int64_t *largest) {
+    std::vector<int64_t> cut{c0};
+    *largest = 0;
+    int64_t g0 = c0, nf_max = 0;
+    for (int64_t b = c0; b < c1; ++b) {
+        const int64_t grown = std::max(nf_max, nf_of(j, b));
+        if (b > g0 && group_bytes(j, g0, b + 1, grown).total > cap) {
+            *largest = std::max(*largest, group_bytes(j, g0, b, nf_max).total);
+            cut.push_back(b);
+            g0 = b;
+            nf_max = nf_of(j, b);
+        } else {
+            nf_max = grown;
+        }
+    }
+    if (c1 > g0) *largest = std::max(*largest, group_bytes(j, g0, c1, nf_max).total);
+    cut.push_back(c1);
+    return cut;
+}
+
+// One group on one slot, start to finish (the slot's stream is synchronised before return).
+int run_group(RSlot &s, const RaggedJob &j, int64_t c0, int64_t c1) {
+    const int64_t B = c1 - c0, s0 = j.offsets[c0], n = j.offsets[c1] - s0, fb = j.foff[c0], nf = j.foff[c1] - fb;
+    int64_t nf_max = 0;
+    for (int64_t b = c0; b < c1; ++b) nf_max = std::max(nf_max, nf_of(j, b));
+    if (j.k == 0) nf_max = 0;
+    const GroupBytes g = group_bytes(j, c0, c1, nf_max);
+    PDC_TRY(ensure_buf(s.buf, g.total));
+    char *p = static_cast<char *>(s.buf.p);
+    hipStream_t st = s.stream;
+    if (n > 0) {
+        PDC_HIP(hipMemcpyAsync(p + g.in_t, j.t + s0, n * 8, hipMemcpyHostToDevice, st));
+        PDC_HIP(hipMemcpyAsync(p + g.in_y, j.y + s0, n * 8, hipMemcpyHostToDevice, st));
+        if (j.dy) PDC_HIP(hipMemcpyAsync(p + g.in_dy, j.dy + s0, n * 8, hipMemcpyHostToDevice, st));
+    }
+    std::vector<int64_t> off((size_t)B + 1), foff((size_t)B + 1);
+    for (int64_t b = 0; b <= B; ++b) {
+        off[(size_t)b] = j.offsets[c0 + b] - s0;
+        foff[(size_t)b] = j.foff[c0 + b] - fb;
+    }
+    const int k = j.k;
+    const RaggedLayout w = ragged_layout(n, B, nf, nf_max, k);
+    char *work = p + g.work;
+    double *d_pitched = nullptr;
+    if (k > 0) {
+        d_pitched = reinterpret_cast<double *>(work + w.pitched);
+        // all-ones bytes: a NaN in every bin, the pad [nf_b, nf_max) stays so (see the header for why this keeps
+        // scipy's answers)
+        PDC_HIP(hipMemsetAsync(d_pitched, 0xff, (size_t)(B * nf_max * 8), st));
+    }
+    PDC_TRY(ragged_dev(s.device, st, (const double *)(p + g.in_t), (const double *)(p + g.in_y),
+                       j.dy ? (const double *)(p + g.in_dy) : nullptr, off.data(), B, j.f0 + c0, j.delta + c0, foff.data(),
+                       j.fit_mean, j.psd, j.power ? (double *)(p + g.pow) : nullptr, d_pitched, nf_max,
+                       j.amax ? (double *)(p + g.amax) : nullptr, j.argmax ? (int64_t *)(p + g.arg) : nullptr, work,
+                       w.total, s.meta, false));
+    const int64_t nk = B * (int64_t)k;
+    int64_t *d_count = reinterpret_cast<int64_t *>(work + w.table), *d_idx = d_count + B, *d_lo = d_idx + nk,
+            *d_hi = d_lo + nk;
+    double *d_h = reinterpret_cast<double *>(d_hi + nk), *d_p = d_h + nk;
+    if (k > 0)
+        PDC_TRY(pdc_peaks_topk_dev(s.device, st, d_pitched, B, nf_max, k, j.by_prominence, d_count, d_idx, d_h, d_p,
+                                   d_lo, d_hi));
+    if (j.power && nf > 0) PDC_HIP(hipMemcpyAsync(j.power + fb, p + g.pow, nf * 8, hipMemcpyDeviceToHost, st));
+    if (j.amax) PDC_HIP(hipMemcpyAsync(j.amax + c0, p + g.amax, B * 8, hipMemcpyDeviceToHost, st));
+    if (j.argmax) PDC_HIP(hipMemcpyAsync(j.argmax + c0, p + g.arg, B * 8, hipMemcpyDeviceToHost, st));
+    if (k > 0) {
+        if (j.count) PDC_HIP(hipMemcpyAsync(j.count + c0, d_count, B * 8, hipMemcpyDeviceToHost, st));
+        if (j.idx) PDC_HIP(hipMemcpyAsync(j.idx + c0 * k, d_idx, nk * 8, hipMemcpyDeviceToHost, st));
+        if (j.height) PDC_HIP(hipMemcpyAsync(j.height + c0 * k, d_h, nk * 8, hipMemcpyDeviceToHost, st));
+        if (j.prom) PDC_HIP(hipMemcpyAsync(j.prom + c0 * k, d_p, nk * 8, hipMemcpyDeviceToHost, st));
+        if (j.lo) PDC_HIP(hipMemcpyAsync(j.lo + c0 * k, d_lo, nk * 8, hipMemcpyDeviceToHost, st));
+        if (j.hi) PDC_HIP(hipMemcpyAsync(j.hi + c0 * k, d_hi, nk * 8, hipMemcpyDeviceToHost, st));
+    }
+    PDC_HIP(hipStreamSynchronize(st));
+    if (k > 0 && j.lo) {
+        // the pad's one artefact: a sign flip of the pair (nf_b - 1, nf_b) is no crossing of the row itself
+        for (int64_t b = 0; b < B; ++b) {
+            const int64_t nfb = j.foff[c0 + b + 1] - j.foff[c0 + b];
+            for (int r = 0; r < k; ++r)
+                if (j.lo[(c0 + b) * k + r] >= nfb - 1) j.lo[(c0 + b) * k + r] = -1;
+        }
+    }
+    return PDC_OK;
+}
+
+int ragged_host(const char *what, const RaggedJob &j, int64_t n_curves, const int *devices, int n_devices) {
+    PDC_REQUIRE(devices && n_devices >= 1 && n_devices <= 64, "%s: 1 .. 64 device slots (got %d)", what, n_devices);
+    PDC_REQUIRE(j.offsets[n_curves] == 0 || (j.t && j.y), "%s: t and y must not be NULL", what);
+    for (int i = 0; i < n_devices; ++i) PDC_TRY(use_device(devices[i]));
+    std::lock_guard<std::mutex> lk(g_ragged_mutex);
+    if (g_ragged_devices != std::vector<int>(devices, devices + n_devices)) {
+        PDC_TRY(free_slots());
+        g_ragged_slots.resize((size_t)n_devices);
+        for (int i = 0; i < n_devices; ++i) g_ragged_slots[(size_t)i].device = devices[i];
+        g_ragged_devices.assign(devices, devices + n_devices);
+    }
+    // contiguous shares balanced by sum n_b nf_b (+ n_b + nf_b: the per-sample and per-bin work)
+    std::vector<double> pre((size_t)n_curves + 1, 0.0);
+    for (int64_t b = 0; b < n_curves; ++b) {
+        const double nb = (double)(j.offsets[b + 1] - j.offsets[b]), fb = (double)(j.foff[b + 1] - j.foff[b]);
+        pre[(size_t)b + 1] = pre[(size_t)b] + nb * fb + nb + fb;
+    }
+    std::vector<int64_t> share((size_t)n_devices + 1, n_curves);
+    share[0] = 0;
+    for (int i = 1; i < n_devices; ++i)
+        share[(size_t)i] = std::lower_bound(pre.begin(), pre.end(), pre.back() * i / n_devices) - pre.begin();
+    // each slot's groups: the largest group shrinks by powers of two (WorkScale) until it fits the slot's budget,
+    // PDC_WORK_BUDGET_GB and its share of what the device has free (plus what the slot already holds)
+    std::vector<std::vector<int64_t>> cuts((size_t)n_devices);
+    for (int i = 0; i < n_devices; ++i) {
+        RSlot &s = g_ragged_slots[(size_t)i];
+        PDC_TRY(use_device(s.device));
+        if (!s.stream) PDC_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+        const int64_t c0 = share[(size_t)i], c1 = share[(size_t)i + 1];
+        if (c1 <= c0) continue;
+        int same = 0;
+        int64_t held = 0;
+        for (const RSlot &o : g_ragged_slots)
+            if (o.device == s.device) {
+                ++same;
+                held += o.buf.cap;
+            }
+        int64_t budget = work_budget();
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            const int64_t avail = (int64_t)((double)((int64_t)free_b + held) * 0.9 / same);
+            if (avail > 0 && (budget == 0 || avail < budget)) budget = avail;
+        } else {
+            (void)hipGetLastError();
+        }
+        int64_t nf_max = 0;
+        for (int64_t b = c0; b < c1 && j.k > 0; ++b) nf_max = std::max(nf_max, nf_of(j, b));
+        const int64_t whole = group_bytes(j, c0, c1, nf_max).total;
+        WorkScale ws(budget, [&] {
+            int64_t largest;
+            (void)make_groups(j, c0, c1, (int64_t)((double)whole * work_scale()), &largest);
+            return largest;
+        });
+        PDC_REQUIRE_FITS(ws, what);
+        int64_t largest;
+        cuts[(size_t)i] = make_groups(j, c0, c1, (int64_t)((double)whole * work_scale()), &largest);
+    }
+    std::vector<int> rc((size_t)n_devices, PDC_OK);
+    std::vector<std::string> why((size_t)n_devices);
+    auto run_slot = [&](int i) {
+        RSlot &s = g_ragged_slots[(size_t)i];
+        const std::vector<int64_t> &cut = cuts[(size_t)i];
+        int r = use_device(s.device);
+        for (size_t q = 0; r == PDC_OK && q + 1 < cut.size(); ++q) r = run_group(s, j, cut[q], cut[q + 1]);
+        if (r != PDC_OK) {
+            rc[(size_t)i] = r;
+            why[(size_t)i] = pdc_last_error();
+            (void)hipStreamSynchronize(s.stream);
+        }
+    };
+    if (n_devices == 1) {
+        run_slot(0);
+    } else {
+        std::vector<std::thread> th;
+        for (int i = 0; i < n_devices; ++i) th.emplace_back(run_slot, i);
+        for (std::thread &x : th) x.join();
+    }
+    for (int i = 0; i < n_devices; ++i)
+        if (rc[(size_t)i] != PDC_OK) {
+            set_error("%s", why[(size_t)i].c_str());
+            return rc[(size_t)i];
+        }
+    return PDC_OK;
+}
+
+}  // namespace
+
+// Frees the per-slot buffers and streams of the ragged host entries (pdc_release()).
+int pdc::release_ragged() {
+    std::lock_guard<std::mutex> lk(g_ragged_mutex);
+    return free_slots();
+}
+
+extern "C" {
+
+int64_t pdc_gls_ragged_work_bytes(int64_t n_total, int64_t n_curves, int64_t nf_total, int64_t nf_max, int k) {
+    if (n_total < 0 || n_curves < 1 || nf_total < 0 || nf_max < 0 || k < 0) return -1;
+    return ragged_layout(n_total, n_curves, nf_total, nf_max, k).total;
+}
+
+int pdc_gls_scan_ragged_dev(int device, void *stream, const double *d_t, const double *d_y, const double *d_dy,
+                            const int64_t *offsets, int64_t n_curves, const double *f0, const double *delta,
+                            const int64_t *f_offsets, int fit_mean, int psd, double *d_power, double *d_pitched,
+                            int64_t pitch, double *d_amax, int64_t *d_argmax, void *work, int64_t work_bytes) {
+    PDC_TRY(validate("gls_ragged_dev", offsets, n_curves, f0, delta, f_offsets));
+    PDC_REQUIRE(d_power || d_pitched || d_amax || d_argmax, "gls_ragged_dev: no output requested");
+    if (d_pitched)
+        for (int64_t b = 0; b < n_curves; ++b)
+            PDC_REQUIRE(f_offsets[b + 1] - f_offsets[b] <= pitch, "gls_ragged_dev: curve %lld has more bins than the pitch",
+                        (long long)b);
+    std::vector<int64_t> meta;
+    return ragged_dev(device, (hipStream_t)stream, d_t, d_y, d_dy, offsets, n_curves, f0, delta, f_offsets, fit_mean, psd,
+                      d_power, d_pitched, pitch, d_amax, d_argmax, work, work_bytes, meta, true);
+}
+
+int pdc_gls_scan_ragged(const double *t, const double *y, const double *dy, const int64_t *offsets, int64_t n_curves,
+                        const double *f0, const double *delta, const int64_t *f_offsets, int fit_mean, int psd,
+                        double *power_out, double *amax_out, int64_t *argmax_out, const int *devices, int n_devices) {
+    PDC_TRY(validate("gls_ragged", offsets, n_curves, f0, delta, f_offsets));
+    PDC_REQUIRE(power_out || amax_out || argmax_out, "gls_ragged: no output requested");
+    RaggedJob j = {};
+    j.t = t;
+    j.y = y;
+    j.dy = dy;
+    j.offsets = offsets;
+    j.foff = f_offsets;
+    j.f0 = f0;
+    j.delta = delta;
+    j.fit_mean = fit_mean ? 1 : 0;
+    j.psd = psd ? 1 : 0;
+    j.power = power_out;
+    j.amax = amax_out;
+    j.argmax = argmax_out;
+    return ragged_host("gls_ragged", j, n_curves, devices, n_devices);
+}
+
+int pdc_gls_ragged_peaks(const double *t, const double *y, const double *dy, const int64_t *offsets, int64_t n_curves,
+                         const double *f0, const double *delta, const int64_t *f_offsets, int fit_mean, int psd, int k,
+                         int by_prominence, int64_t *count_out, int64_t *idx_out, double *height_out,
+                         double *prominence_out, int64_t *half_lo_out, int64_t *half_hi_out, double *power_out,
+                         const int *devices, int n_devices) {
+    PDC_TRY(validate("gls_ragged_peaks", offsets, n_curves, f0, delta, f_offsets));
+    PDC_REQUIRE(k >= 1 && k <= 1024, "gls_ragged_peaks: k must be 1..1024 (got %d)", k);
+    PDC_REQUIRE(count_out || idx_out || height_out || prominence_out || half_lo_out || half_hi_out || power_out,
+                "gls_ragged_peaks: no output requested");
+    RaggedJob j = {};
+    j.t = t;
+    j.y = y;
+    j.dy = dy;
+    j.offsets = offsets;
+    j.foff = f_offsets;
+    j.f0 = f0;
+    j.delta = delta;
+    j.fit_mean = fit_mean ? 1 : 0;
+    j.psd = psd ? 1 : 0;
+    j.k = k;
+    j.by_prominence = by_prominence ? 1 : 0;
+    j.power = power_out;
+    j.count = count_out;
+    j.idx = idx_out;
+    j.height = height_out;
+    j.prom = prominence_out;
+    j.lo = half_lo_out;
+    j.hi = half_hi_out;
+    return ragged_host("gls_ragged_peaks", j, n_curves, devices, n_devices);
+}
+
+}  // extern "C"

@@ -21,6 +21,8 @@ int cached(int device, Slot slot, int64_t bytes, void **dptr);
 
 // Frees the multi-GPU plans the one-shot `_multi` entry points cache (multi.hip).
 void release_multi();
+// Frees the per-slot buffers and streams the ragged-grid GLS host entries keep between calls (gls_ragged.hip).
+int release_ragged();
 
 // Every device / pinned-host allocation of the library goes through these two, so that
 // pdc_alloc_counts() can show a caller (and the tests) that a cached path allocates nothing on

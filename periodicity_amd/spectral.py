@@ -19,7 +19,7 @@ import numpy as np
 from . import _cabi
 from .core import FSeries, TSeries
 
-__all__ = ["GLS", "LombScargle", "BGLST"]
+__all__ = ["GLS", "LombScargle", "BGLST", "GLSBatch", "PeakTable"]
 
 
 def _as_tseries(signal):
@@ -115,6 +115,82 @@ class GLS(object):
     def copy(self):
         return _copy.deepcopy(self)
 
+    def _ragged_grids(self, signals):
+        """Every curve's grid, exactly ``self._grid(signal)``, and the ``(f0, delta, f_offsets)`` the ragged
+        kernel rebuilds it from (``start + j*step`` per curve).  A grid of fewer than two bins has no step of its
+        own; any positive step rebuilds it, and 1 is used."""
+        grids = [self._grid(s) for s in signals]
+        f_offsets = np.zeros(len(grids) + 1, dtype=np.int64)
+        f_offsets[1:] = np.cumsum([g.size for g in grids])
+        f0 = np.array([g[0] if g.size else 0.0 for g in grids], dtype=np.float64)
+        delta = np.array([g[1] - g[0] if g.size > 1 else 1.0 for g in grids], dtype=np.float64)
+        return grids, f0, delta, f_offsets
+
+    def batch(self, signals, errs=None, fit_mean=True, *, peaks=0, by_prominence=False, want_power=True):
+        """Periodograms of many light curves, each on the grid its own data give (``self._grid``, the rule of
+        ``spectral.py:88-98`` applied per curve), in one set of launches (``pdc_gls_scan_ragged`` /
+        ``pdc_gls_ragged_peaks``): what a loop of ``GLS(...)(s, e, fit_mean)`` followed by
+        ``period_at_highest_peak`` etc. gives, without a launch per curve.
+
+        Parameters
+        ----------
+        signals: sequence of TSeries (or anything ``GLS.__call__`` accepts)
+        errs: None, or a sequence (one entry per signal) of arrays or Nones
+        fit_mean: bool
+        peaks: int, keyword-only
+            ``k > 0``: also the ``k`` (<= 1024) highest - or, ``by_prominence``, most prominent - ``find_peaks``
+            maxima of every spectrum, found on the device (``GLSBatch.peaks``).
+        want_power: bool, keyword-only
+            ``False``: the spectra stay on the device (``periodograms`` is None); needs ``peaks > 0``.
+
+        With ``devices=(...)`` the curves are dealt to those device slots in contiguous groups balanced by
+        ``sum n_b nf_b``.  The ``GLS`` object's own attributes (``frequency``, ``periodogram`` ...) are left as
+        they were.
+        """
+        if self.method == "fft":
+            raise NotImplementedError("GLS.batch runs the direct sums only: method='fft' needs one FFT size per curve")
+        signals = [_as_tseries(s) for s in signals]
+        if not signals:
+            raise ValueError("GLS.batch needs at least one signal")
+        if errs is not None:
+            errs = list(errs)
+            if len(errs) != len(signals):
+                raise ValueError(f"errs has {len(errs)} entries for {len(signals)} signals")
+        peaks = int(peaks)
+        if peaks < 0 or peaks > 1024:
+            raise ValueError("peaks must be 0 .. 1024")
+        if not want_power and peaks == 0:
+            raise ValueError("nothing requested: want_power=False needs peaks > 0")
+        grids, f0, delta, f_offsets = self._ragged_grids(signals)
+        t = np.concatenate([np.asarray(s.time, dtype=float) for s in signals])
+        y = np.concatenate([np.asarray(s.values, dtype=float) for s in signals])
+        offsets = np.zeros(len(signals) + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([len(s) for s in signals])
+        dy = None
+        if errs is not None and any(e is not None for e in errs):
+            parts = []
+            for s, e in zip(signals, errs):
+                e = np.ones(len(s)) if e is None else np.asarray(e, dtype=float).ravel()
+                if e.size != len(s):
+                    raise ValueError("Input arrays have incompatible lengths.")
+                parts.append(e)
+            dy = np.concatenate(parts)
+        devices = self.devices if self.devices else None
+        if peaks:
+            out = _cabi.gls_ragged_peaks(t, y, dy, offsets, f0, delta, f_offsets, k=peaks, by_prominence=by_prominence,
+                                         fit_mean=fit_mean, psd=self.psd, want_power=want_power, device=self.device,
+                                         devices=devices)
+            power = out["power"]
+            table = PeakTable(grids, out, by_prominence)
+        else:
+            power = _cabi.gls_scan_ragged(t, y, dy, offsets, f0, delta, f_offsets, fit_mean, self.psd,
+                                          device=self.device, devices=devices)[0]
+            table = None
+        periodograms = None
+        if want_power:
+            periodograms = [FSeries(g, power[f_offsets[b]:f_offsets[b + 1]]) for b, g in enumerate(grids)]
+        return GLSBatch(grids, periodograms, table)
+
     def bootstrap(self, n_bootstraps, random_seed=None):
         """Maxima of ``n_bootstraps`` periodograms of ``(values, err)`` resampled with replacement
         on the unchanged time axis (``spectral.py:140-152``).  The draws come from
@@ -184,6 +260,48 @@ class GLS(object):
 
 
 LombScargle = GLS
+
+
+class PeakTable(object):
+    """The ``k`` best peaks of every spectrum of a ``GLS.batch`` call, ``[B][k]`` arrays ranked descending (by
+    height, or by prominence), padded with NaN (``index``: -1) past a curve's ``count`` of ``find_peaks`` maxima.
+
+    ``period_lo[b, r]``, ``period_hi[b, r]`` are the pair ``periods_at_half_max(r + 1, use_prominence=by_prominence)``
+    returns for curve ``b`` (``core.py:963-978``); each is NaN where that method finds no crossing on its side.
+    """
+
+    def __init__(self, grids, out, by_prominence):
+        self.by_prominence = bool(by_prominence)
+        self.count = out["count"]
+        self.index = out["indices"]
+        self.height = out["heights"]
+        self.prominence = out["prominences"]
+        B, k = self.index.shape
+        self.frequency = np.full((B, k), np.nan)
+        self.period_lo = np.full((B, k), np.nan)
+        self.period_hi = np.full((B, k), np.nan)
+        for b, g in enumerate(grids):
+            for name, idx in (("frequency", self.index[b]), ("period_lo", out["half_lo"][b]),
+                              ("period_hi", out["half_hi"][b])):
+                ok = idx >= 0
+                getattr(self, name)[b, ok] = g[idx[ok]]
+        with np.errstate(divide="ignore"):
+            self.period = 1.0 / self.frequency
+            self.period_lo = 1.0 / self.period_lo
+            self.period_hi = 1.0 / self.period_hi
+
+
+class GLSBatch(object):
+    """What ``GLS.batch`` returns: ``frequency`` (one grid per curve), ``periodograms`` (one ``FSeries`` per curve,
+    or None) and ``peaks`` (a :class:`PeakTable`, or None)."""
+
+    def __init__(self, frequency, periodograms, peaks):
+        self.frequency = frequency
+        self.periodograms = periodograms
+        self.peaks = peaks
+
+    def __len__(self):
+        return len(self.frequency)
 
 
 class BGLST(GLS):
@@ -283,3 +401,6 @@ class BGLST(GLS):
         raise NotImplementedError("BGLST has no bootstrap: the log-likelihood itself carries the significance")
 
     fap = fal = window = model = bootstrap
+
+    def batch(self, *args, **kwargs):
+        raise NotImplementedError("BGLST.batch is not implemented: the ragged-grid batch computes GLS power only")
