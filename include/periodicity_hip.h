@@ -340,6 +340,57 @@ int pdc_gls_scan_ragged_dev(int device, void *stream, const double *d_t, const d
                             int fit_mean, int psd, double *d_power, double *d_pitched, int64_t pitch,
                             double *d_amax, int64_t *d_argmax, void *work, int64_t work_bytes);
 
+/* ---- PDM / AoV / conditional entropy over curves on their OWN period grids (PDM.batch ...) ---------
+ * Replaces a survey's loop of PDM()(s), AOV()(s) or ConditionalEntropy()(s) (each curve on the grid its own
+ * data give: np.linspace(p_min, p_max, count), p_min = 2 median_dt, p_max = oversample baseline,
+ * phase.py:167-180) followed by find_dips / find_peaks / periods_at_half_max on each result.
+ * kind: 0 PDM theta over nb x nc covers (sigma[b] = np.var(values_b, ddof=1) is required), 1 AoV over nb
+ * phase bins (nc ignored), 2 conditional entropy over nb phase x nc magnitude bins (x = the magnitude bin
+ * of every sample, 0 .. nc-1; a curve may have at most 65 280 samples: one workgroup bins it in 16-bit cells).
+ * Curve b owns samples [offsets[b], offsets[b+1]) of t and x and the trial periods
+ * linspace(start[b], stop[b], P_b), P_b = p_offsets[b+1] - p_offsets[b], rebuilt on the device with numpy's
+ * rule: j*step[b] + start[b] (two roundings), exactly stop[b] at j = P_b - 1 > 0; for P_b == 1 pass
+ * step = stop - start.  significant[b] (or NULL: none) turns on the sub-harmonic averaging of PDM's
+ * do_subharmonic with that threshold (1 - 11 / N**0.8, computed by the caller); it needs P_b >= 2.
+ * Values come back in period order, out[p_offsets[b] + j].  For a curve of < 8192 samples and < 131 072
+ * periods they are bit-identical to pdc_pdm_scan / pdc_aov_scan / pdc_cond_entropy_scan on that curve;
+ * longer curves agree to rounding (the single call splits them otherwise).
+ * Devices, groups and budget as for pdc_gls_scan_ragged: curves are dealt to the `n_devices` listed slots
+ * in contiguous groups balanced by sum n_b P_b, per-slot buffers are kept (pdc_release frees them),
+ * groups fit PDC_WORK_BUDGET_GB and free memory, and results are bit-identical for any grouping.
+ *
+ * pdc_phase_ragged_peaks: the [B][k] peak table (k <= 1024) of pdc_gls_ragged_peaks on every curve's row in
+ * FSeries order (ascending frequency 1/p: index j' = P_b - 1 - j when stop[b] > start[b], j' = j otherwise; that is
+ * FSeries' order for grids whose periods share one sign and have distinct reciprocals): of its DIPS for PDM and
+ * conditional entropy (find_dips, ranked deepest first; height_out holds the statistic itself, the half-maximum
+ * crossings are those of the negated row), of its peaks for AoV.  out may be NULL: the rows stay in HBM.
+ *
+ * pdc_phase_ragged_work_bytes / pdc_phase_scan_ragged_dev: ONE launch sequence on `device` / `stream`, no
+ * grouping: t, x on the device; offsets ... significant on the HOST (the entry waits for their upload before
+ * it returns, not for the launches).  d_out [p_offsets[B]] and/or d_pitched [B][pitch] (FSeries order, negated
+ * for the dip kinds; its pad is the caller's).  work_bytes >= pdc_phase_ragged_work_bytes(B, p_offsets[B], 0, 0);
+ * p_max > 0 and k > 0 size the group workspace of the peak entry (+ the pitched copy and the [B][k] table). */
+int pdc_phase_scan_ragged(int kind, const double *t, const double *x, const int64_t *offsets,
+                          int64_t n_curves, const double *start, const double *step, const double *stop,
+                          const int64_t *p_offsets, const double *sigma, const double *significant, int nb,
+                          int nc, double *out, const int *devices, int n_devices);
+int pdc_phase_ragged_peaks(int kind, const double *t, const double *x, const int64_t *offsets,
+                           int64_t n_curves, const double *start, const double *step, const double *stop,
+                           const int64_t *p_offsets, const double *sigma, const double *significant, int nb,
+                           int nc, int k, int by_prominence, int64_t *count_out, int64_t *idx_out,
+                           double *height_out, double *prominence_out, int64_t *half_lo_out,
+                           int64_t *half_hi_out, double *out, const int *devices, int n_devices);
+int64_t pdc_phase_ragged_work_bytes(int64_t n_curves, int64_t p_total, int64_t p_max, int k);
+/* TEST HOOK (not for callers): how many groups of curves the last pdc_phase_scan_ragged / pdc_phase_ragged_peaks call
+ * of this process ran, summed over its device slots (1 per busy slot when everything fit the budget). */
+int pdc_test_phase_ragged_groups(int64_t *groups);
+int pdc_phase_scan_ragged_dev(int kind, int device, void *stream, const double *d_t, const double *d_x,
+                              const int64_t *offsets, int64_t n_curves, const double *start,
+                              const double *step, const double *stop, const int64_t *p_offsets,
+                              const double *sigma, const double *significant, int nb, int nc,
+                              double *d_out, double *d_pitched, int64_t pitch, void *work,
+                              int64_t work_bytes);
+
 /* ---- Phase Dispersion Minimization -----------------------------------------------------------
  * Replaces pool.map(PDM._pdm, periods) (phase.py:128-149, 185-187): theta_out[p] for every trial
  * period, bins phi in [k/m0, (k+nc)/m0) U [0, (k+nc-m0)/m0), m0 = nb*nc, phi = (t/period) % 1

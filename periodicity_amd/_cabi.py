@@ -87,6 +87,13 @@ PROTOTYPES = {
     "pdc_gls_ragged_work_bytes": (_L, [_L, _L, _L, _L, _I]),
     "pdc_gls_scan_ragged_dev": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _I, _I,
                                      _VP, _VP, _L, _VP, _VP, _VP, _L]),
+    "pdc_phase_scan_ragged": (_I, [_I, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _I]),
+    "pdc_phase_ragged_peaks": (_I, [_I, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I,
+                                    _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I]),
+    "pdc_phase_ragged_work_bytes": (_L, [_L, _L, _L, _I]),
+    "pdc_test_phase_ragged_groups": (_I, [C.POINTER(_L)]),
+    "pdc_phase_scan_ragged_dev": (_I, [_I, _I, _VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I,
+                                       _VP, _VP, _L, _VP, _L]),
     "pdc_pdm_scan": (_I, [_VP, _VP, _L, _VP, _L, _I, _I, _D, _VP, _I]),
     "pdc_pdm_scan_dev": (_I, [_I, _VP, _VP, _VP, _L, _VP, _L, _I, _I, _D, _VP]),
     "pdc_aov_scan": (_I, [_VP, _VP, _L, _VP, _L, _I, _VP, _I]),
@@ -564,6 +571,36 @@ def gls_ragged_peaks(t, y, dy, offsets, f0, delta, f_offsets, k=1, by_prominence
                                      _ptr(out["heights"]), _ptr(out["prominences"]), _ptr(out["half_lo"]),
                                      _ptr(out["half_hi"]), _ptr(out["power"]), _ptr(devs), devs.size))
     return out
+
+
+def phase_scan_ragged(kind, t, x, offsets, start, step, stop, p_offsets, nb, nc, sigma=None, significant=None,
+                      k=0, by_prominence=False, want_power=True, device=None, devices=None):
+    """PDM (kind 0), AoV (1) or conditional entropy (2) over a batch of curves, each on its own period grid
+    ``linspace(start[b], stop[b], p_offsets[b+1] - p_offsets[b])`` (``pdc_phase_scan_ragged``; with ``k > 0``
+    ``pdc_phase_ragged_peaks``): ``(out [p_offsets[-1]] | None, peak table dict | None)``."""
+    t, x = _f64(t, "t"), _f64(x, "x")
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    p_offsets = np.ascontiguousarray(p_offsets, dtype=np.int64)
+    start, step, stop = _f64(start, "start"), _f64(step, "step"), _f64(stop, "stop")
+    sigma = None if sigma is None else _f64(sigma, "sigma")
+    significant = None if significant is None else _f64(significant, "significant")
+    nb_ = offsets.size - 1
+    if nb_ < 1 or p_offsets.size != nb_ + 1 or any(a.size != nb_ for a in (start, step, stop)):
+        raise ValueError("offsets / p_offsets need n_curves + 1 entries, start / step / stop n_curves")
+    if offsets[-1] != t.size or x.size != t.size:
+        raise ValueError("Input arrays have incompatible lengths.")
+    out = np.empty(int(p_offsets[-1]), dtype=np.float64) if want_power else None
+    devs = _slots(device, devices)
+    common = (int(kind), _ptr(t), _ptr(x), _ptr(offsets), nb_, _ptr(start), _ptr(step), _ptr(stop), _ptr(p_offsets),
+              _ptr(sigma), _ptr(significant), int(nb), int(nc))
+    if not k:
+        check(lib().pdc_phase_scan_ragged(*common, _ptr(out), _ptr(devs), devs.size))
+        return out, None
+    table = _topk_outputs(nb_, int(k))
+    check(lib().pdc_phase_ragged_peaks(*common, int(k), int(bool(by_prominence)), _ptr(table["count"]),
+                                       _ptr(table["indices"]), _ptr(table["heights"]), _ptr(table["prominences"]),
+                                       _ptr(table["half_lo"]), _ptr(table["half_hi"]), _ptr(out), _ptr(devs), devs.size))
+    return out, table
 
 
 def pdm_scan(t, x, periods, nb, nc, sigma, device=None, devices=None):

@@ -23,6 +23,8 @@ int cached(int device, Slot slot, int64_t bytes, void **dptr);
 void release_multi();
 // Frees the per-slot buffers and streams the ragged-grid GLS host entries keep between calls (gls_ragged.hip).
 int release_ragged();
+// ... and those of the ragged-grid PDM / AoV / conditional-entropy host entries (pdm_ragged.hip).
+int release_phase_ragged();
 
 // Every device / pinned-host allocation of the library goes through these two, so that
 // pdc_alloc_counts() can show a caller (and the tests) that a cached path allocates nothing on

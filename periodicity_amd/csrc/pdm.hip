@@ -32,12 +32,7 @@ using namespace pdc;
 
 namespace {
 
-// samples staged per barrier (256 = the staging area a 256-thread workgroup owns anyway; 128 measured 2 %,
-// 64 10 % slower at C5)
-#ifndef PDC_PDM_CHUNK
-#define PDC_PDM_CHUNK 256
-#endif
-constexpr int kChunk = PDC_PDM_CHUNK;
+#include "pdm_common.h"
 
 constexpr int kStatParts = 512;  // partial sums of the sample statistics (split mode)
 constexpr int kCUs = 256;        // MI355X
@@ -66,20 +61,6 @@ struct PdmArgs {
     // phase bins x nc magnitude bins, x = magnitude bin of every sample)
     int kind = 0;
 };
-
-template <int BLOCK>
-__device__ __forceinline__ double block_reduce(double v, double *red, bool take_max) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const double u = __shfl_down(v, o, 64);
-        v = take_max ? (u > v ? u : v) : v + u;
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = red[0];
-    for (int w = 1; w < BLOCK / 64; ++w) r = take_max ? (red[w] > r ? red[w] : r) : r + red[w];
-    return r;
-}
 
 // Fixed-order fold of `count` partial values by a whole workgroup (identical in every workgroup).
 template <int BLOCK>
@@ -116,126 +97,6 @@ __global__ __launch_bounds__(256) void pdm_stats_kernel(PdmArgs a, int pass) {
             a.stat[2 * kStatParts + blockIdx.x] = acc;
         }
     }
-}
-
-// theta from one period's fine-bin histogram (phase.py:137-148); sum_at / cnt_at read bin b.
-template <typename SumAt, typename CntAt>
-__device__ __forceinline__ double theta_from_bins(SumAt sum_at, CntAt cnt_at, int m0, int nc, double q_total,
-                                                  double q_nan, double q_over, double sigma) {
-    double num = (double)nc * (q_total - q_nan) - q_over;
-    long long n_sum = 0;
-    int good = 0;
-    for (int k = 0; k < m0; ++k) {
-        double s = 0.0;
-        long long c = 0;
-        for (int j = 0; j < nc; ++j) {
-            int b = k + j;
-            if (b >= m0) {
-                if (b == m0) {  // [1.0, (m0+1)/m0): only phi == 1.0 can live here
-                    s += sum_at(m0);
-                    c += cnt_at(m0);
-                }
-                b -= m0;
-            }
-            s += sum_at(b);
-            c += cnt_at(b);
-        }
-        if (c > 1) {
-            num -= s * s / (double)c;
-            n_sum += c;
-            ++good;
-        } else if (c == 1) {
-            num -= s * s;  // a singleton contributes x^2 - x^2 = 0 and is not a "good" bin
-        }
-    }
-    // no cover with two or more members: the reference divides an empty sum by zero -> NaN
-    // (phase.py:147); here `num` would only hold the rounding residue of the singletons
-    return good == 0 ? __builtin_nan("") : (num / (double)(n_sum - good)) / sigma;
-}
-
-// Analysis of Variance (Schwarzenberg-Czerny 1989, MNRAS 241, 153, eq. 1-3) from the same histogram:
-// r = m0 phase bins [k/r, (k+1)/r) (phi == 1.0 joins the last one), n valid samples,
-//     s1^2 = sum_i n_i (xbar_i - xbar)^2 / (r - 1),   s2^2 = sum_i sum_j (x_ij - xbar_i)^2 / (n - r),
-// Theta_AoV = s1^2 / s2^2.  With S_i = sum of the (mean-shifted) samples of bin i and Q their total
-// square: between = sum S_i^2 / n_i - (sum S_i)^2 / n,  within = Q - sum S_i^2 / n_i.
-template <typename SumAt, typename CntAt>
-__device__ __forceinline__ double aov_from_bins(SumAt sum_at, CntAt cnt_at, int m0, double q_valid) {
-    double per_bin = 0.0, s_all = 0.0;
-    long long n = 0;
-    for (int k = 0; k < m0; ++k) {
-        double s = sum_at(k);
-        long long c = cnt_at(k);
-        if (k == m0 - 1) {
-            s += sum_at(m0);
-            c += cnt_at(m0);
-        }
-        if (c > 0) per_bin += s * s / (double)c;
-        s_all += s;
-        n += c;
-    }
-    if (n <= m0 || m0 < 2) return __builtin_nan("");
-    const double between = per_bin - s_all * s_all / (double)n;
-    const double within = q_valid - per_bin;
-    return ((double)(n - m0) * between) / ((double)(m0 - 1) * within);
-}
-
-// Conditional entropy (Graham et al. 2013, MNRAS 434, 2629, eq. 1): H_c = sum_ij p(m_j, phi_i)
-// ln(p(phi_i) / p(m_j, phi_i)) over the occupied cells of an m0 x mag (phase x magnitude) partition;
-// cnt_at(i * mag + j) reads cell (i, j), row m0 (phi == 1.0) joins row m0 - 1.
-template <typename CntAt>
-__device__ __forceinline__ double ce_from_bins(CntAt cnt_at, int m0, int mag) {
-    long long n = 0;
-    for (int c = 0; c < (m0 + 1) * mag; ++c) n += cnt_at(c);
-    if (n == 0) return __builtin_nan("");
-    double h = 0.0;
-    for (int i = 0; i < m0; ++i) {
-        long long row = 0;
-        for (int j = 0; j < mag; ++j) row += cnt_at(i * mag + j) + (i == m0 - 1 ? cnt_at(m0 * mag + j) : 0);
-        for (int j = 0; j < mag; ++j) {
-            const long long c = cnt_at(i * mag + j) + (i == m0 - 1 ? cnt_at(m0 * mag + j) : 0);
-            if (c > 0) h += ((double)c / (double)n) * log((double)row / (double)c);
-        }
-    }
-    return h;
-}
-
-// Gregory & Loredo (1992, ApJ 398, 146): arrival times t_i, model M_m = a periodic rate that is constant in
-// each of m phase bins.  For trial frequency w and phase offset phi the likelihood depends on the data only
-// through the multiplicity W_m(w, phi) = N! / (n_1! ... n_m!) of the bin counts (their eq. 5.13-5.14), and
-// the marginal over the offset,
-//     S_m(w) = (1 / 2 pi) Int dphi  m^N / W_m(w, phi),
-// is what the odds ratio O_m1 (eq. 5.28) integrates over dw / w.  Here: ln S_m(w) with the offset integral as
-// the mean over `offsets` equally spaced shifts of the bin boundaries by 1 / (m offsets) of a cycle - the
-// counts of every shift are sums of `offsets` consecutive FINE bins of a histogram over F = m offsets bins
-// [f / F, (f + 1) / F) (phi == 1.0 joins the last), cnt_at(f).  Log-sum-exp over the shifts, lgamma for the
-// factorials.
-template <typename CntAt>
-__device__ __forceinline__ double gl_from_bins(CntAt cnt_at, int F, int m) {
-    const int offsets = F / m;
-    long long n = 0;
-    for (int f = 0; f <= F; ++f) n += cnt_at(f);
-    if (n == 0 || offsets < 1) return __builtin_nan("");
-    const double base = (double)n * log((double)m) - lgamma((double)n + 1.0);
-    double top = 0.0, sum = 0.0;
-    for (int k = 0; k < offsets; ++k) {
-        double lw = base;
-        int f = k;
-        for (int j = 0; j < m; ++j) {
-            long long c = 0;
-            for (int i = 0; i < offsets; ++i) {
-                c += cnt_at(f) + (f == F - 1 ? cnt_at(F) : 0);
-                f = f + 1 == F ? 0 : f + 1;
-            }
-            lw += lgamma((double)c + 1.0);
-        }
-        if (k == 0 || lw > top) {   // running log-sum-exp
-            sum = k == 0 ? 1.0 : sum * exp(top - lw) + 1.0;
-            top = lw;
-        } else {
-            sum += exp(lw - top);
-        }
-    }
-    return top + log(sum / (double)offsets);
 }
 
 // SPLIT waves of a workgroup share one group of 64 trial periods (lane = period) and split every
@@ -315,127 +176,7 @@ __global__ __launch_bounds__(BLOCK) void pdm_scan_kernel(PdmArgs a) {
     // this workgroup's samples: all of them, or slice blockIdx.y of them in split mode
     const int64_t s_begin = ZS ? (int64_t)blockIdx.y * a.z_len : 0;
     const int64_t s_end = ZS ? (s_begin + a.z_len < a.n ? s_begin + a.z_len : a.n) : a.n;
-    for (int64_t base = s_begin; base < s_end; base += kChunk) {
-        __syncthreads();
-        for (int i = tid; i < kChunk; i += BLOCK) {
-            const int64_t g = base + i;
-            double2 v = g < s_end ? make_double2(a.t[g], GL ? 0.0 : (CE ? a.x[g] : a.x[g] - mean)) : make_double2(0.0, 0.0);
-            if (KIND == 2 && !(v.y >= 0.0 && v.y < (double)mag)) {
-                // the magnitude bin is the caller's double and indexes the cell histogram: anything outside
-                // 0 .. mag-1 (NaN included) is staged with a NaN time - its phase is NaN, so it takes the exact
-                // path and counts nowhere, exactly as if the sample were absent (the host entries reject such
-                // input; `_dev` callers get this).  Checked once per staged sample, not once per pair.
-                v = make_double2(__builtin_nan(""), 0.0);
-            }
-            stage[i] = v;
-        }
-        __syncthreads();
-        const int cnt = (int)((s_end - base) < kChunk ? (s_end - base) : kChunk);
-        const int i_end = cnt < (part + 1) * (kChunk / SPLIT) ? cnt : (part + 1) * (kChunk / SPLIT);
-        // two samples per trip: two independent read -> bin -> atomic chains in flight per wave.
-        // Fast path: 7 VALU ops (v_fract_f64 twice); the histogram update is unconditional.
-        auto fast_bin = [&](const double t, int &k) -> bool {
-            const double u = __builtin_amdgcn_fract(t * rp) * dm0;
-            k = (int)u;
-            return __builtin_fabs(__builtin_amdgcn_fract(u) - 0.5) < thr;
-        };
-        // exact path: numpy's float remainder of the IEEE quotient, explicit edges; a NaN phase
-        // belongs to no bin (adds zero to bin 0)
-        auto exact_bin = [&](const double2 tx, int &k, double &val, unsigned &inc) {
-            const double qe = tx.x / period;
-            const double phi = qe - __builtin_floor(qe);  // == fmod-based Python % for divisor 1
-            if (phi != phi) {
-                q_nan += tx.y * tx.y;
-                k = 0;
-                val = 0.0;
-                inc = 0u;
-                return;
-            }
-            k = (int)(phi * dm0);
-            k = k < 0 ? 0 : (k > m0 ? m0 : k);
-            while (k > 0 && phi < edge[k]) --k;
-            while (k < m0 && phi >= edge[k + 1]) ++k;
-            if (k == m0) q_over += tx.y * tx.y;
-        };
-        auto add = [&](const int k, const double val, const unsigned inc) {
-            if (CE) {   // val = the sample's magnitude bin (range-checked when staged); a NaN phase (inc == 0) counts nowhere
-                const int cell = k * mag + (int)val;
-                atomicAdd(&hcnt[(cell >> 1) * BLOCK + tid], inc << ((cell & 1) * 16));
-            } else {
-                atomicAdd(&hsum[k * BLOCK + tid], val);
-                atomicAdd(&hcnt[k * BLOCK + tid], inc);
-            }
-        };
-        auto update = [&](const double2 tx) {
-            int k;
-            double val = tx.y;
-            unsigned inc = 1u;
-            if (!fast_bin(tx.x, k)) exact_bin(tx, k, val, inc);
-            add(k, val, inc);
-        };
-        int i = part * (kChunk / SPLIT);
-        // the samples of the next trip are read before this trip's histogram atomics go out (the compiler
-        // cannot move an LDS read above a possibly aliasing LDS atomic by itself); the staging area
-        // is followed by the histograms, so reading a few entries past the chunk is harmless
-        {   // four samples per trip: four independent read -> bin -> atomic chains in flight per wave (two per
-            // trip measured 3.5-8 % slower on one box); the next four are read before this trip's atomics go out
-            double2 n0 = stage[i], n1 = stage[i + 1], n2 = stage[i + 2], n3 = stage[i + 3];
-            for (; i + 3 < i_end; i += 4) {
-                const double2 t0 = n0, t1 = n1, t2 = n2, t3 = n3;
-                n0 = stage[i + 4];
-                n1 = stage[i + 5];
-                n2 = stage[i + 6];
-                n3 = stage[i + 7];
-                int k0, k1, k2, k3;
-                double v0 = t0.y, v1 = t1.y, v2 = t2.y, v3 = t3.y;
-                unsigned i0 = 1u, i1 = 1u, i2 = 1u, i3 = 1u;
-                const bool f0 = fast_bin(t0.x, k0), f1 = fast_bin(t1.x, k1), f2 = fast_bin(t2.x, k2), f3 = fast_bin(t3.x, k3);
-                if (!f0) exact_bin(t0, k0, v0, i0);
-                add(k0, v0, i0);
-                if (!f1) exact_bin(t1, k1, v1, i1);
-                add(k1, v1, i1);
-                if (!f2) exact_bin(t2, k2, v2, i2);
-                add(k2, v2, i2);
-                if (!f3) exact_bin(t3, k3, v3, i3);
-                add(k3, v3, i3);
-            }
-        }
-        double2 na = stage[i], nb2 = stage[i + 1];
-        for (; i + 1 < i_end; i += 2) {
-            // both fast bins first: two independent dependency chains back to back
-            const double2 ta = na, tb = nb2;
-            na = stage[i + 2];
-            nb2 = stage[i + 3];
-            int ka, kb;
-            double va = ta.y, vb = tb.y;
-            unsigned ia = 1u, ib = 1u;
-            const bool fa = fast_bin(ta.x, ka), fb = fast_bin(tb.x, kb);
-            if (!fa) exact_bin(ta, ka, va, ia);
-            add(ka, va, ia);
-            if (!fb) exact_bin(tb, kb, vb, ib);
-            add(kb, vb, ib);
-        }
-        for (; i < i_end; ++i) update(stage[i]);
-    }
-
-    if (SPLIT > 1) {
-        // fold the partial histograms of parts 1..SPLIT-1 into part 0 (threads tid + 64*q)
-        __syncthreads();
-        double *qx = reinterpret_cast<double *>(stage);  // q_over / q_nan exchange, [2][BLOCK]
-        qx[tid] = q_over;
-        qx[BLOCK + tid] = q_nan;
-        __syncthreads();
-        if (part == 0) {
-            for (int q = 1; q < SPLIT; ++q) {
-                const int other = tid + 64 * q;
-                for (int k = 0; k < nbins; ++k)
-                    if (!CE) hsum[k * BLOCK + tid] += hsum[k * BLOCK + other];
-                for (int k = 0; k < ncw; ++k) hcnt[k * BLOCK + tid] += hcnt[k * BLOCK + other];   // (fields cannot carry)
-                q_over += qx[other];
-                q_nan += qx[BLOCK + other];
-            }
-        }
-    }
+#include "pdm_chunks.inc"
     if (part != 0 || pidx >= a.n_periods) return;
     if (ZS) {  // split mode: leave the histogram of this slice of the samples for pdm_finish_kernel
         const int64_t z = blockIdx.y;
@@ -543,14 +284,6 @@ __global__ __launch_bounds__(64 * kFinZ) void pdm_finish_kernel(PdmArgs a) {
     else a.theta[pidx] = theta_from_bins(sum_at, cnt_at, m0, a.nc, q_total, q_nan, q_over, a.sigma);
 }
 
-// `last` = highest histogram bin; bytes_per_bin 12: sum + count, 4: counts only (two 16-bit cells per word)
-size_t lds_bytes(int last, int block, int bytes_per_bin = 12) {
-    const size_t stage = (size_t)(kChunk > block ? kChunk : block) * 16;
-    const size_t nbins = (size_t)last + 1;
-    const size_t hist = bytes_per_bin == 4 ? ((nbins + 1) / 2 + 1) * block * 4 : nbins * block * 12;
-    return stage + hist + (size_t)(last + 2) * 8 + 64;
-}
-
 // dynamic-LDS limit of a kernel, raised once per device (not on every call)
 template <typename Kernel>
 int allow_lds(Kernel kernel) {
@@ -566,7 +299,6 @@ struct SplitShape {
     size_t stat_b = 0, psum_b = 0, pq_b = 0, pcnt_b = 0;
 };
 
-constexpr int64_t kCellSamples = 65280;   // samples a workgroup of a counts-only kind may bin: its cells are 16-bit
 
 SplitShape split_shape(int kind, int64_t n, int64_t n_periods, int nb, int nc) {
     static const int env_split = [] { const char *e = getenv("PDC_PDM_SPLIT"); return e ? atoi(e) : -1; }();

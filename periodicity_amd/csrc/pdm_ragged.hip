@@ -1,0 +1,715 @@
+// PDM, AoV and conditional entropy over a batch of light curves that each keep their OWN period grid ("ragged"
+// grids): PDM.batch, AOV.batch, ConditionalEntropy.batch.
+//
+// The phase-folding classes build every curve's grid from that curve's data - np.linspace(p_min, p_max, count)
+// with p_min = 2 median_dt, p_max = oversample baseline and, for n_periods=None, a count of their own
+// (phase.py:167-180) - so two curves almost never share one.  Here curve b owns samples [offsets[b], offsets[b+1])
+// and the trial periods linspace(start[b], stop[b], P_b), P_b = p_offsets[b+1] - p_offsets[b], written to
+// out[p_offsets[b] + j] (period order, as the single call's `_scan` returns them).
+//
+// Decomposition
+//   pdm_ragged_prep_kernel    one workgroup of BLOCK threads per curve: mean of x, max |t| and sum (x - mean)^2 by
+//                             block_reduce<BLOCK> over i = tid, tid + BLOCK, ...  - the order and the BLOCK of the
+//                             unsplit pdm_scan_kernel, whose every workgroup computes the same three values for
+//                             itself; so the scan below starts from the single call's bits.
+//   pdm_ragged_scan_kernel    one workgroup per (curve, tile of 64 trial periods), found by a scalar binary search
+//                             in a dispatch-order tile prefix table; tiles are dispatched costliest curve (most
+//                             samples) first.  The period of a lane is rebuilt with numpy's linspace rule
+//                             (j*step + start, two roundings - the unit is built with -ffp-contract=off - and
+//                             exactly `stop` at the last index), not uploaded.  The sample loop is
+//                             pdm_chunks.inc, the text of pdm_scan_kernel's; the <BLOCK, SPLIT> instance is the one
+//                             the single call takes for a grid of < 131 072 periods (<256, 4>, or <64, 1> when
+//                             that histogram does not fit 150 KB of LDS), and so is the epilogue (pdm_common.h).
+//   pdm_ragged_finish_kernel  one workgroup per curve: the sub-harmonic averaging of
+//                             phase.py:_average_with_double_period (every read sees the scan's values), then the
+//                             output row and, for a peak table, a pitched [B][pitch] copy in FSeries order
+//                             (ascending frequency: the period index reversed when stop > start, kept when the
+//                             grid descends), negated for the kinds whose signal
+//                             is a minimum (PDM, conditional entropy) so that pdc_peaks_topk_dev ranks their dips.
+//                             The caller fills the pad with NaN; why the pad keeps scipy's answers, and the one
+//                             half-maximum artefact it leaves, is explained in gls_ragged.hip / periodicity_hip.h.
+//
+// Bit identity: for a curve whose single call runs unsplit (n < 8192 samples, P < 131 072 periods) every value is
+// computed by the same instructions on the same inputs in the same order.  Longer curves are split over workgroups
+// by the single call (another summation order) and agree to rounding.
+#include "pdc_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+using namespace pdc;
+
+namespace {
+
+#include "pdm_common.h"
+
+constexpr int kPTile = 64;   // trial periods per workgroup: BLOCK / SPLIT of both instances
+constexpr int kFinBlock = 256;
+
+struct RaggedPhaseArgs {
+    const double *t, *x;                          // samples of every curve; x = the magnitude bins for CE
+    const int64_t *offsets, *poff;                // [B + 1] samples, periods
+    const double *start, *step, *stop;            // [B] the linspace description of each grid
+    const double *sigma;                          // [B] PDM's np.var(values, ddof=1), else nullptr
+    const double *signif;                         // [B] 1 - 11 / N**0.8 (sub-harmonic averaging), or nullptr
+    const int64_t *otile, *order;                 // [m + 1] tile prefix in dispatch order, [m] curve at each position
+    int64_t m, tiles;
+    int nb, nc;
+    double *stat;                                 // [B][3] mean, max |t|, sum (x - mean)^2
+    double *raw;                                  // [P_total] the scan's statistic
+    double *out;                                  // [P_total] or nullptr (may be `raw`)
+    double *pitched;                              // [B][pitch] or nullptr
+    int64_t pitch;
+};
+
+// np.linspace(start, stop, count)[j]: y = j * step; y += start; y[-1] = stop (count > 1).  With count == 1 the host
+// passes step = stop - start (numpy's `y * delta`).
+__device__ __forceinline__ double linspace_at(int64_t j, int64_t count, double start, double step, double stop) {
+    if (count > 1 && j == count - 1) return stop;
+    return __dadd_rn(__dmul_rn((double)j, step), start);
+}
+
+template <int BLOCK, bool CE>
+__global__ __launch_bounds__(BLOCK) void pdm_ragged_prep_kernel(RaggedPhaseArgs ra) {
+    __shared__ double red[BLOCK / 64];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const int64_t off = ra.offsets[b], n = ra.offsets[b + 1] - off;
+    const double *t = ra.t + off, *x = ra.x + off;
+    // (pdm_scan_kernel's unsplit statistics, statement for statement)
+    double acc = 0.0, tmax = 0.0;
+    for (int64_t i = tid; i < n; i += BLOCK) {
+        acc += x[i];
+        const double at = __builtin_fabs(t[i]);
+        tmax = at > tmax ? at : tmax;
+    }
+    const double mean = block_reduce<BLOCK>(acc, red, false) / (double)n;
+    tmax = block_reduce<BLOCK>(tmax, red, true);
+    acc = 0.0;
+    for (int64_t i = tid; i < n && !CE; i += BLOCK) {
+        const double d = x[i] - mean;
+        acc += d * d;
+    }
+    const double q_total = block_reduce<BLOCK>(acc, red, false);
+    if (tid == 0) {
+        ra.stat[b * 3 + 0] = mean;
+        ra.stat[b * 3 + 1] = tmax;
+        ra.stat[b * 3 + 2] = q_total;
+    }
+}
+
+template <int BLOCK, int SPLIT, int KIND>
+__global__ __launch_bounds__(BLOCK) void pdm_ragged_scan_kernel(RaggedPhaseArgs ra) {
+    static_assert(BLOCK / SPLIT == kPTile, "one tile of trial periods per workgroup");
+    constexpr bool CE = KIND == 2;   // counts only
+    constexpr bool GL = false;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const int64_t L = blockIdx.x;
+    // dispatch position: the p with otile[p] <= L < otile[p + 1] (every listed curve has >= 1 tile)
+    int64_t lo = 0, hi = ra.m - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (ra.otile[mid] <= L) lo = mid;
+        else hi = mid - 1;
+    }
+    const int64_t curve = ra.order[lo];
+    const int64_t tile = L - ra.otile[lo];
+    const int64_t off = ra.offsets[curve];
+    const int64_t n = ra.offsets[curve + 1] - off;
+    const int64_t po = ra.poff[curve];
+    const int64_t np = ra.poff[curve + 1] - po;
+    const struct {
+        const double *t, *x;
+    } a{ra.t + off, ra.x + off};   // (the names pdm_chunks.inc reads)
+
+    const int mag = KIND == 2 ? ra.nc : 1;
+    const int m0 = CE ? ra.nb : ra.nb * ra.nc;
+    const int nbins = (m0 + 1) * mag;
+    double2 *stage = reinterpret_cast<double2 *>(lds_raw);
+    constexpr int kStage = kChunk > BLOCK ? kChunk : BLOCK;
+    double *hsum = reinterpret_cast<double *>(stage + kStage);
+    const int ncw = CE ? (nbins + 1) / 2 : nbins;
+    unsigned *hcnt = reinterpret_cast<unsigned *>(hsum + (CE ? 0 : (size_t)nbins * BLOCK));
+    double *edge = reinterpret_cast<double *>(hcnt + (size_t)ncw * BLOCK);
+    const int tid = threadIdx.x;
+
+    for (int k = tid; k < m0 + 2; k += BLOCK) edge[k] = (double)k / (double)m0;
+    for (int k = 0; k < nbins; ++k)
+        if (!CE) hsum[k * BLOCK + tid] = 0.0;
+    for (int k = 0; k < ncw; ++k) hcnt[k * BLOCK + tid] = 0u;
+
+    const double mean = ra.stat[curve * 3 + 0], tmax = ra.stat[curve * 3 + 1], q_total = ra.stat[curve * 3 + 2];
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), part = wave % SPLIT;
+    const int slot = (wave / SPLIT) * 64 + (tid & 63);
+    const int64_t pidx = tile * kPTile + slot;
+    const double period = pidx < np ? linspace_at(pidx, np, ra.start[curve], ra.step[curve], ra.stop[curve]) : 1.0;
+    const double rp = 1.0 / period;
+    const double dm0 = (double)m0;
+    const double eps = dm0 * (8.9e-16 * tmax * __builtin_fabs(rp) + 8.9e-16);
+    const double thr = 0.5 - eps;
+    double q_over = 0.0;
+    double q_nan = 0.0;
+    const int64_t s_begin = 0, s_end = n;
+#include "pdm_chunks.inc"
+    if (part != 0 || pidx >= np) return;
+    auto sum_at = [&](int b) { return hsum[b * BLOCK + tid]; };
+    auto cnt_at = [&](int b) {
+        return CE ? (long long)((hcnt[(b >> 1) * BLOCK + tid] >> ((b & 1) * 16)) & 0xFFFFu) : (long long)hcnt[b * BLOCK + tid];
+    };
+    double v;
+    if (CE) v = ce_from_bins(cnt_at, m0, mag);
+    else if (KIND == 1) v = aov_from_bins(sum_at, cnt_at, m0, q_total - q_nan);
+    else v = theta_from_bins(sum_at, cnt_at, m0, ra.nc, q_total, q_nan, q_over, ra.sigma[curve]);
+    ra.raw[po + pidx] = v;
+}
+
+// Sub-harmonic averaging (phase.py:_average_with_double_period) and the output rows of one curve.
+template <bool DIP>
+__global__ __launch_bounds__(kFinBlock) void pdm_ragged_finish_kernel(RaggedPhaseArgs ra) {
+    const int64_t b = blockIdx.x;
+    const int64_t po = ra.poff[b], np = ra.poff[b + 1] - po;
+    const double start = ra.start[b], step = ra.step[b], stop = ra.stop[b];
+    const bool sub = ra.signif != nullptr;   // (the host requires np >= 2 then)
+    const double significant = sub ? ra.signif[b] : 0.0;
+    const double spacing = sub ? linspace_at(1, np, start, step, stop) - linspace_at(0, np, start, step, stop) : 1.0;
+    const double lead = start / spacing, half = stop / 2.0;
+    // FSeries order is ascending frequency 1 / p: the reversed period index on an ascending grid, the period index
+    // on a descending (or constant) one - for grids whose periods have one sign, which the caller ensures
+    const bool rev = stop > start;
+    const double *raw = ra.raw + po;
+    for (int64_t j = threadIdx.x; j < np; j += kFinBlock) {
+        double v = raw[j];
+        if (sub && v < significant && linspace_at(j, np, start, step, stop) <= half) {
+            // np.round(2 * here + shortest / spacing).astype(int): half-to-even, then numpy's indexing
+            int64_t d = (int64_t)rint((double)(2 * j) + lead);
+            if (d < 0) d += np;
+            v = d >= 0 && d < np ? (v + raw[d]) / 2 : __builtin_nan("");
+        }
+        if (ra.out && ra.out != ra.raw) ra.out[po + j] = v;
+        if (ra.pitched) ra.pitched[b * ra.pitch + (rev ? np - 1 - j : j)] = DIP ? -v : v;
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------
+int64_t up256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+int64_t tiles_of(int64_t np) { return (np + kPTile - 1) / kPTile; }
+bool is_dip(int kind) { return kind != 1; }   // PDM theta and the conditional entropy are minimal at the period
+
+// The one instance per statistic and bin counts: `last` = highest histogram bin, bytes per bin 12 (sum + count) or
+// 4 (counts only), and whether the <256, 4> histogram fits 150 KB of LDS (else <64, 1>) - pdm.hip's choice.
+struct Shape {
+    int last, bpb, block;
+    size_t lds;
+};
+Shape shape_of(int kind, int nb, int nc) {
+    if (kind == 1) nc = 1;
+    const int m0 = kind == 2 ? nb : nb * nc;
+    Shape s;
+    s.last = kind == 2 ? (nb + 1) * nc - 1 : m0;
+    s.bpb = kind == 2 ? 4 : 12;
+    s.block = lds_bytes(s.last, 256, s.bpb) > 150 * 1024 ? 64 : 256;
+    s.lds = lds_bytes(s.last, s.block, s.bpb);
+    return s;
+}
+
+// Workspace of one launch over B curves: per-curve statistics, the metadata tables, the scan's rows; with k > 0
+// also the NaN-padded [B][p_max] copy and the [B][k] peak table.
+struct PhaseLayout {
+    int64_t stat, meta, raw, pitched, table, total;
+};
+constexpr int kMetaArrays = 9;   // offsets | poff | otile | order (int64) | start | step | stop | sigma | signif, B + 1 each
+
+PhaseLayout phase_layout(int64_t n_curves, int64_t p_total, int64_t p_max, int k) {
+    PhaseLayout w;
+    w.stat = 0;
+    w.meta = up256(n_curves * 24);
+    w.raw = w.meta + up256(kMetaArrays * (n_curves + 1) * 8);
+    w.pitched = w.raw + up256(p_total * 8);
+    w.table = w.pitched + (k > 0 ? up256(n_curves * p_max * 8) : 0);
+    // count | idx | half_lo | half_hi | height | prominence
+    w.total = w.table + (k > 0 ? up256((n_curves + 5 * n_curves * (int64_t)k) * 8) : 0);
+    return w;
+}
+
+const char *kind_name(int kind) { return kind == 0 ? "pdm" : (kind == 1 ? "aov" : "cond_entropy"); }
+
+// Checks the host-side description of a batch; the same text for every entry point.
+int validate(const char *what, int kind, const int64_t *offsets, int64_t n_curves, const double *start,
+             const double *step, const double *stop, const int64_t *poff, const double *sigma, const double *signif,
+             int nb, int nc) {
+    PDC_REQUIRE(kind >= 0 && kind <= 2, "%s: kind must be 0 (PDM), 1 (AoV) or 2 (conditional entropy), got %d", what, kind);
+    PDC_REQUIRE(offsets && start && step && stop && poff, "%s: NULL argument", what);
+    PDC_REQUIRE(kind != 0 || sigma, "%s: PDM needs sigma[]", what);
+    PDC_REQUIRE(n_curves >= 1 && n_curves < ((int64_t)1 << 31), "%s: n_curves must be 1 .. 2^31 - 1 (got %lld)", what,
+                (long long)n_curves);
+    PDC_REQUIRE(nb >= 1 && nc >= 1, "%s: bin counts must be positive", what);
+    const Shape s = shape_of(kind, nb, nc);
+    PDC_REQUIRE(s.last <= 190, "%s: %d histogram bins exceed the 191 that fit in LDS", what, s.last + 1);
+    PDC_REQUIRE(offsets[0] == 0 && poff[0] == 0, "%s: offsets[0] and p_offsets[0] must be 0", what);
+    int64_t tiles = 0;
+    for (int64_t b = 0; b < n_curves; ++b) {
+        const int64_t n = offsets[b + 1] - offsets[b], np = poff[b + 1] - poff[b];
+        PDC_REQUIRE(n >= 0, "%s: offsets must be non-decreasing (curve %lld)", what, (long long)b);
+        PDC_REQUIRE(np >= 0, "%s: p_offsets must be non-decreasing (curve %lld)", what, (long long)b);
+        PDC_REQUIRE(kind != 2 || n <= kCellSamples,
+                    "%s: curve %lld has %lld samples; a conditional-entropy batch bins a whole curve in one workgroup "
+                    "of 16-bit cells (at most %lld samples)", what, (long long)b, (long long)n, (long long)kCellSamples);
+        PDC_REQUIRE(!signif || np >= 2, "%s: curve %lld: sub-harmonic averaging needs at least two trial periods", what,
+                    (long long)b);
+        tiles += tiles_of(np);
+    }
+    PDC_REQUIRE(tiles < ((int64_t)1 << 31), "%s: %lld tiles of %d periods: the grids are too large for one launch",
+                what, (long long)tiles, kPTile);
+    return PDC_OK;
+}
+
+template <typename Kernel>
+int launch_scan(Kernel kernel, int block, const Shape &s, int64_t tiles, hipStream_t st, const RaggedPhaseArgs &a) {
+    PDC_TRY(allow_dynamic_lds((const void *)kernel, 150 * 1024));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3((unsigned)block), s.lds, st, a);
+    return PDC_OK;
+}
+
+// Every launch of one group of curves.  Metadata come from the host (offsets, p_offsets rebased to the group), the
+// sample arrays and the workspace are on the device.
+int phase_ragged_dev(int kind, int device, hipStream_t st, const double *d_t, const double *d_x, const int64_t *offsets,
+                     int64_t n_curves, const double *start, const double *step, const double *stop, const int64_t *poff,
+                     const double *sigma, const double *signif, int nb, int nc, double *d_out, double *d_pitched,
+                     int64_t pitch, void *work, int64_t work_bytes, std::vector<int64_t> &meta, bool wait_meta) {
+    const int64_t n_total = offsets[n_curves], p_total = poff[n_curves];
+    const PhaseLayout w = phase_layout(n_curves, p_total, 0, 0);   // (the pitched copy is the caller's)
+    PDC_REQUIRE(work && work_bytes >= w.total, "phase_ragged: workspace too small (%lld < %lld bytes)",
+                (long long)work_bytes, (long long)w.total);
+    PDC_REQUIRE(n_total == 0 || (d_t && d_x), "phase_ragged: t and x must not be NULL");
+    if (kind == 1) nc = 1;
+    PDC_TRY(use_device(device));
+    char *base = static_cast<char *>(work);
+    // metadata: one upload; dispatch order = curves with >= 1 tile, most samples first (ties: curve order)
+    const int64_t B1 = n_curves + 1;
+    meta.assign((size_t)(kMetaArrays * B1), 0);
+    int64_t *m_off = meta.data(), *m_poff = m_off + B1, *m_otile = m_poff + B1, *m_order = m_otile + B1;
+    double *m_start = reinterpret_cast<double *>(m_order + B1), *m_step = m_start + B1, *m_stop = m_step + B1,
+           *m_sigma = m_stop + B1, *m_signif = m_sigma + B1;
+    std::vector<int64_t> ord;
+    ord.reserve((size_t)n_curves);
+    for (int64_t b = 0; b < n_curves; ++b) {
+        m_off[b] = offsets[b];
+        m_poff[b] = poff[b];
+        m_start[b] = start[b];
+        m_step[b] = step[b];
+        m_stop[b] = stop[b];
+        m_sigma[b] = sigma ? sigma[b] : 1.0;
+        m_signif[b] = signif ? signif[b] : 0.0;
+        if (poff[b + 1] > poff[b]) ord.push_back(b);
+    }
+    m_off[n_curves] = n_total;
+    m_poff[n_curves] = p_total;
+    static const bool costly_first = [] { const char *e = getenv("PDC_RAGGED_ORDER"); return !(e && e[0] == '0'); }();
+    if (costly_first)
+        std::stable_sort(ord.begin(), ord.end(), [&](int64_t x, int64_t y) {
+            return offsets[x + 1] - offsets[x] > offsets[y + 1] - offsets[y];
+        });
+    const int64_t m = (int64_t)ord.size();
+    for (int64_t p = 0; p < m; ++p) {
+        m_order[p] = ord[(size_t)p];
+        m_otile[p + 1] = m_otile[p] + tiles_of(poff[ord[(size_t)p] + 1] - poff[ord[(size_t)p]]);
+    }
+    const int64_t tiles = m_otile[m];
+    int64_t *d_meta = reinterpret_cast<int64_t *>(base + w.meta);
+    PDC_HIP(hipMemcpyAsync(d_meta, meta.data(), (size_t)(kMetaArrays * B1 * 8), hipMemcpyHostToDevice, st));
+    if (wait_meta) PDC_HIP(hipStreamSynchronize(st));   // (`meta` goes when the caller returns)
+    const double *d_dbl = reinterpret_cast<const double *>(d_meta + 4 * B1);
+
+    RaggedPhaseArgs a = {};
+    a.t = d_t;
+    a.x = d_x;
+    a.offsets = d_meta;
+    a.poff = d_meta + B1;
+    a.otile = d_meta + 2 * B1;
+    a.order = d_meta + 3 * B1;
+    a.start = d_dbl;
+    a.step = d_dbl + B1;
+    a.stop = d_dbl + 2 * B1;
+    a.sigma = d_dbl + 3 * B1;
+    a.signif = signif ? d_dbl + 4 * B1 : nullptr;
+    a.m = m;
+    a.tiles = tiles;
+    a.nb = nb;
+    a.nc = nc;
+    a.stat = reinterpret_cast<double *>(base + w.stat);
+    // the scan writes the caller's rows directly unless the finishing pass still has to read them
+    a.raw = d_out && !signif ? d_out : reinterpret_cast<double *>(base + w.raw);
+    a.out = d_out;
+    a.pitched = d_pitched;
+    a.pitch = pitch;
+    const Shape s = shape_of(kind, nb, nc);
+    const bool ce = kind == 2;
+    if (s.block == 64) {
+        if (ce) hipLaunchKernelGGL((pdm_ragged_prep_kernel<64, true>), dim3((unsigned)n_curves), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((pdm_ragged_prep_kernel<64, false>), dim3((unsigned)n_curves), dim3(64), 0, st, a);
+    } else {
+        if (ce) hipLaunchKernelGGL((pdm_ragged_prep_kernel<256, true>), dim3((unsigned)n_curves), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((pdm_ragged_prep_kernel<256, false>), dim3((unsigned)n_curves), dim3(256), 0, st, a);
+    }
+    PDC_HIP(hipGetLastError());
+    if (tiles > 0) {
+        if (s.block == 64) {
+            if (kind == 2) PDC_TRY(launch_scan(pdm_ragged_scan_kernel<64, 1, 2>, 64, s, tiles, st, a));
+            else if (kind == 1) PDC_TRY(launch_scan(pdm_ragged_scan_kernel<64, 1, 1>, 64, s, tiles, st, a));
+            else PDC_TRY(launch_scan(pdm_ragged_scan_kernel<64, 1, 0>, 64, s, tiles, st, a));
+        } else {
+            if (kind == 2) PDC_TRY(launch_scan(pdm_ragged_scan_kernel<256, 4, 2>, 256, s, tiles, st, a));
+            else if (kind == 1) PDC_TRY(launch_scan(pdm_ragged_scan_kernel<256, 4, 1>, 256, s, tiles, st, a));
+            else PDC_TRY(launch_scan(pdm_ragged_scan_kernel<256, 4, 0>, 256, s, tiles, st, a));
+        }
+        PDC_HIP(hipGetLastError());
+    }
+    if (signif || d_pitched) {
+        if (is_dip(kind)) hipLaunchKernelGGL(pdm_ragged_finish_kernel<true>, dim3((unsigned)n_curves), dim3(kFinBlock), 0, st, a);
+        else hipLaunchKernelGGL(pdm_ragged_finish_kernel<false>, dim3((unsigned)n_curves), dim3(kFinBlock), 0, st, a);
+        PDC_HIP(hipGetLastError());
+    }
+    return PDC_OK;
+}
+
+// ---- host entries: curves dealt to device slots, each slot's share processed in groups that fit its budget ----
+struct RBuf {
+    void *p = nullptr;
+    int64_t cap = 0;
+};
+
+struct RSlot {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    RBuf buf;               // inputs | out | workspace of one group
+    std::vector<int64_t> meta;
+};
+
+std::mutex g_phase_mutex;
+std::vector<int> g_phase_devices;
+std::vector<RSlot> g_phase_slots;
+int64_t g_phase_groups = 0;   // groups the last host call ran, over all slots (pdc_test_phase_ragged_groups)
+
+int ensure_buf(RBuf &b, int64_t bytes) {   // (on the current device) grow-only
+    if (bytes < 256) bytes = 256;
+    if (b.cap >= bytes) return PDC_OK;
+    if (b.p) PDC_HIP(hipFree(b.p));
+    b.p = nullptr;
+    b.cap = 0;
+    PDC_TRY(device_alloc(&b.p, bytes + bytes / 8));
+    b.cap = bytes + bytes / 8;
+    return PDC_OK;
+}
+
+int free_slots() {
+    for (RSlot &s : g_phase_slots) {
+        PDC_HIP(hipSetDevice(s.device));
+        if (s.stream) PDC_HIP(hipStreamDestroy(s.stream));
+        if (s.buf.p) PDC_HIP(hipFree(s.buf.p));
+    }
+    g_phase_slots.clear();
+    g_phase_devices.clear();
+    return PDC_OK;
+}
+
+// What one host call computes and where its results go (caller's host arrays, any may be NULL).
+struct PhaseJob {
+    int kind, nb, nc, k, by_prominence;
+    const double *t, *x;
+    const int64_t *offsets, *poff;
+    const double *start, *step, *stop, *sigma, *signif;
+    double *out;
+    int64_t *count, *idx, *lo, *hi;
+    double *height, *prom;
+};
+
+// Bytes of the slot buffer for the group [c0, c1) whose longest grid has p_max periods.
+struct GroupBytes {
+    int64_t in_t, in_x, out, work, total;
+};
+GroupBytes group_bytes(const PhaseJob &j, int64_t c0, int64_t c1, int64_t p_max) {
+    const int64_t n = j.offsets[c1] - j.offsets[c0], np = j.poff[c1] - j.poff[c0], B = c1 - c0;
+    GroupBytes g;
+    g.in_t = 0;
+    g.in_x = up256(n * 8);
+    g.out = g.in_x + up256(n * 8);
+    g.work = g.out + (j.out ? up256(np * 8) : 0);
+    g.total = g.work + phase_layout(B, np, p_max, j.k).total;
+    return g;
+}
+int64_t np_of(const PhaseJob &j, int64_t b) { return j.poff[b + 1] - j.poff[b]; }
+
+// Contiguous groups of [c0, c1) of at most `cap` bytes each (a curve that alone exceeds it is a group of its own);
+// *largest = the bytes of the largest group.
+std::vector<int64_t> make_groups(const PhaseJob &j, int64_t c0, int64_t c1, int64_t cap, int64_t *largest) {
+    std::vector<int64_t> cut{c0};
+    *largest = 0;
+    int64_t g0 = c0, p_max = 0;
+    for (int64_t b = c0; b < c1; ++b) {
+        const int64_t grown = j.k > 0 ? std::max(p_max, np_of(j, b)) : 0;
+        if (b > g0 && group_bytes(j, g0, b + 1, grown).total > cap) {
+            *largest = std::max(*largest, group_bytes(j, g0, b, p_max).total);
+            cut.push_back(b);
+            g0 = b;
+            p_max = j.k > 0 ? np_of(j, b) : 0;
+        } else {
+            p_max = grown;
+        }
+    }
+    if (c1 > g0) *largest = std::max(*largest, group_bytes(j, g0, c1, p_max).total);
+    cut.push_back(c1);
+    return cut;
+}
+
+// One group on one slot, start to finish (the slot's stream is synchronised before return).
+int run_group(RSlot &s, const PhaseJob &j, int64_t c0, int64_t c1) {
+    const int64_t B = c1 - c0, s0 = j.offsets[c0], n = j.offsets[c1] - s0, pb = j.poff[c0], np = j.poff[c1] - pb;
+    int64_t p_max = 0;
+    for (int64_t b = c0; b < c1 && j.k > 0; ++b) p_max = std::max(p_max, np_of(j, b));
+    const GroupBytes g = group_bytes(j, c0, c1, p_max);
+    PDC_TRY(ensure_buf(s.buf, g.total));
+    char *p = static_cast<char *>(s.buf.p);
+    hipStream_t st = s.stream;
+    if (n > 0) {
+        PDC_HIP(hipMemcpyAsync(p + g.in_t, j.t + s0, n * 8, hipMemcpyHostToDevice, st));
+        PDC_HIP(hipMemcpyAsync(p + g.in_x, j.x + s0, n * 8, hipMemcpyHostToDevice, st));
+    }
+    std::vector<int64_t> off((size_t)B + 1), poff((size_t)B + 1);
+    for (int64_t b = 0; b <= B; ++b) {
+        off[(size_t)b] = j.offsets[c0 + b] - s0;
+        poff[(size_t)b] = j.poff[c0 + b] - pb;
+    }
+    const int k = j.k;
+    const PhaseLayout w = phase_layout(B, np, p_max, k);
+    char *work = p + g.work;
+    double *d_pitched = nullptr;
+    if (k > 0) {
+        d_pitched = reinterpret_cast<double *>(work + w.pitched);
+        // all-ones bytes: a NaN in every bin, the pad [P_b, p_max) stays so
+        PDC_HIP(hipMemsetAsync(d_pitched, 0xff, (size_t)(B * p_max * 8), st));
+    }
+    PDC_TRY(phase_ragged_dev(j.kind, s.device, st, (const double *)(p + g.in_t), (const double *)(p + g.in_x), off.data(),
+                             B, j.start + c0, j.step + c0, j.stop + c0, poff.data(), j.sigma ? j.sigma + c0 : nullptr,
+                             j.signif ? j.signif + c0 : nullptr, j.nb, j.nc, j.out ? (double *)(p + g.out) : nullptr,
+                             d_pitched, p_max, work, w.total, s.meta, false));
+    const int64_t nk = B * (int64_t)k;
+    int64_t *d_count = reinterpret_cast<int64_t *>(work + w.table), *d_idx = d_count + B, *d_lo = d_idx + nk,
+            *d_hi = d_lo + nk;
+    double *d_h = reinterpret_cast<double *>(d_hi + nk), *d_p = d_h + nk;
+    if (k > 0)
+        PDC_TRY(pdc_peaks_topk_dev(s.device, st, d_pitched, B, p_max, k, j.by_prominence, d_count, d_idx, d_h, d_p, d_lo,
+                                   d_hi));
+    if (j.out && np > 0) PDC_HIP(hipMemcpyAsync(j.out + pb, p + g.out, np * 8, hipMemcpyDeviceToHost, st));
+    if (k > 0) {
+        if (j.count) PDC_HIP(hipMemcpyAsync(j.count + c0, d_count, B * 8, hipMemcpyDeviceToHost, st));
+        if (j.idx) PDC_HIP(hipMemcpyAsync(j.idx + c0 * k, d_idx, nk * 8, hipMemcpyDeviceToHost, st));
+        if (j.height) PDC_HIP(hipMemcpyAsync(j.height + c0 * k, d_h, nk * 8, hipMemcpyDeviceToHost, st));
+        if (j.prom) PDC_HIP(hipMemcpyAsync(j.prom + c0 * k, d_p, nk * 8, hipMemcpyDeviceToHost, st));
+        if (j.lo) PDC_HIP(hipMemcpyAsync(j.lo + c0 * k, d_lo, nk * 8, hipMemcpyDeviceToHost, st));
+        if (j.hi) PDC_HIP(hipMemcpyAsync(j.hi + c0 * k, d_hi, nk * 8, hipMemcpyDeviceToHost, st));
+    }
+    PDC_HIP(hipStreamSynchronize(st));
+    if (k > 0 && j.lo) {
+        // the pad's one artefact: a sign flip of the pair (P_b - 1, P_b) is no crossing of the row itself
+        for (int64_t b = 0; b < B; ++b) {
+            const int64_t npb = np_of(j, c0 + b);
+            for (int r = 0; r < k; ++r)
+                if (j.lo[(c0 + b) * k + r] >= npb - 1) j.lo[(c0 + b) * k + r] = -1;
+        }
+    }
+    if (k > 0 && j.height && is_dip(j.kind))   // the table ranked -stat: heights back to the statistic's own values
+        for (int64_t i = c0 * k; i < c1 * k; ++i) j.height[i] = -j.height[i];
+    return PDC_OK;
+}
+
+int phase_host(const char *what, const PhaseJob &j, int64_t n_curves, const int *devices, int n_devices) {
+    PDC_REQUIRE(devices && n_devices >= 1 && n_devices <= 64, "%s: 1 .. 64 device slots (got %d)", what, n_devices);
+    PDC_REQUIRE(j.offsets[n_curves] == 0 || (j.t && j.x), "%s: t and x must not be NULL", what);
+    if (j.kind == 2)   // the magnitude bins index the cell histogram: reject what is not one of 0 .. n_mag-1
+        for (int64_t b = 0; b < n_curves; ++b)
+            for (int64_t i = j.offsets[b]; i < j.offsets[b + 1]; ++i)
+                PDC_REQUIRE(j.x[i] >= 0.0 && j.x[i] < (double)j.nc,
+                            "%s: curve %lld: mag_bin[%lld] = %g is not a bin index in 0 .. %d", what, (long long)b,
+                            (long long)(i - j.offsets[b]), j.x[i], j.nc - 1);
+    for (int i = 0; i < n_devices; ++i) PDC_TRY(use_device(devices[i]));
+    std::lock_guard<std::mutex> lk(g_phase_mutex);
+    if (g_phase_devices != std::vector<int>(devices, devices + n_devices)) {
+        PDC_TRY(free_slots());
+        g_phase_slots.resize((size_t)n_devices);
+        for (int i = 0; i < n_devices; ++i) g_phase_slots[(size_t)i].device = devices[i];
+        g_phase_devices.assign(devices, devices + n_devices);
+    }
+    // contiguous shares balanced by sum n_b P_b (+ n_b + P_b: the per-sample and per-period work)
+    std::vector<double> pre((size_t)n_curves + 1, 0.0);
+    for (int64_t b = 0; b < n_curves; ++b) {
+        const double nb = (double)(j.offsets[b + 1] - j.offsets[b]), pb = (double)np_of(j, b);
+        pre[(size_t)b + 1] = pre[(size_t)b] + nb * pb + nb + pb;
+    }
+    std::vector<int64_t> share((size_t)n_devices + 1, n_curves);
+    share[0] = 0;
+    for (int i = 1; i < n_devices; ++i)
+        share[(size_t)i] = std::lower_bound(pre.begin(), pre.end(), pre.back() * i / n_devices) - pre.begin();
+    // each slot's groups: the largest group shrinks by powers of two (WorkScale) until it fits the slot's budget,
+    // PDC_WORK_BUDGET_GB and its share of what the device has free (plus what the slot already holds)
+    std::vector<std::vector<int64_t>> cuts((size_t)n_devices);
+    for (int i = 0; i < n_devices; ++i) {
+        RSlot &s = g_phase_slots[(size_t)i];
+        PDC_TRY(use_device(s.device));
+        if (!s.stream) PDC_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+        const int64_t c0 = share[(size_t)i], c1 = share[(size_t)i + 1];
+        if (c1 <= c0) continue;
+        int same = 0;
+        int64_t held = 0;
+        for (const RSlot &o : g_phase_slots)
+            if (o.device == s.device) {
+                ++same;
+                held += o.buf.cap;
+            }
+        int64_t budget = work_budget();
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            const int64_t avail = (int64_t)((double)((int64_t)free_b + held) * 0.9 / same);
+            if (avail > 0 && (budget == 0 || avail < budget)) budget = avail;
+        } else {
+            (void)hipGetLastError();
+        }
+        int64_t p_max = 0;
+        for (int64_t b = c0; b < c1 && j.k > 0; ++b) p_max = std::max(p_max, np_of(j, b));
+        const int64_t whole = group_bytes(j, c0, c1, p_max).total;
+        WorkScale ws(budget, [&] {
+            int64_t largest;
+            (void)make_groups(j, c0, c1, (int64_t)((double)whole * work_scale()), &largest);
+            return largest;
+        });
+        PDC_REQUIRE_FITS(ws, what);
+        int64_t largest;
+        cuts[(size_t)i] = make_groups(j, c0, c1, (int64_t)((double)whole * work_scale()), &largest);
+    }
+    g_phase_groups = 0;
+    for (const std::vector<int64_t> &cut : cuts) g_phase_groups += cut.empty() ? 0 : (int64_t)cut.size() - 1;
+    std::vector<int> rc((size_t)n_devices, PDC_OK);
+    std::vector<std::string> why((size_t)n_devices);
+    auto run_slot = [&](int i) {
+        RSlot &s = g_phase_slots[(size_t)i];
+        const std::vector<int64_t> &cut = cuts[(size_t)i];
+        int r = use_device(s.device);
+        for (size_t q = 0; r == PDC_OK && q + 1 < cut.size(); ++q) r = run_group(s, j, cut[q], cut[q + 1]);
+        if (r != PDC_OK) {
+            rc[(size_t)i] = r;
+            why[(size_t)i] = pdc_last_error();
+            (void)hipStreamSynchronize(s.stream);
+        }
+    };
+    if (n_devices == 1) {
+        run_slot(0);
+    } else {
+        std::vector<std::thread> th;
+        for (int i = 0; i < n_devices; ++i) th.emplace_back(run_slot, i);
+        for (std::thread &x : th) x.join();
+    }
+    for (int i = 0; i < n_devices; ++i)
+        if (rc[(size_t)i] != PDC_OK) {
+            set_error("%s", why[(size_t)i].c_str());
+            return rc[(size_t)i];
+        }
+    return PDC_OK;
+}
+
+PhaseJob make_job(int kind, const double *t, const double *x, const int64_t *offsets, const double *start,
+                  const double *step, const double *stop, const int64_t *p_offsets, const double *sigma,
+                  const double *significant, int nb, int nc) {
+    PhaseJob j = {};
+    j.kind = kind;
+    j.nb = nb;
+    j.nc = kind == 1 ? 1 : nc;
+    j.t = t;
+    j.x = x;
+    j.offsets = offsets;
+    j.poff = p_offsets;
+    j.start = start;
+    j.step = step;
+    j.stop = stop;
+    j.sigma = kind == 0 ? sigma : nullptr;
+    j.signif = significant;
+    return j;
+}
+
+}  // namespace
+
+// Frees the per-slot buffers and streams of the ragged phase-scan host entries (pdc_release()).
+int pdc::release_phase_ragged() {
+    std::lock_guard<std::mutex> lk(g_phase_mutex);
+    return free_slots();
+}
+
+extern "C" {
+
+int pdc_test_phase_ragged_groups(int64_t *groups) {
+    PDC_REQUIRE(groups, "pdc_test_phase_ragged_groups: NULL argument");
+    std::lock_guard<std::mutex> lk(g_phase_mutex);
+    *groups = g_phase_groups;
+    return PDC_OK;
+}
+
+int64_t pdc_phase_ragged_work_bytes(int64_t n_curves, int64_t p_total, int64_t p_max, int k) {
+    if (n_curves < 1 || p_total < 0 || p_max < 0 || k < 0) return -1;
+    return phase_layout(n_curves, p_total, p_max, k).total;
+}
+
+int pdc_phase_scan_ragged_dev(int kind, int device, void *stream, const double *d_t, const double *d_x,
+                              const int64_t *offsets, int64_t n_curves, const double *start, const double *step,
+                              const double *stop, const int64_t *p_offsets, const double *sigma,
+                              const double *significant, int nb, int nc, double *d_out, double *d_pitched, int64_t pitch,
+                              void *work, int64_t work_bytes) {
+    PDC_TRY(validate("phase_ragged_dev", kind, offsets, n_curves, start, step, stop, p_offsets, sigma, significant, nb, nc));
+    PDC_REQUIRE(d_out || d_pitched, "phase_ragged_dev: no output requested");
+    if (d_pitched)
+        for (int64_t b = 0; b < n_curves; ++b)
+            PDC_REQUIRE(p_offsets[b + 1] - p_offsets[b] <= pitch, "phase_ragged_dev: curve %lld has more periods than the pitch",
+                        (long long)b);
+    std::vector<int64_t> meta;
+    return phase_ragged_dev(kind, device, (hipStream_t)stream, d_t, d_x, offsets, n_curves, start, step, stop, p_offsets,
+                            kind == 0 ? sigma : nullptr, significant, nb, nc, d_out, d_pitched, pitch, work, work_bytes,
+                            meta, true);
+}
+
+int pdc_phase_scan_ragged(int kind, const double *t, const double *x, const int64_t *offsets, int64_t n_curves,
+                          const double *start, const double *step, const double *stop, const int64_t *p_offsets,
+                          const double *sigma, const double *significant, int nb, int nc, double *out,
+                          const int *devices, int n_devices) {
+    PDC_TRY(validate("phase_ragged", kind, offsets, n_curves, start, step, stop, p_offsets, sigma, significant, nb, nc));
+    PDC_REQUIRE(out, "phase_ragged: no output requested");
+    PhaseJob j = make_job(kind, t, x, offsets, start, step, stop, p_offsets, sigma, significant, nb, nc);
+    j.out = out;
+    return phase_host(kind_name(kind), j, n_curves, devices, n_devices);
+}
+
+int pdc_phase_ragged_peaks(int kind, const double *t, const double *x, const int64_t *offsets, int64_t n_curves,
+                           const double *start, const double *step, const double *stop, const int64_t *p_offsets,
+                           const double *sigma, const double *significant, int nb, int nc, int k, int by_prominence,
+                           int64_t *count_out, int64_t *idx_out, double *height_out, double *prominence_out,
+                           int64_t *half_lo_out, int64_t *half_hi_out, double *out, const int *devices, int n_devices) {
+    PDC_TRY(validate("phase_ragged_peaks", kind, offsets, n_curves, start, step, stop, p_offsets, sigma, significant, nb,
+                     nc));
+    PDC_REQUIRE(k >= 1 && k <= 1024, "phase_ragged_peaks: k must be 1..1024 (got %d)", k);
+    PDC_REQUIRE(count_out || idx_out || height_out || prominence_out || half_lo_out || half_hi_out || out,
+                "phase_ragged_peaks: no output requested");
+    PhaseJob j = make_job(kind, t, x, offsets, start, step, stop, p_offsets, sigma, significant, nb, nc);
+    j.k = k;
+    j.by_prominence = by_prominence ? 1 : 0;
+    j.out = out;
+    j.count = count_out;
+    j.idx = idx_out;
+    j.height = height_out;
+    j.prom = prominence_out;
+    j.lo = half_lo_out;
+    j.hi = half_hi_out;
+    return phase_host(kind_name(kind), j, n_curves, devices, n_devices);
+}
+
+}  // extern "C"

@@ -21,7 +21,7 @@ from .core import FSeries, TSeries
 
 MAX_CORES = cpu_count()
 
-__all__ = ["StringLength", "PDM", "AOV", "ConditionalEntropy", "GregoryLoredo", "SuperSmoother"]
+__all__ = ["StringLength", "PDM", "AOV", "ConditionalEntropy", "GregoryLoredo", "SuperSmoother", "PhaseBatch"]
 
 
 # ---- host-side grid / scaling rules (O(N) or O(n_periods) numpy, as upstream) -----------------------
@@ -46,14 +46,184 @@ def _string_periods(baseline, dphi, count):
     return 1 / np.linspace(count * step, step, count)
 
 
-def _pdm_periods(signal, p_min, p_max, count, oversample):
-    """Trial periods equally spaced in PERIOD (``phase.py:167-180``) and the limits used."""
+def _pdm_limits(signal, p_min, p_max, count, oversample):
+    """The limits and the number of trial periods of ``_pdm_periods``."""
     span = signal.baseline
     shortest = 2 * signal.median_dt if p_min is None else p_min
     longest = oversample * span if p_max is None else p_max
     if count is None:
         count = int((1 / shortest - 1 / longest) * oversample * span + 1)
+    return shortest, longest, count
+
+
+def _pdm_periods(signal, p_min, p_max, count, oversample):
+    """Trial periods equally spaced in PERIOD (``phase.py:167-180``) and the limits used."""
+    shortest, longest, count = _pdm_limits(signal, p_min, p_max, count, oversample)
     return np.linspace(shortest, longest, count), shortest, longest
+
+
+def _linspace_steps(start, stop, count):
+    """Per row, the ``step`` with which ``np.linspace(start, stop, count)`` fills its values: ``j * step + start``
+    (two roundings), exactly ``stop`` at the last of two or more.  One value: ``0 * (stop - start) + start``, so the
+    step is ``stop - start``.  (numpy divides the other way when the step underflows to zero; such a grid is
+    refused.)"""
+    start, stop = np.asarray(start, dtype=np.float64), np.asarray(stop, dtype=np.float64)
+    count = np.asarray(count, dtype=np.int64)
+    delta = stop - start
+    with np.errstate(invalid="ignore", divide="ignore"):
+        step = np.where(count > 1, delta / np.maximum(count - 1, 1).astype(np.float64), delta)
+    bad = (count > 1) & (step == 0) & (delta != 0)
+    if bad.any():
+        raise ValueError(f"curve {int(np.flatnonzero(bad)[0])}: the period range is too narrow for its grid")
+    return step
+
+
+def _linspace_at(start, step, stop, count, j):
+    """``np.linspace(start, stop, count)[j]`` from ``_linspace_steps`` (all arguments broadcast)."""
+    j = np.asarray(j, dtype=np.int64)
+    fill = j.astype(np.float64) * step + start
+    return np.where((count > 1) & (j == count - 1), stop, fill)
+
+
+def _check_fseries_order(start, step, stop, count):
+    """The device writes the peak table's rows in FSeries order, which for a linspace grid of periods is the period
+    index reversed (ascending grid: 1/p strictly decreasing) or kept (descending or constant grid: 1/p
+    non-decreasing).  That holds when the periods share one sign and, on an ascending grid, no two neighbours round
+    to the same reciprocal; any other grid (through zero, non-finite limits) is refused, naming the curve."""
+    one_sign = ((start > 0) & (stop > 0)) | ((start < 0) & (stop < 0))
+    ok = (count <= 1) | (start == stop) | (one_sign & np.isfinite(start) & np.isfinite(stop))
+    if not ok.all():
+        b = int(np.flatnonzero(~ok)[0])
+        raise ValueError(f"curve {b}: a peak table needs a period grid of one sign (p_min = {start[b]!r}, "
+                         f"p_max = {stop[b]!r})")
+    # ascending: ties of 1/p need neighbours within a few ulp of each other; check the (rare) fine grids exactly
+    fine = np.flatnonzero((stop > start) & (count > 1) & (np.abs(step) < 1e-13 * np.maximum(abs(start), abs(stop))))
+    for b in fine:
+        p = _linspace_at(start[b], step[b], stop[b], count[b], np.arange(count[b]))
+        if not np.all(1 / p[1:] < 1 / p[:-1]):
+            raise ValueError(f"curve {int(b)}: neighbouring trial periods share a frequency; no peak table")
+
+
+class PhaseBatch(object):
+    """What ``PDM.batch``, ``AOV.batch`` and ``ConditionalEntropy.batch`` return: ``periods`` (one trial grid per
+    curve, ``_pdm_periods``), ``periodograms`` (one ``FSeries(1 / periods, statistic)`` per curve, as the single
+    call returns it, or None) and ``peaks`` (a :class:`~periodicity_amd.spectral.PeakTable`, or None)."""
+
+    def __init__(self, start, step, stop, p_offsets, values, peaks):
+        self._start, self._step, self._stop, self._p_offsets = start, step, stop, p_offsets
+        self._periods = None
+        self.peaks = peaks
+        self.periodograms = None
+        if values is not None:
+            self.periodograms = [FSeries(1 / p, values[p_offsets[b]:p_offsets[b + 1]])
+                                 for b, p in enumerate(self.periods)]
+
+    @property
+    def periods(self):
+        if self._periods is None:
+            count = np.diff(self._p_offsets)
+            rows = np.repeat(np.arange(count.size), count)
+            j = np.arange(self._p_offsets[-1], dtype=np.int64) - np.repeat(self._p_offsets[:-1], count)
+            flat = _linspace_at(self._start[rows], self._step[rows], self._stop[rows], count[rows], j)
+            self._periods = np.split(flat, self._p_offsets[1:-1])
+        return self._periods
+
+    def _frequency_at(self, rows, bins):
+        """Frequency of bin ``bins`` of ``periodograms[rows]``: ascending frequency, so the period index reversed on
+        an ascending grid and kept on a descending one (``_check_fseries_order``)."""
+        count = np.diff(self._p_offsets)[rows]
+        start, stop = self._start[rows], self._stop[rows]
+        j = np.where(stop > start, count - 1 - bins, bins)
+        return 1 / _linspace_at(start, self._step[rows], stop, count, j)
+
+    def __len__(self):
+        return self._p_offsets.size - 1
+
+
+_KINDS = {"pdm": 0, "aov": 1, "ce": 2}
+_CELL_SAMPLES = 65280   # conditional entropy: a workgroup bins a whole curve in 16-bit cells
+
+
+def _phase_batch(scan, kind, signals, nb, nc, peaks, by_prominence, want_power, subharmonic=False):
+    """The batch of :class:`PDM` / :class:`AOV` / :class:`ConditionalEntropy` (``pdc_phase_scan_ragged``): every
+    curve on exactly the grid its own single call would scan, with that call's host-side inputs (``sigma``, the
+    magnitude bins, the sub-harmonic threshold) computed the same way, per curve, and uploaded."""
+    from .spectral import PeakTable
+    code = _KINDS[kind]
+    peaks = int(peaks)
+    if peaks < 0 or peaks > 1024:
+        raise ValueError("peaks must be 0 .. 1024")
+    if not want_power and peaks == 0:
+        raise ValueError("nothing requested: want_power=False needs peaks > 0")
+    signals = [_coerce(s) for s in signals]
+    if not signals:
+        raise ValueError(f"{type(scan).__name__}.batch needs at least one signal")
+    values = [np.asarray(s.values, dtype=float) for s in signals]
+    sizes = np.array([v.size for v in values], dtype=np.int64)
+    if code == 2 and sizes.max() > _CELL_SAMPLES:
+        b = int(np.argmax(sizes > _CELL_SAMPLES))
+        raise ValueError(f"curve {b} has {sizes[b]} samples: ConditionalEntropy.batch bins a whole curve in one "
+                         f"workgroup of 16-bit cells, at most {_CELL_SAMPLES} samples")
+    limits = [_pdm_limits(s, scan.p_min, scan.p_max, scan.n_periods, scan.oversample) for s in signals]
+    start = np.array([lim[0] for lim in limits], dtype=np.float64)
+    stop = np.array([lim[1] for lim in limits], dtype=np.float64)
+    count = np.array([lim[2] for lim in limits], dtype=np.int64)
+    if (count < 0).any():
+        b = int(np.argmax(count < 0))
+        raise ValueError(f"curve {b}: number of samples, {count[b]}, must be non-negative")
+    significant = None
+    if subharmonic:
+        if (count < 2).any():
+            b = int(np.argmax(count < 2))
+            raise ValueError(f"curve {b}: sub-harmonic averaging needs at least two trial periods (got {count[b]})")
+        significant = np.array([1.0 - 11.0 / s.size ** 0.8 for s in signals], dtype=np.float64)
+    step = _linspace_steps(start, stop, count)
+    if peaks:
+        _check_fseries_order(start, step, stop, count)
+    offsets = np.zeros(len(signals) + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum(sizes)
+    p_offsets = np.zeros(len(signals) + 1, dtype=np.int64)
+    p_offsets[1:] = np.cumsum(count)
+    t = np.concatenate([np.asarray(s.time, dtype=float) for s in signals])
+    x = np.concatenate(values)
+    sigma = None
+    if code == 0:
+        sigma = np.array([np.var(s.values, ddof=1) for s in signals], dtype=np.float64)
+    elif code == 2:
+        # ConditionalEntropy.__call__'s magnitude bins, for all curves at once (nanmin / nanmax are fmin / fmax)
+        low = np.repeat(np.fmin.reduceat(x, offsets[:-1]), sizes)
+        high = np.repeat(np.fmax.reduceat(x, offsets[:-1]), sizes)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            unit = (x - low) / (high - low)
+            x = np.minimum(np.floor(unit * nc), nc - 1).astype(float)
+            ok = (x >= 0) & (x < nc)
+        if not ok.all():
+            b = int(np.searchsorted(offsets, np.argmin(ok), side="right") - 1)
+            raise ValueError(f"curve {b}: magnitude bins must lie in 0 .. n_mag-1 (a constant curve, or NaN values)")
+    devices = scan.devices if scan.devices else None
+    out, table = _cabi.phase_scan_ragged(code, t, x, offsets, start, step, stop, p_offsets, nb, nc, sigma=sigma,
+                                         significant=significant, k=peaks, by_prominence=by_prominence,
+                                         want_power=want_power, device=scan.device, devices=devices)
+    res = PhaseBatch(start, step, stop, p_offsets, out, None)
+    if table is not None:
+        res.peaks = PeakTable(None, table, by_prominence, frequency_at=res._frequency_at)
+    return res
+
+
+_BATCH_DOC = """Periodograms of many light curves, each on the grid its own data give (``_pdm_periods`` per curve), in
+        one set of launches (``pdc_phase_scan_ragged`` / ``pdc_phase_ragged_peaks``): what a loop of ``{cls}(...)(s)``
+        followed by ``{find}()`` gives, without a launch per curve.  Returns a :class:`PhaseBatch`.
+
+        peaks: int, keyword-only
+            ``k > 0`` (<= 1024): also the ``k`` {what} of every periodogram, found on the device
+            (``PhaseBatch.peaks``; ``height`` holds the statistic itself).
+        by_prominence: bool, keyword-only
+            Rank them by prominence instead.
+        want_power: bool, keyword-only
+            ``False``: the periodograms stay on the device (``periodograms`` is None); needs ``peaks > 0``.
+
+        With ``devices=(...)`` the curves are dealt to those device slots in contiguous groups balanced by
+        ``sum n_b P_b``.  The object's own attributes (``periods``, ``periodogram`` ...) are left as they were."""
 
 
 def _average_with_double_period(thetas, periods, n_samples, shortest, longest):
@@ -177,6 +347,12 @@ class PDM(object):
         self.periodogram = FSeries(1 / self.periods, thetas)
         return self.periodogram
 
+    def batch(self, signals, *, peaks=0, by_prominence=False, want_power=True):
+        return _phase_batch(self, "pdm", signals, self.nb, self.nc, peaks, by_prominence, want_power,
+                            subharmonic=self.do_subharmonic)
+
+    batch.__doc__ = _BATCH_DOC.format(cls="PDM", find="find_dips", what="deepest (``find_dips``) minima")
+
 
 class AOV(object):
     """Analysis of Variance period search (Schwarzenberg-Czerny 1989) - one of the scans the
@@ -216,6 +392,11 @@ class AOV(object):
                                devices=self.devices)
         self.periodogram = FSeries(1 / self.periods, theta)
         return self.periodogram
+
+    def batch(self, signals, *, peaks=0, by_prominence=False, want_power=True):
+        return _phase_batch(self, "aov", signals, self.n_bins, 1, peaks, by_prominence, want_power)
+
+    batch.__doc__ = _BATCH_DOC.format(cls="AOV", find="find_peaks", what="highest (``find_peaks``) maxima")
 
 
 class SuperSmoother(object):
@@ -300,6 +481,12 @@ class ConditionalEntropy(object):
                                           device=self.device, devices=self.devices)
         self.periodogram = FSeries(1 / self.periods, entropy)
         return self.periodogram
+
+    def batch(self, signals, *, peaks=0, by_prominence=False, want_power=True):
+        return _phase_batch(self, "ce", signals, self.n_phase, self.n_mag, peaks, by_prominence, want_power)
+
+    batch.__doc__ = _BATCH_DOC.format(cls="ConditionalEntropy", find="find_dips",
+                                      what="deepest (``find_dips``) minima")
 
 
 class GregoryLoredo(object):

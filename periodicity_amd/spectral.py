@@ -265,12 +265,13 @@ LombScargle = GLS
 class PeakTable(object):
     """The ``k`` best peaks of every spectrum of a ``GLS.batch`` call, ``[B][k]`` arrays ranked descending (by
     height, or by prominence), padded with NaN (``index``: -1) past a curve's ``count`` of ``find_peaks`` maxima.
+    (``PDM.batch`` and ``ConditionalEntropy.batch`` fill it with the ``find_dips`` minima, deepest first.)
 
     ``period_lo[b, r]``, ``period_hi[b, r]`` are the pair ``periods_at_half_max(r + 1, use_prominence=by_prominence)``
     returns for curve ``b`` (``core.py:963-978``); each is NaN where that method finds no crossing on its side.
     """
 
-    def __init__(self, grids, out, by_prominence):
+    def __init__(self, grids, out, by_prominence, frequency_at=None):
         self.by_prominence = bool(by_prominence)
         self.count = out["count"]
         self.index = out["indices"]
@@ -280,11 +281,17 @@ class PeakTable(object):
         self.frequency = np.full((B, k), np.nan)
         self.period_lo = np.full((B, k), np.nan)
         self.period_hi = np.full((B, k), np.nan)
-        for b, g in enumerate(grids):
-            for name, idx in (("frequency", self.index[b]), ("period_lo", out["half_lo"][b]),
-                              ("period_hi", out["half_hi"][b])):
+        columns = (("frequency", self.index), ("period_lo", out["half_lo"]), ("period_hi", out["half_hi"]))
+        if frequency_at is None:
+            for b, g in enumerate(grids):
+                for name, idx in columns:
+                    ok = idx[b] >= 0
+                    getattr(self, name)[b, ok] = g[idx[b][ok]]
+        else:   # frequency_at(rows, bins): the grids without building them (the phase scans' batches)
+            rows = np.broadcast_to(np.arange(B)[:, None], (B, k))
+            for name, idx in columns:
                 ok = idx >= 0
-                getattr(self, name)[b, ok] = g[idx[ok]]
+                getattr(self, name)[ok] = frequency_at(rows[ok], idx[ok])
         with np.errstate(divide="ignore"):
             self.period = 1.0 / self.frequency
             self.period_lo = 1.0 / self.period_lo
