@@ -16,25 +16,20 @@
 //                            in a tile prefix table.  The running sums, the rotation tables and the
 //                            three-term recurrence are those of gls_scan_kernel (K = 8, one wave per
 //                            64-lane column, two columns); the epilogue (gls_epilogue.h) is fused.  Tiles
-//                            are dispatched costliest curve first (cost ~ n_b), so that the long curves
-//                            do not run alone at the end of the launch.  Optionally also writes a pitched
+//                            are dispatched costliest curve first (ragged_order, cost ~ n_b), so that the long
+//                            curves do not run alone at the end of the launch.  Optionally also writes a pitched
 //                            [B][pitch] copy of the spectra (the caller fills the pad with NaN) for the
 //                            peak table of peaks.hip.
 //   gls_ragged_peak_kernel   NaN-aware max / argmax per curve from the per-tile partials (the rule of
 //                            gls_peak_kernel: first maximum on ties, -1 / NaN for a row without a finite bin).
 //
-// Designed for survey curves (1e2 - 1e4 samples, grids of ~2.5 N bins): no sample parts, no balanced pieces
-// (one huge curve has its own path in gls.hip).
+// The host entries' device slots, groups, budget and peak table are the shared driver's (ragged.hip); this unit
+// sizes and runs one group.  Designed for survey curves (1e2 - 1e4 samples, grids of ~2.5 N bins): no sample parts,
+// no balanced pieces (one huge curve has its own path in gls.hip).
 #include "pdc_internal.h"
 #include "gls_epilogue.h"
 
-#include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <string>
-#include <thread>
 #include <vector>
 
 using namespace pdc;
@@ -358,13 +353,12 @@ __global__ __launch_bounds__(64) void gls_ragged_peak_kernel(const double *blk_m
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-int64_t up256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 int64_t tiles_of(int64_t nf) { return (nf + kRTile - 1) / kRTile; }
 
 // Workspace of one launch over B curves: records (+ two spare ones for the scan's read-ahead), per-curve scalars,
-// the metadata tables, the tile partials; with k > 0 also the NaN-padded [B][nf_max] copy and the [B][k] peak table.
+// the metadata tables, the tile partials; with k > 0 also the peak-table tail (ragged_table_bytes).
 struct RaggedLayout {
-    int64_t rec, scal, meta, blk_max, blk_arg, pitched, table, total;
+    int64_t rec, scal, meta, blk_max, blk_arg, pitched, total;
 };
 constexpr int kMetaArrays = 7;   // offsets | foff | ctile | otile | order (int64) | f0 | delta (double), B + 1 each
 
@@ -377,9 +371,7 @@ RaggedLayout ragged_layout(int64_t n_total, int64_t n_curves, int64_t nf_total, 
     w.blk_max = w.meta + up256(kMetaArrays * (n_curves + 1) * 8);
     w.blk_arg = w.blk_max + up256(tiles_max * 8);
     w.pitched = w.blk_arg + up256(tiles_max * 8);
-    w.table = w.pitched + (k > 0 ? up256(n_curves * nf_max * 8) : 0);
-    // count | idx | half_lo | half_hi | height | prominence
-    w.total = w.table + (k > 0 ? up256((n_curves + 5 * n_curves * (int64_t)k) * 8) : 0);
+    w.total = w.pitched + ragged_table_bytes(n_curves, nf_max, k);
     return w;
 }
 
@@ -387,22 +379,14 @@ RaggedLayout ragged_layout(int64_t n_total, int64_t n_curves, int64_t nf_total, 
 int validate(const char *what, const int64_t *offsets, int64_t n_curves, const double *f0, const double *delta,
              const int64_t *f_offsets) {
     PDC_REQUIRE(offsets && f0 && delta && f_offsets, "%s: NULL argument", what);
-    PDC_REQUIRE(n_curves >= 1 && n_curves < ((int64_t)1 << 31), "%s: n_curves must be 1 .. 2^31 - 1 (got %lld)", what,
-                (long long)n_curves);
-    PDC_REQUIRE(offsets[0] == 0 && f_offsets[0] == 0, "%s: offsets[0] and f_offsets[0] must be 0", what);
-    int64_t tiles = 0;
-    for (int64_t b = 0; b < n_curves; ++b) {
-        PDC_REQUIRE(offsets[b + 1] >= offsets[b], "%s: offsets must be non-decreasing (curve %lld)", what, (long long)b);
-        PDC_REQUIRE(f_offsets[b + 1] >= f_offsets[b], "%s: f_offsets must be non-decreasing (curve %lld)", what,
-                    (long long)b);
+    auto grid = [&](int64_t b) {
         PDC_REQUIRE(std::isfinite(f0[b]) && std::isfinite(delta[b]) && delta[b] > 0.0,
                     "%s: curve %lld: f0 and delta must be finite and delta > 0 (f0 = %g, delta = %g)", what, (long long)b,
                     f0[b], delta[b]);
-        tiles += tiles_of(f_offsets[b + 1] - f_offsets[b]);
-    }
-    PDC_REQUIRE(tiles < ((int64_t)1 << 31), "%s: %lld tiles of %lld bins: the grid is too large for one launch", what,
-                (long long)tiles, (long long)kRTile);
-    return PDC_OK;
+        return PDC_OK;
+    };
+    return ragged_validate(what, offsets, f_offsets, "f_offsets", n_curves, kRTile,
+                           "bins: the grid is too large for one launch", grid);
 }
 
 // Every workgroup-visible launch of one group of curves.  Metadata come from the host (offsets, f_offsets rebased
@@ -418,34 +402,22 @@ int ragged_dev(int device, hipStream_t st, const double *d_t, const double *d_y,
     PDC_REQUIRE(n_total == 0 || (d_t && d_y), "gls_ragged: t and y must not be NULL");
     PDC_TRY(use_device(device));
     char *base = static_cast<char *>(work);
-    // metadata: one upload; dispatch order = curves with >= 1 tile, most samples first (ties: curve order)
+    // metadata: one upload; dispatch order = ragged_order (costliest curve first)
     const int64_t B1 = n_curves + 1;
     meta.assign((size_t)(kMetaArrays * B1), 0);
     int64_t *m_off = meta.data(), *m_foff = m_off + B1, *m_ctile = m_foff + B1, *m_otile = m_ctile + B1,
             *m_order = m_otile + B1;
     double *m_f0 = reinterpret_cast<double *>(m_order + B1), *m_delta = m_f0 + B1;
-    std::vector<int64_t> ord;
-    ord.reserve((size_t)n_curves);
     for (int64_t b = 0; b < n_curves; ++b) {
         m_off[b] = offsets[b];
         m_foff[b] = foff[b];
         m_f0[b] = f0[b];
         m_delta[b] = delta[b];
         m_ctile[b + 1] = m_ctile[b] + tiles_of(foff[b + 1] - foff[b]);
-        if (foff[b + 1] > foff[b]) ord.push_back(b);
     }
     m_off[n_curves] = n_total;
     m_foff[n_curves] = nf_total;
-    static const bool costly_first = [] { const char *e = getenv("PDC_RAGGED_ORDER"); return !(e && e[0] == '0'); }();
-    if (costly_first)
-        std::stable_sort(ord.begin(), ord.end(), [&](int64_t x, int64_t y) {
-            return offsets[x + 1] - offsets[x] > offsets[y + 1] - offsets[y];
-        });
-    const int64_t m = (int64_t)ord.size();
-    for (int64_t p = 0; p < m; ++p) {
-        m_order[p] = ord[(size_t)p];
-        m_otile[p + 1] = m_otile[p] + tiles_of(foff[ord[(size_t)p] + 1] - foff[ord[(size_t)p]]);
-    }
+    const int64_t m = ragged_order(offsets, foff, n_curves, kRTile, m_order, m_otile);
     const int64_t tiles = m_ctile[n_curves];
     int64_t *d_meta = reinterpret_cast<int64_t *>(base + w.meta);
     PDC_HIP(hipMemcpyAsync(d_meta, meta.data(), (size_t)(kMetaArrays * B1 * 8), hipMemcpyHostToDevice, st));
@@ -498,255 +470,72 @@ int ragged_dev(int device, hipStream_t st, const double *d_t, const double *d_y,
     return PDC_OK;
 }
 
-// ---- host entries: curves dealt to device slots, each slot's share processed in groups that fit its budget ----
-struct RBuf {
-    void *p = nullptr;
-    int64_t cap = 0;
-};
+// ---- host entries: ragged_run (ragged.hip) deals the curves to device slots and runs each slot's groups ----------
+RaggedSlots g_slots;
 
-struct RSlot {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    RBuf buf;               // inputs | power | amax | argmax | workspace of one group
-    std::vector<int64_t> meta;
-};
-
-std::mutex g_ragged_mutex;
-std::vector<int> g_ragged_devices;
-std::vector<RSlot> g_ragged_slots;
-
-int ensure_buf(RBuf &b, int64_t bytes) {   // (on the current device) grow-only
-    if (bytes < 256) bytes = 256;
-    if (b.cap >= bytes) return PDC_OK;
-    if (b.p) PDC_HIP(hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-    PDC_TRY(device_alloc(&b.p, bytes + bytes / 8));
-    b.cap = bytes + bytes / 8;
-    return PDC_OK;
-}
-
-int free_slots() {
-    for (RSlot &s : g_ragged_slots) {
-        PDC_HIP(hipSetDevice(s.device));
-        if (s.stream) PDC_HIP(hipStreamDestroy(s.stream));
-        if (s.buf.p) PDC_HIP(hipFree(s.buf.p));
-    }
-    g_ragged_slots.clear();
-    g_ragged_devices.clear();
-    return PDC_OK;
-}
-
-// What one host call computes and where its results go (caller's host arrays, any may be NULL).
-struct RaggedJob {
+// What one host call computes and where its results go (caller's host arrays, any may be NULL); rows = f_offsets.
+struct RaggedJob : RaggedBatch {
     const double *t, *y, *dy;
-    const int64_t *offsets, *foff;
     const double *f0, *delta;
-    int fit_mean, psd, k, by_prominence;
+    int fit_mean, psd;
     double *power, *amax;
     int64_t *argmax;
-    int64_t *count, *idx, *lo, *hi;
-    double *height, *prom;
-};
 
-// Bytes of the slot buffer for the group [c0, c1) whose longest grid has nf_max bins.
-struct GroupBytes {
-    int64_t in_t, in_y, in_dy, pow, amax, arg, work, total;
-};
-GroupBytes group_bytes(const RaggedJob &j, int64_t c0, int64_t c1, int64_t nf_max) {
-    const int64_t n = j.offsets[c1] - j.offsets[c0], nf = j.foff[c1] - j.foff[c0], B = c1 - c0;
-    GroupBytes g;
-    g.in_t = 0;
-    g.in_y = up256(n * 8);
-    g.in_dy = g.in_y + up256(n * 8);
-    g.pow = g.in_dy + (j.dy ? up256(n * 8) : 0);
-    g.amax = g.pow + (j.power ? up256(nf * 8) : 0);
-    g.arg = g.amax + (j.amax ? up256(B * 8) : 0);
-    g.work = g.arg + (j.argmax ? up256(B * 8) : 0);
-    g.total = g.work + ragged_layout(n, B, nf, nf_max, j.k).total;
-    return g;
-}
-int64_t nf_of(const RaggedJob &j, int64_t b) { return j.foff[b + 1] - j.foff[b]; }
+    // The slot buffer of the group [c0, c1) whose longest grid has nf_max bins: inputs | power | amax | argmax | workspace.
+    struct Bytes {
+        int64_t in_t, in_y, in_dy, pow, amax, arg, work, total;
+    };
+    Bytes bytes(int64_t c0, int64_t c1, int64_t nf_max) const {
+        const int64_t n = offsets[c1] - offsets[c0], nf = rows[c1] - rows[c0], B = c1 - c0;
+        Bytes g;
+        g.in_t = 0;
+        g.in_y = up256(n * 8);
+        g.in_dy = g.in_y + up256(n * 8);
+        g.pow = g.in_dy + (dy ? up256(n * 8) : 0);
+        g.amax = g.pow + (power ? up256(nf * 8) : 0);
+        g.arg = g.amax + (amax ? up256(B * 8) : 0);
+        g.work = g.arg + (argmax ? up256(B * 8) : 0);
+        g.total = g.work + ragged_layout(n, B, nf, nf_max, k).total;
+        return g;
+    }
+    int64_t group_bytes(int64_t c0, int64_t c1, int64_t nf_max) const override { return bytes(c0, c1, nf_max).total; }
 
-// Contiguous groups of [c0, c1) of at most `cap` bytes each (a curve that alone exceeds it is a group of its own);
-// *largest = the bytes of the largest group.
-std::vector<int64_t> make_groups(const RaggedJob &j, int64_t c0, int64_t c1, int64_t cap, int64_t *largest) {
-    std::vector<int64_t> cut{c0};
-    *largest = 0;
-    int64_t g0 = c0, nf_max = 0;
-    for (int64_t b = c0; b < c1; ++b) {
-        const int64_t grown = std::max(nf_max, nf_of(j, b));
-        if (b > g0 && group_bytes(j, g0, b + 1, grown).total > cap) {
-            *largest = std::max(*largest, group_bytes(j, g0, b, nf_max).total);
-            cut.push_back(b);
-            g0 = b;
-            nf_max = nf_of(j, b);
-        } else {
-            nf_max = grown;
+    int run_group(RaggedSlot &s, int64_t c0, int64_t c1, int64_t nf_max, double *pitched) const override {
+        const int64_t B = c1 - c0, s0 = offsets[c0], n = offsets[c1] - s0, fb = rows[c0], nf = rows[c1] - fb;
+        const Bytes g = bytes(c0, c1, nf_max);
+        char *p = static_cast<char *>(s.buf);
+        hipStream_t st = s.stream;
+        if (n > 0) {
+            PDC_HIP(hipMemcpyAsync(p + g.in_t, t + s0, n * 8, hipMemcpyHostToDevice, st));
+            PDC_HIP(hipMemcpyAsync(p + g.in_y, y + s0, n * 8, hipMemcpyHostToDevice, st));
+            if (dy) PDC_HIP(hipMemcpyAsync(p + g.in_dy, dy + s0, n * 8, hipMemcpyHostToDevice, st));
         }
-    }
-    if (c1 > g0) *largest = std::max(*largest, group_bytes(j, g0, c1, nf_max).total);
-    cut.push_back(c1);
-    return cut;
-}
-
-// One group on one slot, start to finish (the slot's stream is synchronised before return).
-int run_group(RSlot &s, const RaggedJob &j, int64_t c0, int64_t c1) {
-    const int64_t B = c1 - c0, s0 = j.offsets[c0], n = j.offsets[c1] - s0, fb = j.foff[c0], nf = j.foff[c1] - fb;
-    int64_t nf_max = 0;
-    for (int64_t b = c0; b < c1; ++b) nf_max = std::max(nf_max, nf_of(j, b));
-    if (j.k == 0) nf_max = 0;
-    const GroupBytes g = group_bytes(j, c0, c1, nf_max);
-    PDC_TRY(ensure_buf(s.buf, g.total));
-    char *p = static_cast<char *>(s.buf.p);
-    hipStream_t st = s.stream;
-    if (n > 0) {
-        PDC_HIP(hipMemcpyAsync(p + g.in_t, j.t + s0, n * 8, hipMemcpyHostToDevice, st));
-        PDC_HIP(hipMemcpyAsync(p + g.in_y, j.y + s0, n * 8, hipMemcpyHostToDevice, st));
-        if (j.dy) PDC_HIP(hipMemcpyAsync(p + g.in_dy, j.dy + s0, n * 8, hipMemcpyHostToDevice, st));
-    }
-    std::vector<int64_t> off((size_t)B + 1), foff((size_t)B + 1);
-    for (int64_t b = 0; b <= B; ++b) {
-        off[(size_t)b] = j.offsets[c0 + b] - s0;
-        foff[(size_t)b] = j.foff[c0 + b] - fb;
-    }
-    const int k = j.k;
-    const RaggedLayout w = ragged_layout(n, B, nf, nf_max, k);
-    char *work = p + g.work;
-    double *d_pitched = nullptr;
-    if (k > 0) {
-        d_pitched = reinterpret_cast<double *>(work + w.pitched);
-        // all-ones bytes: a NaN in every bin, the pad [nf_b, nf_max) stays so (see the header for why this keeps
-        // scipy's answers)
-        PDC_HIP(hipMemsetAsync(d_pitched, 0xff, (size_t)(B * nf_max * 8), st));
-    }
-    PDC_TRY(ragged_dev(s.device, st, (const double *)(p + g.in_t), (const double *)(p + g.in_y),
-                       j.dy ? (const double *)(p + g.in_dy) : nullptr, off.data(), B, j.f0 + c0, j.delta + c0, foff.data(),
-                       j.fit_mean, j.psd, j.power ? (double *)(p + g.pow) : nullptr, d_pitched, nf_max,
-                       j.amax ? (double *)(p + g.amax) : nullptr, j.argmax ? (int64_t *)(p + g.arg) : nullptr, work,
-                       w.total, s.meta, false));
-    const int64_t nk = B * (int64_t)k;
-    int64_t *d_count = reinterpret_cast<int64_t *>(work + w.table), *d_idx = d_count + B, *d_lo = d_idx + nk,
-            *d_hi = d_lo + nk;
-    double *d_h = reinterpret_cast<double *>(d_hi + nk), *d_p = d_h + nk;
-    if (k > 0)
-        PDC_TRY(pdc_peaks_topk_dev(s.device, st, d_pitched, B, nf_max, k, j.by_prominence, d_count, d_idx, d_h, d_p,
-                                   d_lo, d_hi));
-    if (j.power && nf > 0) PDC_HIP(hipMemcpyAsync(j.power + fb, p + g.pow, nf * 8, hipMemcpyDeviceToHost, st));
-    if (j.amax) PDC_HIP(hipMemcpyAsync(j.amax + c0, p + g.amax, B * 8, hipMemcpyDeviceToHost, st));
-    if (j.argmax) PDC_HIP(hipMemcpyAsync(j.argmax + c0, p + g.arg, B * 8, hipMemcpyDeviceToHost, st));
-    if (k > 0) {
-        if (j.count) PDC_HIP(hipMemcpyAsync(j.count + c0, d_count, B * 8, hipMemcpyDeviceToHost, st));
-        if (j.idx) PDC_HIP(hipMemcpyAsync(j.idx + c0 * k, d_idx, nk * 8, hipMemcpyDeviceToHost, st));
-        if (j.height) PDC_HIP(hipMemcpyAsync(j.height + c0 * k, d_h, nk * 8, hipMemcpyDeviceToHost, st));
-        if (j.prom) PDC_HIP(hipMemcpyAsync(j.prom + c0 * k, d_p, nk * 8, hipMemcpyDeviceToHost, st));
-        if (j.lo) PDC_HIP(hipMemcpyAsync(j.lo + c0 * k, d_lo, nk * 8, hipMemcpyDeviceToHost, st));
-        if (j.hi) PDC_HIP(hipMemcpyAsync(j.hi + c0 * k, d_hi, nk * 8, hipMemcpyDeviceToHost, st));
-    }
-    PDC_HIP(hipStreamSynchronize(st));
-    if (k > 0 && j.lo) {
-        // the pad's one artefact: a sign flip of the pair (nf_b - 1, nf_b) is no crossing of the row itself
-        for (int64_t b = 0; b < B; ++b) {
-            const int64_t nfb = j.foff[c0 + b + 1] - j.foff[c0 + b];
-            for (int r = 0; r < k; ++r)
-                if (j.lo[(c0 + b) * k + r] >= nfb - 1) j.lo[(c0 + b) * k + r] = -1;
+        std::vector<int64_t> off((size_t)B + 1), foff((size_t)B + 1);
+        for (int64_t b = 0; b <= B; ++b) {
+            off[(size_t)b] = offsets[c0 + b] - s0;
+            foff[(size_t)b] = rows[c0 + b] - fb;
         }
+        PDC_TRY(ragged_dev(s.device, st, (const double *)(p + g.in_t), (const double *)(p + g.in_y),
+                           dy ? (const double *)(p + g.in_dy) : nullptr, off.data(), B, f0 + c0, delta + c0, foff.data(),
+                           fit_mean, psd, power ? (double *)(p + g.pow) : nullptr, pitched, nf_max,
+                           amax ? (double *)(p + g.amax) : nullptr, argmax ? (int64_t *)(p + g.arg) : nullptr,
+                           p + g.work, g.total - g.work, s.meta, false));
+        if (power && nf > 0) PDC_HIP(hipMemcpyAsync(power + fb, p + g.pow, nf * 8, hipMemcpyDeviceToHost, st));
+        if (amax) PDC_HIP(hipMemcpyAsync(amax + c0, p + g.amax, B * 8, hipMemcpyDeviceToHost, st));
+        if (argmax) PDC_HIP(hipMemcpyAsync(argmax + c0, p + g.arg, B * 8, hipMemcpyDeviceToHost, st));
+        return PDC_OK;
     }
-    return PDC_OK;
-}
+};
 
 int ragged_host(const char *what, const RaggedJob &j, int64_t n_curves, const int *devices, int n_devices) {
-    PDC_REQUIRE(devices && n_devices >= 1 && n_devices <= 64, "%s: 1 .. 64 device slots (got %d)", what, n_devices);
     PDC_REQUIRE(j.offsets[n_curves] == 0 || (j.t && j.y), "%s: t and y must not be NULL", what);
-    for (int i = 0; i < n_devices; ++i) PDC_TRY(use_device(devices[i]));
-    std::lock_guard<std::mutex> lk(g_ragged_mutex);
-    if (g_ragged_devices != std::vector<int>(devices, devices + n_devices)) {
-        PDC_TRY(free_slots());
-        g_ragged_slots.resize((size_t)n_devices);
-        for (int i = 0; i < n_devices; ++i) g_ragged_slots[(size_t)i].device = devices[i];
-        g_ragged_devices.assign(devices, devices + n_devices);
-    }
-    // contiguous shares balanced by sum n_b nf_b (+ n_b + nf_b: the per-sample and per-bin work)
-    std::vector<double> pre((size_t)n_curves + 1, 0.0);
-    for (int64_t b = 0; b < n_curves; ++b) {
-        const double nb = (double)(j.offsets[b + 1] - j.offsets[b]), fb = (double)(j.foff[b + 1] - j.foff[b]);
-        pre[(size_t)b + 1] = pre[(size_t)b] + nb * fb + nb + fb;
-    }
-    std::vector<int64_t> share((size_t)n_devices + 1, n_curves);
-    share[0] = 0;
-    for (int i = 1; i < n_devices; ++i)
-        share[(size_t)i] = std::lower_bound(pre.begin(), pre.end(), pre.back() * i / n_devices) - pre.begin();
-    // each slot's groups: the largest group shrinks by powers of two (WorkScale) until it fits the slot's budget,
-    // PDC_WORK_BUDGET_GB and its share of what the device has free (plus what the slot already holds)
-    std::vector<std::vector<int64_t>> cuts((size_t)n_devices);
-    for (int i = 0; i < n_devices; ++i) {
-        RSlot &s = g_ragged_slots[(size_t)i];
-        PDC_TRY(use_device(s.device));
-        if (!s.stream) PDC_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-        const int64_t c0 = share[(size_t)i], c1 = share[(size_t)i + 1];
-        if (c1 <= c0) continue;
-        int same = 0;
-        int64_t held = 0;
-        for (const RSlot &o : g_ragged_slots)
-            if (o.device == s.device) {
-                ++same;
-                held += o.buf.cap;
-            }
-        int64_t budget = work_budget();
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const int64_t avail = (int64_t)((double)((int64_t)free_b + held) * 0.9 / same);
-            if (avail > 0 && (budget == 0 || avail < budget)) budget = avail;
-        } else {
-            (void)hipGetLastError();
-        }
-        int64_t nf_max = 0;
-        for (int64_t b = c0; b < c1 && j.k > 0; ++b) nf_max = std::max(nf_max, nf_of(j, b));
-        const int64_t whole = group_bytes(j, c0, c1, nf_max).total;
-        WorkScale ws(budget, [&] {
-            int64_t largest;
-            (void)make_groups(j, c0, c1, (int64_t)((double)whole * work_scale()), &largest);
-            return largest;
-        });
-        PDC_REQUIRE_FITS(ws, what);
-        int64_t largest;
-        cuts[(size_t)i] = make_groups(j, c0, c1, (int64_t)((double)whole * work_scale()), &largest);
-    }
-    std::vector<int> rc((size_t)n_devices, PDC_OK);
-    std::vector<std::string> why((size_t)n_devices);
-    auto run_slot = [&](int i) {
-        RSlot &s = g_ragged_slots[(size_t)i];
-        const std::vector<int64_t> &cut = cuts[(size_t)i];
-        int r = use_device(s.device);
-        for (size_t q = 0; r == PDC_OK && q + 1 < cut.size(); ++q) r = run_group(s, j, cut[q], cut[q + 1]);
-        if (r != PDC_OK) {
-            rc[(size_t)i] = r;
-            why[(size_t)i] = pdc_last_error();
-            (void)hipStreamSynchronize(s.stream);
-        }
-    };
-    if (n_devices == 1) {
-        run_slot(0);
-    } else {
-        std::vector<std::thread> th;
-        for (int i = 0; i < n_devices; ++i) th.emplace_back(run_slot, i);
-        for (std::thread &x : th) x.join();
-    }
-    for (int i = 0; i < n_devices; ++i)
-        if (rc[(size_t)i] != PDC_OK) {
-            set_error("%s", why[(size_t)i].c_str());
-            return rc[(size_t)i];
-        }
-    return PDC_OK;
+    return ragged_run(what, g_slots, j, n_curves, devices, n_devices);
 }
 
 }  // namespace
 
 // Frees the per-slot buffers and streams of the ragged host entries (pdc_release()).
-int pdc::release_ragged() {
-    std::lock_guard<std::mutex> lk(g_ragged_mutex);
-    return free_slots();
-}
+int pdc::release_ragged() { return g_slots.release(); }
 
 extern "C" {
 
@@ -780,7 +569,7 @@ int pdc_gls_scan_ragged(const double *t, const double *y, const double *dy, cons
     j.y = y;
     j.dy = dy;
     j.offsets = offsets;
-    j.foff = f_offsets;
+    j.rows = f_offsets;
     j.f0 = f0;
     j.delta = delta;
     j.fit_mean = fit_mean ? 1 : 0;
@@ -805,7 +594,7 @@ int pdc_gls_ragged_peaks(const double *t, const double *y, const double *dy, con
     j.y = y;
     j.dy = dy;
     j.offsets = offsets;
-    j.foff = f_offsets;
+    j.rows = f_offsets;
     j.f0 = f0;
     j.delta = delta;
     j.fit_mean = fit_mean ? 1 : 0;

@@ -5,6 +5,9 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <functional>
+#include <mutex>
+#include <vector>
 
 #include "../../include/periodicity_hip.h"
 
@@ -25,6 +28,63 @@ void release_multi();
 int release_ragged();
 // ... and those of the ragged-grid PDM / AoV / conditional-entropy host entries (pdm_ragged.hip).
 int release_phase_ragged();
+
+// ---- ragged-grid batches: the host side the kinds share (ragged.hip) ---------------------------------------------
+// A ragged batch is a catalogue of light curves that each keep their own grid: curve b owns samples
+// [offsets[b], offsets[b+1]) and rows [rows[b], rows[b+1]) - GLS's frequency bins (gls_ragged.hip) or the phase
+// folds' trial periods (pdm_ragged.hip).  Each kind keeps its kernels, workspace layout, uploads and launches.
+inline int64_t up256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+
+// The checks every ragged entry shares, with their texts: n_curves, offsets and `rows_name` starting at 0 and never
+// decreasing, fewer than 2^31 tiles of `tile` rows (`too_large` ends that message); curve(b) adds the kind's own.
+int ragged_validate(const char *what, const int64_t *offsets, const int64_t *rows, const char *rows_name,
+                    int64_t n_curves, int64_t tile, const char *too_large, const std::function<int(int64_t)> &curve);
+
+// Dispatch order of a ragged scan: order[0, m) = the curves with at least one row, most samples first (ties in curve
+// order), otile[0, m] = their prefix of tiles of `tile` rows; returns m.
+int64_t ragged_order(const int64_t *offsets, const int64_t *rows, int64_t n_curves, int64_t tile, int64_t *order,
+                     int64_t *otile);
+
+// Bytes of a group's peak table, the tail of its buffer (0 for k == 0): the pitched [B][pitch] copy of the rows, whose
+// pad [rows_b, pitch) is NaN, then count [B] | idx | half_lo | half_hi | height | prominence [B][k].
+int64_t ragged_table_bytes(int64_t n_curves, int64_t pitch, int k);
+
+struct RaggedSlot {   // one device slot: its stream, its grow-only buffer, the host copy of a group's metadata
+    int device = 0;
+    hipStream_t stream = nullptr;
+    void *buf = nullptr;
+    int64_t cap = 0;
+    std::vector<int64_t> meta;   // (uploaded asynchronously: lives until the stream is synchronised)
+};
+
+struct RaggedSlots {   // one kind's slots, kept between host calls for the same device list
+    std::mutex mutex;
+    std::vector<int> devices;
+    std::vector<RaggedSlot> slots;
+    int64_t groups = 0;   // groups the last call ran, over all slots
+    int release();        // frees every slot's stream and buffer (pdc_release())
+};
+
+// One host call of a kind: where its peak table goes (caller's host arrays, any may be NULL) and its two group hooks.
+struct RaggedBatch {
+    const int64_t *offsets, *rows;   // [B + 1]
+    int k, by_prominence;            // k > 0: a [B][k] peak table of the rows (pdc_peaks_topk_dev)
+    int64_t *count, *idx, *lo, *hi;
+    double *height, *prom;
+    int64_t rows_of(int64_t b) const { return rows[b + 1] - rows[b]; }
+    // Slot-buffer bytes of the group [c0, c1) whose longest grid has row_max rows (0 without a table); the buffer
+    // ends with the ragged_table_bytes(c1 - c0, row_max, k) of the peak table.
+    virtual int64_t group_bytes(int64_t c0, int64_t c1, int64_t row_max) const = 0;
+    // Enqueues the group on s.stream: uploads, launches (rows also into `pitched` when not NULL), copies of the kind's
+    // own outputs to the host.  ragged_run ranks the table and synchronises.
+    virtual int run_group(RaggedSlot &s, int64_t c0, int64_t c1, int64_t row_max, double *pitched) const = 0;
+};
+
+// A host call: curves dealt to device slots in contiguous shares balanced by sum n_b rows_b + n_b + rows_b (a device
+// may repeat), each share cut into contiguous groups that fit the slot's budget, one thread per slot; a slot's error
+// is the call's.
+int ragged_run(const char *what, RaggedSlots &slots, const RaggedBatch &batch, int64_t n_curves, const int *devices,
+               int n_devices);
 
 // Every device / pinned-host allocation of the library goes through these two, so that
 // pdc_alloc_counts() can show a caller (and the tests) that a cached path allocates nothing on

@@ -14,9 +14,9 @@
 //                             itself; so the scan below starts from the single call's bits.
 //   pdm_ragged_scan_kernel    one workgroup per (curve, tile of 64 trial periods), found by a scalar binary search
 //                             in a dispatch-order tile prefix table; tiles are dispatched costliest curve (most
-//                             samples) first.  The period of a lane is rebuilt with numpy's linspace rule
-//                             (j*step + start, two roundings - the unit is built with -ffp-contract=off - and
-//                             exactly `stop` at the last index), not uploaded.  The sample loop is
+//                             samples) first (ragged_order).  The period of a lane is rebuilt with numpy's
+//                             linspace rule (j*step + start, two roundings - the unit is built with
+//                             -ffp-contract=off - and exactly `stop` at the last index), not uploaded.  The sample loop is
 //                             pdm_chunks.inc, the text of pdm_scan_kernel's; the <BLOCK, SPLIT> instance is the one
 //                             the single call takes for a grid of < 131 072 periods (<256, 4>, or <64, 1> when
 //                             that histogram does not fit 150 KB of LDS), and so is the epilogue (pdm_common.h).
@@ -27,19 +27,17 @@
 //                             grid descends), negated for the kinds whose signal
 //                             is a minimum (PDM, conditional entropy) so that pdc_peaks_topk_dev ranks their dips.
 //                             The caller fills the pad with NaN; why the pad keeps scipy's answers, and the one
-//                             half-maximum artefact it leaves, is explained in gls_ragged.hip / periodicity_hip.h.
+//                             half-maximum artefact it leaves, is explained in ragged.hip / periodicity_hip.h.
+//
+// The host entries' device slots, groups, budget and peak table are the shared driver's (ragged.hip); this unit
+// sizes and runs one group.
 //
 // Bit identity: for a curve whose single call runs unsplit (n < 8192 samples, P < 131 072 periods) every value is
 // computed by the same instructions on the same inputs in the same order.  Longer curves are split over workgroups
 // by the single call (another summation order) and agree to rounding.
 #include "pdc_internal.h"
 
-#include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <mutex>
-#include <string>
-#include <thread>
 #include <vector>
 
 using namespace pdc;
@@ -196,8 +194,6 @@ __global__ __launch_bounds__(kFinBlock) void pdm_ragged_finish_kernel(RaggedPhas
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-int64_t up256(int64_t x) { return (x + 255) & ~(int64_t)255; }
-int64_t tiles_of(int64_t np) { return (np + kPTile - 1) / kPTile; }
 bool is_dip(int kind) { return kind != 1; }   // PDM theta and the conditional entropy are minimal at the period
 
 // The one instance per statistic and bin counts: `last` = highest histogram bin, bytes per bin 12 (sum + count) or
@@ -218,9 +214,9 @@ Shape shape_of(int kind, int nb, int nc) {
 }
 
 // Workspace of one launch over B curves: per-curve statistics, the metadata tables, the scan's rows; with k > 0
-// also the NaN-padded [B][p_max] copy and the [B][k] peak table.
+// also the peak-table tail (ragged_table_bytes).
 struct PhaseLayout {
-    int64_t stat, meta, raw, pitched, table, total;
+    int64_t stat, meta, raw, pitched, total;
 };
 constexpr int kMetaArrays = 9;   // offsets | poff | otile | order (int64) | start | step | stop | sigma | signif, B + 1 each
 
@@ -230,9 +226,7 @@ PhaseLayout phase_layout(int64_t n_curves, int64_t p_total, int64_t p_max, int k
     w.meta = up256(n_curves * 24);
     w.raw = w.meta + up256(kMetaArrays * (n_curves + 1) * 8);
     w.pitched = w.raw + up256(p_total * 8);
-    w.table = w.pitched + (k > 0 ? up256(n_curves * p_max * 8) : 0);
-    // count | idx | half_lo | half_hi | height | prominence
-    w.total = w.table + (k > 0 ? up256((n_curves + 5 * n_curves * (int64_t)k) * 8) : 0);
+    w.total = w.pitched + ragged_table_bytes(n_curves, p_max, k);
     return w;
 }
 
@@ -245,27 +239,20 @@ int validate(const char *what, int kind, const int64_t *offsets, int64_t n_curve
     PDC_REQUIRE(kind >= 0 && kind <= 2, "%s: kind must be 0 (PDM), 1 (AoV) or 2 (conditional entropy), got %d", what, kind);
     PDC_REQUIRE(offsets && start && step && stop && poff, "%s: NULL argument", what);
     PDC_REQUIRE(kind != 0 || sigma, "%s: PDM needs sigma[]", what);
-    PDC_REQUIRE(n_curves >= 1 && n_curves < ((int64_t)1 << 31), "%s: n_curves must be 1 .. 2^31 - 1 (got %lld)", what,
-                (long long)n_curves);
     PDC_REQUIRE(nb >= 1 && nc >= 1, "%s: bin counts must be positive", what);
     const Shape s = shape_of(kind, nb, nc);
     PDC_REQUIRE(s.last <= 190, "%s: %d histogram bins exceed the 191 that fit in LDS", what, s.last + 1);
-    PDC_REQUIRE(offsets[0] == 0 && poff[0] == 0, "%s: offsets[0] and p_offsets[0] must be 0", what);
-    int64_t tiles = 0;
-    for (int64_t b = 0; b < n_curves; ++b) {
-        const int64_t n = offsets[b + 1] - offsets[b], np = poff[b + 1] - poff[b];
-        PDC_REQUIRE(n >= 0, "%s: offsets must be non-decreasing (curve %lld)", what, (long long)b);
-        PDC_REQUIRE(np >= 0, "%s: p_offsets must be non-decreasing (curve %lld)", what, (long long)b);
+    auto curve = [&](int64_t b) {
+        const int64_t n = offsets[b + 1] - offsets[b];
         PDC_REQUIRE(kind != 2 || n <= kCellSamples,
                     "%s: curve %lld has %lld samples; a conditional-entropy batch bins a whole curve in one workgroup "
                     "of 16-bit cells (at most %lld samples)", what, (long long)b, (long long)n, (long long)kCellSamples);
-        PDC_REQUIRE(!signif || np >= 2, "%s: curve %lld: sub-harmonic averaging needs at least two trial periods", what,
-                    (long long)b);
-        tiles += tiles_of(np);
-    }
-    PDC_REQUIRE(tiles < ((int64_t)1 << 31), "%s: %lld tiles of %d periods: the grids are too large for one launch",
-                what, (long long)tiles, kPTile);
-    return PDC_OK;
+        PDC_REQUIRE(!signif || poff[b + 1] - poff[b] >= 2,
+                    "%s: curve %lld: sub-harmonic averaging needs at least two trial periods", what, (long long)b);
+        return PDC_OK;
+    };
+    return ragged_validate(what, offsets, poff, "p_offsets", n_curves, kPTile,
+                           "periods: the grids are too large for one launch", curve);
 }
 
 template <typename Kernel>
@@ -289,14 +276,12 @@ int phase_ragged_dev(int kind, int device, hipStream_t st, const double *d_t, co
     if (kind == 1) nc = 1;
     PDC_TRY(use_device(device));
     char *base = static_cast<char *>(work);
-    // metadata: one upload; dispatch order = curves with >= 1 tile, most samples first (ties: curve order)
+    // metadata: one upload; dispatch order = ragged_order (costliest curve first)
     const int64_t B1 = n_curves + 1;
     meta.assign((size_t)(kMetaArrays * B1), 0);
     int64_t *m_off = meta.data(), *m_poff = m_off + B1, *m_otile = m_poff + B1, *m_order = m_otile + B1;
     double *m_start = reinterpret_cast<double *>(m_order + B1), *m_step = m_start + B1, *m_stop = m_step + B1,
            *m_sigma = m_stop + B1, *m_signif = m_sigma + B1;
-    std::vector<int64_t> ord;
-    ord.reserve((size_t)n_curves);
     for (int64_t b = 0; b < n_curves; ++b) {
         m_off[b] = offsets[b];
         m_poff[b] = poff[b];
@@ -305,20 +290,10 @@ int phase_ragged_dev(int kind, int device, hipStream_t st, const double *d_t, co
         m_stop[b] = stop[b];
         m_sigma[b] = sigma ? sigma[b] : 1.0;
         m_signif[b] = signif ? signif[b] : 0.0;
-        if (poff[b + 1] > poff[b]) ord.push_back(b);
     }
     m_off[n_curves] = n_total;
     m_poff[n_curves] = p_total;
-    static const bool costly_first = [] { const char *e = getenv("PDC_RAGGED_ORDER"); return !(e && e[0] == '0'); }();
-    if (costly_first)
-        std::stable_sort(ord.begin(), ord.end(), [&](int64_t x, int64_t y) {
-            return offsets[x + 1] - offsets[x] > offsets[y + 1] - offsets[y];
-        });
-    const int64_t m = (int64_t)ord.size();
-    for (int64_t p = 0; p < m; ++p) {
-        m_order[p] = ord[(size_t)p];
-        m_otile[p + 1] = m_otile[p] + tiles_of(poff[ord[(size_t)p] + 1] - poff[ord[(size_t)p]]);
-    }
+    const int64_t m = ragged_order(offsets, poff, n_curves, kPTile, m_order, m_otile);
     const int64_t tiles = m_otile[m];
     int64_t *d_meta = reinterpret_cast<int64_t *>(base + w.meta);
     PDC_HIP(hipMemcpyAsync(d_meta, meta.data(), (size_t)(kMetaArrays * B1 * 8), hipMemcpyHostToDevice, st));
@@ -377,158 +352,56 @@ int phase_ragged_dev(int kind, int device, hipStream_t st, const double *d_t, co
     return PDC_OK;
 }
 
-// ---- host entries: curves dealt to device slots, each slot's share processed in groups that fit its budget ----
-struct RBuf {
-    void *p = nullptr;
-    int64_t cap = 0;
-};
+// ---- host entries: ragged_run (ragged.hip) deals the curves to device slots and runs each slot's groups ----------
+RaggedSlots g_slots;
 
-struct RSlot {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    RBuf buf;               // inputs | out | workspace of one group
-    std::vector<int64_t> meta;
-};
-
-std::mutex g_phase_mutex;
-std::vector<int> g_phase_devices;
-std::vector<RSlot> g_phase_slots;
-int64_t g_phase_groups = 0;   // groups the last host call ran, over all slots (pdc_test_phase_ragged_groups)
-
-int ensure_buf(RBuf &b, int64_t bytes) {   // (on the current device) grow-only
-    if (bytes < 256) bytes = 256;
-    if (b.cap >= bytes) return PDC_OK;
-    if (b.p) PDC_HIP(hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-    PDC_TRY(device_alloc(&b.p, bytes + bytes / 8));
-    b.cap = bytes + bytes / 8;
-    return PDC_OK;
-}
-
-int free_slots() {
-    for (RSlot &s : g_phase_slots) {
-        PDC_HIP(hipSetDevice(s.device));
-        if (s.stream) PDC_HIP(hipStreamDestroy(s.stream));
-        if (s.buf.p) PDC_HIP(hipFree(s.buf.p));
-    }
-    g_phase_slots.clear();
-    g_phase_devices.clear();
-    return PDC_OK;
-}
-
-// What one host call computes and where its results go (caller's host arrays, any may be NULL).
-struct PhaseJob {
-    int kind, nb, nc, k, by_prominence;
+// What one host call computes and where its results go (caller's host arrays, any may be NULL); rows = p_offsets.
+struct PhaseJob : RaggedBatch {
+    int kind, nb, nc;
     const double *t, *x;
-    const int64_t *offsets, *poff;
     const double *start, *step, *stop, *sigma, *signif;
     double *out;
-    int64_t *count, *idx, *lo, *hi;
-    double *height, *prom;
-};
 
-// Bytes of the slot buffer for the group [c0, c1) whose longest grid has p_max periods.
-struct GroupBytes {
-    int64_t in_t, in_x, out, work, total;
-};
-GroupBytes group_bytes(const PhaseJob &j, int64_t c0, int64_t c1, int64_t p_max) {
-    const int64_t n = j.offsets[c1] - j.offsets[c0], np = j.poff[c1] - j.poff[c0], B = c1 - c0;
-    GroupBytes g;
-    g.in_t = 0;
-    g.in_x = up256(n * 8);
-    g.out = g.in_x + up256(n * 8);
-    g.work = g.out + (j.out ? up256(np * 8) : 0);
-    g.total = g.work + phase_layout(B, np, p_max, j.k).total;
-    return g;
-}
-int64_t np_of(const PhaseJob &j, int64_t b) { return j.poff[b + 1] - j.poff[b]; }
+    // The slot buffer of the group [c0, c1) whose longest grid has p_max periods: inputs | out | workspace.
+    struct Bytes {
+        int64_t in_t, in_x, out, work, total;
+    };
+    Bytes bytes(int64_t c0, int64_t c1, int64_t p_max) const {
+        const int64_t n = offsets[c1] - offsets[c0], np = rows[c1] - rows[c0], B = c1 - c0;
+        Bytes g;
+        g.in_t = 0;
+        g.in_x = up256(n * 8);
+        g.out = g.in_x + up256(n * 8);
+        g.work = g.out + (out ? up256(np * 8) : 0);
+        g.total = g.work + phase_layout(B, np, p_max, k).total;
+        return g;
+    }
+    int64_t group_bytes(int64_t c0, int64_t c1, int64_t p_max) const override { return bytes(c0, c1, p_max).total; }
 
-// Contiguous groups of [c0, c1) of at most `cap` bytes each (a curve that alone exceeds it is a group of its own);
-// *largest = the bytes of the largest group.
-std::vector<int64_t> make_groups(const PhaseJob &j, int64_t c0, int64_t c1, int64_t cap, int64_t *largest) {
-    std::vector<int64_t> cut{c0};
-    *largest = 0;
-    int64_t g0 = c0, p_max = 0;
-    for (int64_t b = c0; b < c1; ++b) {
-        const int64_t grown = j.k > 0 ? std::max(p_max, np_of(j, b)) : 0;
-        if (b > g0 && group_bytes(j, g0, b + 1, grown).total > cap) {
-            *largest = std::max(*largest, group_bytes(j, g0, b, p_max).total);
-            cut.push_back(b);
-            g0 = b;
-            p_max = j.k > 0 ? np_of(j, b) : 0;
-        } else {
-            p_max = grown;
+    int run_group(RaggedSlot &s, int64_t c0, int64_t c1, int64_t p_max, double *pitched) const override {
+        const int64_t B = c1 - c0, s0 = offsets[c0], n = offsets[c1] - s0, pb = rows[c0], np = rows[c1] - pb;
+        const Bytes g = bytes(c0, c1, p_max);
+        char *p = static_cast<char *>(s.buf);
+        hipStream_t st = s.stream;
+        if (n > 0) {
+            PDC_HIP(hipMemcpyAsync(p + g.in_t, t + s0, n * 8, hipMemcpyHostToDevice, st));
+            PDC_HIP(hipMemcpyAsync(p + g.in_x, x + s0, n * 8, hipMemcpyHostToDevice, st));
         }
-    }
-    if (c1 > g0) *largest = std::max(*largest, group_bytes(j, g0, c1, p_max).total);
-    cut.push_back(c1);
-    return cut;
-}
-
-// One group on one slot, start to finish (the slot's stream is synchronised before return).
-int run_group(RSlot &s, const PhaseJob &j, int64_t c0, int64_t c1) {
-    const int64_t B = c1 - c0, s0 = j.offsets[c0], n = j.offsets[c1] - s0, pb = j.poff[c0], np = j.poff[c1] - pb;
-    int64_t p_max = 0;
-    for (int64_t b = c0; b < c1 && j.k > 0; ++b) p_max = std::max(p_max, np_of(j, b));
-    const GroupBytes g = group_bytes(j, c0, c1, p_max);
-    PDC_TRY(ensure_buf(s.buf, g.total));
-    char *p = static_cast<char *>(s.buf.p);
-    hipStream_t st = s.stream;
-    if (n > 0) {
-        PDC_HIP(hipMemcpyAsync(p + g.in_t, j.t + s0, n * 8, hipMemcpyHostToDevice, st));
-        PDC_HIP(hipMemcpyAsync(p + g.in_x, j.x + s0, n * 8, hipMemcpyHostToDevice, st));
-    }
-    std::vector<int64_t> off((size_t)B + 1), poff((size_t)B + 1);
-    for (int64_t b = 0; b <= B; ++b) {
-        off[(size_t)b] = j.offsets[c0 + b] - s0;
-        poff[(size_t)b] = j.poff[c0 + b] - pb;
-    }
-    const int k = j.k;
-    const PhaseLayout w = phase_layout(B, np, p_max, k);
-    char *work = p + g.work;
-    double *d_pitched = nullptr;
-    if (k > 0) {
-        d_pitched = reinterpret_cast<double *>(work + w.pitched);
-        // all-ones bytes: a NaN in every bin, the pad [P_b, p_max) stays so
-        PDC_HIP(hipMemsetAsync(d_pitched, 0xff, (size_t)(B * p_max * 8), st));
-    }
-    PDC_TRY(phase_ragged_dev(j.kind, s.device, st, (const double *)(p + g.in_t), (const double *)(p + g.in_x), off.data(),
-                             B, j.start + c0, j.step + c0, j.stop + c0, poff.data(), j.sigma ? j.sigma + c0 : nullptr,
-                             j.signif ? j.signif + c0 : nullptr, j.nb, j.nc, j.out ? (double *)(p + g.out) : nullptr,
-                             d_pitched, p_max, work, w.total, s.meta, false));
-    const int64_t nk = B * (int64_t)k;
-    int64_t *d_count = reinterpret_cast<int64_t *>(work + w.table), *d_idx = d_count + B, *d_lo = d_idx + nk,
-            *d_hi = d_lo + nk;
-    double *d_h = reinterpret_cast<double *>(d_hi + nk), *d_p = d_h + nk;
-    if (k > 0)
-        PDC_TRY(pdc_peaks_topk_dev(s.device, st, d_pitched, B, p_max, k, j.by_prominence, d_count, d_idx, d_h, d_p, d_lo,
-                                   d_hi));
-    if (j.out && np > 0) PDC_HIP(hipMemcpyAsync(j.out + pb, p + g.out, np * 8, hipMemcpyDeviceToHost, st));
-    if (k > 0) {
-        if (j.count) PDC_HIP(hipMemcpyAsync(j.count + c0, d_count, B * 8, hipMemcpyDeviceToHost, st));
-        if (j.idx) PDC_HIP(hipMemcpyAsync(j.idx + c0 * k, d_idx, nk * 8, hipMemcpyDeviceToHost, st));
-        if (j.height) PDC_HIP(hipMemcpyAsync(j.height + c0 * k, d_h, nk * 8, hipMemcpyDeviceToHost, st));
-        if (j.prom) PDC_HIP(hipMemcpyAsync(j.prom + c0 * k, d_p, nk * 8, hipMemcpyDeviceToHost, st));
-        if (j.lo) PDC_HIP(hipMemcpyAsync(j.lo + c0 * k, d_lo, nk * 8, hipMemcpyDeviceToHost, st));
-        if (j.hi) PDC_HIP(hipMemcpyAsync(j.hi + c0 * k, d_hi, nk * 8, hipMemcpyDeviceToHost, st));
-    }
-    PDC_HIP(hipStreamSynchronize(st));
-    if (k > 0 && j.lo) {
-        // the pad's one artefact: a sign flip of the pair (P_b - 1, P_b) is no crossing of the row itself
-        for (int64_t b = 0; b < B; ++b) {
-            const int64_t npb = np_of(j, c0 + b);
-            for (int r = 0; r < k; ++r)
-                if (j.lo[(c0 + b) * k + r] >= npb - 1) j.lo[(c0 + b) * k + r] = -1;
+        std::vector<int64_t> off((size_t)B + 1), poff((size_t)B + 1);
+        for (int64_t b = 0; b <= B; ++b) {
+            off[(size_t)b] = offsets[c0 + b] - s0;
+            poff[(size_t)b] = rows[c0 + b] - pb;
         }
+        PDC_TRY(phase_ragged_dev(kind, s.device, st, (const double *)(p + g.in_t), (const double *)(p + g.in_x),
+                                 off.data(), B, start + c0, step + c0, stop + c0, poff.data(), sigma ? sigma + c0 : nullptr,
+                                 signif ? signif + c0 : nullptr, nb, nc, out ? (double *)(p + g.out) : nullptr,
+                                 pitched, p_max, p + g.work, g.total - g.work, s.meta, false));
+        if (out && np > 0) PDC_HIP(hipMemcpyAsync(out + pb, p + g.out, np * 8, hipMemcpyDeviceToHost, st));
+        return PDC_OK;
     }
-    if (k > 0 && j.height && is_dip(j.kind))   // the table ranked -stat: heights back to the statistic's own values
-        for (int64_t i = c0 * k; i < c1 * k; ++i) j.height[i] = -j.height[i];
-    return PDC_OK;
-}
+};
 
 int phase_host(const char *what, const PhaseJob &j, int64_t n_curves, const int *devices, int n_devices) {
-    PDC_REQUIRE(devices && n_devices >= 1 && n_devices <= 64, "%s: 1 .. 64 device slots (got %d)", what, n_devices);
     PDC_REQUIRE(j.offsets[n_curves] == 0 || (j.t && j.x), "%s: t and x must not be NULL", what);
     if (j.kind == 2)   // the magnitude bins index the cell histogram: reject what is not one of 0 .. n_mag-1
         for (int64_t b = 0; b < n_curves; ++b)
@@ -536,87 +409,9 @@ int phase_host(const char *what, const PhaseJob &j, int64_t n_curves, const int 
                 PDC_REQUIRE(j.x[i] >= 0.0 && j.x[i] < (double)j.nc,
                             "%s: curve %lld: mag_bin[%lld] = %g is not a bin index in 0 .. %d", what, (long long)b,
                             (long long)(i - j.offsets[b]), j.x[i], j.nc - 1);
-    for (int i = 0; i < n_devices; ++i) PDC_TRY(use_device(devices[i]));
-    std::lock_guard<std::mutex> lk(g_phase_mutex);
-    if (g_phase_devices != std::vector<int>(devices, devices + n_devices)) {
-        PDC_TRY(free_slots());
-        g_phase_slots.resize((size_t)n_devices);
-        for (int i = 0; i < n_devices; ++i) g_phase_slots[(size_t)i].device = devices[i];
-        g_phase_devices.assign(devices, devices + n_devices);
-    }
-    // contiguous shares balanced by sum n_b P_b (+ n_b + P_b: the per-sample and per-period work)
-    std::vector<double> pre((size_t)n_curves + 1, 0.0);
-    for (int64_t b = 0; b < n_curves; ++b) {
-        const double nb = (double)(j.offsets[b + 1] - j.offsets[b]), pb = (double)np_of(j, b);
-        pre[(size_t)b + 1] = pre[(size_t)b] + nb * pb + nb + pb;
-    }
-    std::vector<int64_t> share((size_t)n_devices + 1, n_curves);
-    share[0] = 0;
-    for (int i = 1; i < n_devices; ++i)
-        share[(size_t)i] = std::lower_bound(pre.begin(), pre.end(), pre.back() * i / n_devices) - pre.begin();
-    // each slot's groups: the largest group shrinks by powers of two (WorkScale) until it fits the slot's budget,
-    // PDC_WORK_BUDGET_GB and its share of what the device has free (plus what the slot already holds)
-    std::vector<std::vector<int64_t>> cuts((size_t)n_devices);
-    for (int i = 0; i < n_devices; ++i) {
-        RSlot &s = g_phase_slots[(size_t)i];
-        PDC_TRY(use_device(s.device));
-        if (!s.stream) PDC_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-        const int64_t c0 = share[(size_t)i], c1 = share[(size_t)i + 1];
-        if (c1 <= c0) continue;
-        int same = 0;
-        int64_t held = 0;
-        for (const RSlot &o : g_phase_slots)
-            if (o.device == s.device) {
-                ++same;
-                held += o.buf.cap;
-            }
-        int64_t budget = work_budget();
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const int64_t avail = (int64_t)((double)((int64_t)free_b + held) * 0.9 / same);
-            if (avail > 0 && (budget == 0 || avail < budget)) budget = avail;
-        } else {
-            (void)hipGetLastError();
-        }
-        int64_t p_max = 0;
-        for (int64_t b = c0; b < c1 && j.k > 0; ++b) p_max = std::max(p_max, np_of(j, b));
-        const int64_t whole = group_bytes(j, c0, c1, p_max).total;
-        WorkScale ws(budget, [&] {
-            int64_t largest;
-            (void)make_groups(j, c0, c1, (int64_t)((double)whole * work_scale()), &largest);
-            return largest;
-        });
-        PDC_REQUIRE_FITS(ws, what);
-        int64_t largest;
-        cuts[(size_t)i] = make_groups(j, c0, c1, (int64_t)((double)whole * work_scale()), &largest);
-    }
-    g_phase_groups = 0;
-    for (const std::vector<int64_t> &cut : cuts) g_phase_groups += cut.empty() ? 0 : (int64_t)cut.size() - 1;
-    std::vector<int> rc((size_t)n_devices, PDC_OK);
-    std::vector<std::string> why((size_t)n_devices);
-    auto run_slot = [&](int i) {
-        RSlot &s = g_phase_slots[(size_t)i];
-        const std::vector<int64_t> &cut = cuts[(size_t)i];
-        int r = use_device(s.device);
-        for (size_t q = 0; r == PDC_OK && q + 1 < cut.size(); ++q) r = run_group(s, j, cut[q], cut[q + 1]);
-        if (r != PDC_OK) {
-            rc[(size_t)i] = r;
-            why[(size_t)i] = pdc_last_error();
-            (void)hipStreamSynchronize(s.stream);
-        }
-    };
-    if (n_devices == 1) {
-        run_slot(0);
-    } else {
-        std::vector<std::thread> th;
-        for (int i = 0; i < n_devices; ++i) th.emplace_back(run_slot, i);
-        for (std::thread &x : th) x.join();
-    }
-    for (int i = 0; i < n_devices; ++i)
-        if (rc[(size_t)i] != PDC_OK) {
-            set_error("%s", why[(size_t)i].c_str());
-            return rc[(size_t)i];
-        }
+    PDC_TRY(ragged_run(what, g_slots, j, n_curves, devices, n_devices));
+    if (j.k > 0 && j.height && is_dip(j.kind))   // the table ranked -stat: heights back to the statistic's own values
+        for (int64_t i = 0; i < n_curves * j.k; ++i) j.height[i] = -j.height[i];
     return PDC_OK;
 }
 
@@ -630,7 +425,7 @@ PhaseJob make_job(int kind, const double *t, const double *x, const int64_t *off
     j.t = t;
     j.x = x;
     j.offsets = offsets;
-    j.poff = p_offsets;
+    j.rows = p_offsets;
     j.start = start;
     j.step = step;
     j.stop = stop;
@@ -642,17 +437,14 @@ PhaseJob make_job(int kind, const double *t, const double *x, const int64_t *off
 }  // namespace
 
 // Frees the per-slot buffers and streams of the ragged phase-scan host entries (pdc_release()).
-int pdc::release_phase_ragged() {
-    std::lock_guard<std::mutex> lk(g_phase_mutex);
-    return free_slots();
-}
+int pdc::release_phase_ragged() { return g_slots.release(); }
 
 extern "C" {
 
 int pdc_test_phase_ragged_groups(int64_t *groups) {
     PDC_REQUIRE(groups, "pdc_test_phase_ragged_groups: NULL argument");
-    std::lock_guard<std::mutex> lk(g_phase_mutex);
-    *groups = g_phase_groups;
+    std::lock_guard<std::mutex> lk(g_slots.mutex);
+    *groups = g_slots.groups;
     return PDC_OK;
 }
 

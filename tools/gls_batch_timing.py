@@ -2,8 +2,7 @@
 
 The batch: 4096 curves, N log-uniform in 300 .. 5000, baselines 100 .. 3000 days, jittered cadences, so that every
 curve has its own grid (GLS's default rule).  Reports, with the inputs in HBM:
-  (a) the ragged scan (prologue + scan + per-curve maximum; event-timed, median of 5) and its pair rate,
-      dispatched costliest curve first and in curve order (a child process with PDC_RAGGED_ORDER=0);
+  (a) the ragged scan (prologue + scan + per-curve maximum; event-timed, median of 5) and its pair rate;
   (b) wall time of GLS().batch(..., peaks=1) against a loop of GLS()(s) + period_at_highest_peak;
   (c) the shared-grid batch (pdc_gls_scan_dev, 4096 curves of 2000 samples) at about the same number of pairs;
   (d) what the peak table adds: NaN-padded pitched copy + pdc_peaks_topk_dev (k = 1, by height).
@@ -11,7 +10,6 @@ Usage: python tools/gls_batch_timing.py [--scan-only]
 """
 import ctypes as C
 import os
-import subprocess
 import sys
 import time
 
@@ -68,16 +66,12 @@ def main(scan_only):
                                                 ptr(delta), ptr(foff), 1, 0, power.ptr if pw else None, pitch_ptr,
                                                 nf_max, amax.ptr, arg.ptr, work.ptr, wb))
 
-    order = "curve order" if os.environ.get("PDC_RAGGED_ORDER") == "0" else "costliest curve first"
     ms = tm.ms(scan, reps=5, warm=2)
-    print(f"(a) ragged scan, {order}: B={B} N={n_total} ({np.diff(offsets).min()}..{np.diff(offsets).max()}) "
+    print(f"(a) ragged scan: B={B} N={n_total} ({np.diff(offsets).min()}..{np.diff(offsets).max()}) "
           f"nf={nf_total} ({nfb.min()}..{nf_max}) pairs={pairs:.3e}: {ms:.2f} ms, {pairs / ms * 1e3:.3e} pair/s "
           "(prologue + scan + maxima + the 0.2 MB metadata upload)")
     if scan_only:
         return
-    child = subprocess.run([sys.executable, os.path.abspath(__file__), "--scan-only"], capture_output=True, text=True,
-                           env=dict(os.environ, PDC_RAGGED_ORDER="0"), timeout=600)
-    print(child.stdout.strip() or child.stderr.strip()[-2000:])
 
     # (d) the peak table's share: pitched copy with its NaN pad + top-1 by height on it
     out = DB(B * (1 + 5) * 8, dev)

@@ -5,7 +5,6 @@ days, jittered cadences), scanned with PDM's defaults (nb = 5, nc = 2, 1000 peri
 n_periods=None (every curve its own count).  Reports, with the inputs in HBM:
   (a) the ragged scan (prologue + scan; event-timed, median of 5) and its pair rate, next to C5 PDM's
       (pdc_pdm_scan_dev, N = 5e4 x 1e5 periods) measured in the same run;
-  (b) costliest curve first against curve order (a child process with PDC_RAGGED_ORDER=0);
   (c) wall time of PDM().batch(..., peaks=1, want_power=False) against a loop of PDM()(s) + find_dips, with its
       host (Python) / library split.
 Usage: python tools/phase_batch_timing.py [--scan-only | --batch-only]   (--batch-only: one PDM().batch call of the
@@ -13,7 +12,6 @@ survey, peaks=1, want_power=False - the run to put under a kernel trace)
 """
 import ctypes as C
 import os
-import subprocess
 import sys
 import time
 
@@ -53,7 +51,6 @@ def main(scan_only):
     tm = bench.EventTimer(lib, _cabi, dev, sp.value)
     bt, bx = DB.from_array(t, dev), DB.from_array(x, dev)
     ptr = _cabi._ptr
-    order = "curve order" if os.environ.get("PDC_RAGGED_ORDER") == "0" else "costliest curve first"
     for label, n_periods in (("n_periods=1000", 1000), ("n_periods=None", None)):
         start, step, stop, poff = description(sigs, n_periods)
         P = int(poff[-1])
@@ -67,16 +64,13 @@ def main(scan_only):
                                                       None, 0, work.ptr, wb))
 
         ms = tm.ms(scan, reps=5, warm=2)
-        print(f"(a) PDM ragged scan, {label}, {order}: B={B} N={offsets[-1]} ({nb_.min()}..{nb_.max()}) P={P} "
+        print(f"(a) PDM ragged scan, {label}: B={B} N={offsets[-1]} ({nb_.min()}..{nb_.max()}) P={P} "
               f"({np.diff(poff).min()}..{np.diff(poff).max()}) pairs={pairs:.3e}: {ms:.2f} ms, "
               f"{pairs / ms * 1e3:.3e} pair/s (prologue + scan + the metadata upload)")
         work.free()
         out.free()
     if scan_only:
         return
-    child = subprocess.run([sys.executable, os.path.abspath(__file__), "--scan-only"], capture_output=True, text=True,
-                           env=dict(os.environ, PDC_RAGGED_ORDER="0"), timeout=600)
-    print(child.stdout.strip() or child.stderr.strip()[-2000:])
 
     # C5 PDM (N = 5e4 x 1e5 periods), the single-curve rate this batch is measured against
     t5, y5, _, periods, _ = bench.c5_inputs()
