@@ -391,6 +391,49 @@ int pdc_phase_scan_ragged_dev(int kind, int device, void *stream, const double *
                               double *d_out, double *d_pitched, int64_t pitch, void *work,
                               int64_t work_bytes);
 
+/* ---- StringLength over curves on their OWN period grids (StringLength.batch) ------------------------
+ * Replaces a survey's loop of StringLength()(s) (each curve on 1 / np.linspace(n_periods * s, s, n_periods),
+ * s = dphi / baseline, phase.py:67-68) followed by find_dips / periods_at_half_max on each result.
+ * Curve b owns samples [offsets[b], offsets[b+1]) of t and m (m already scaled to [-0.25, 0.25] by the caller)
+ * and the trial periods 1 / linspace(start[b], stop[b], P_b), P_b = p_offsets[b+1] - p_offsets[b]: a FREQUENCY
+ * linspace rebuilt on the device with numpy's rule (j*step[b] + start[b], two roundings, exactly stop[b] at
+ * j = P_b - 1 > 0; for P_b == 1 pass step = stop - start), then an IEEE reciprocal.  Lengths come back in period
+ * order, out[p_offsets[b] + j], bit-identical to pdc_stringlength_scan on that curve and those periods: curves of
+ * 1 .. 26 048 samples run the single call's one-cycle pre-pass and two-workgroups-per-CU kernel as ragged
+ * launches (the same instance, the same per-period code), the periods that kernel marks and every other curve
+ * run the single call's own kernels on the curve's slices.
+ * Devices, groups and budget as for pdc_phase_scan_ragged (bit-identical for any grouping).
+ *
+ * pdc_stringlength_ragged_peaks: the [B][k] peak table (k <= 1024) of the DIPS of every curve's row in FSeries
+ * order (ascending frequency: j' = P_b - 1 - j when start[b] > stop[b], j' = j otherwise), as find_dips ranks
+ * them; height_out holds the lengths themselves, the half-maximum crossings are those of the negated row.
+ * out may be NULL: the rows stay in HBM.
+ *
+ * pdc_stringlength_ragged_work_bytes / pdc_stringlength_scan_ragged_dev: ONE group on `device` / `stream`: t, m
+ * on the device; offsets ... p_offsets on the HOST.  d_out [p_offsets[B]] and/or d_pitched [B][pitch] (FSeries
+ * order, negated; its pad is the caller's).  The entry waits for the stream once, to read how many periods the
+ * ragged kernel left to the one-workgroup kernel.  work_bytes >= pdc_stringlength_ragged_work_bytes(offsets,
+ * p_offsets, B). */
+int pdc_stringlength_scan_ragged(const double *t, const double *m, const int64_t *offsets, int64_t n_curves,
+                                 const double *start, const double *step, const double *stop,
+                                 const int64_t *p_offsets, double *out, const int *devices, int n_devices);
+int pdc_stringlength_ragged_peaks(const double *t, const double *m, const int64_t *offsets, int64_t n_curves,
+                                  const double *start, const double *step, const double *stop,
+                                  const int64_t *p_offsets, int k, int by_prominence, int64_t *count_out,
+                                  int64_t *idx_out, double *height_out, double *prominence_out,
+                                  int64_t *half_lo_out, int64_t *half_hi_out, double *out, const int *devices,
+                                  int n_devices);
+int64_t pdc_stringlength_ragged_work_bytes(const int64_t *offsets, const int64_t *p_offsets, int64_t n_curves);
+/* TEST HOOK (not for callers): of the last pdc_stringlength_scan_ragged / pdc_stringlength_ragged_peaks call of this
+ * process, the groups it ran (summed over its device slots), the (curve, period) pairs the ragged kernel marked for
+ * the one-workgroup kernel, and the curves that took the single call's own route (more than 26 048 samples ...). */
+int pdc_test_sl_ragged_stats(int64_t *groups, int64_t *marked, int64_t *long_curves);
+int pdc_stringlength_scan_ragged_dev(int device, void *stream, const double *d_t, const double *d_m,
+                                     const int64_t *offsets, int64_t n_curves, const double *start,
+                                     const double *step, const double *stop, const int64_t *p_offsets,
+                                     double *d_out, double *d_pitched, int64_t pitch, void *work,
+                                     int64_t work_bytes);
+
 /* ---- Phase Dispersion Minimization -----------------------------------------------------------
  * Replaces pool.map(PDM._pdm, periods) (phase.py:128-149, 185-187): theta_out[p] for every trial
  * period, bins phi in [k/m0, (k+nc)/m0) U [0, (k+nc-m0)/m0), m0 = nb*nc, phi = (t/period) % 1

@@ -94,6 +94,13 @@ PROTOTYPES = {
     "pdc_test_phase_ragged_groups": (_I, [C.POINTER(_L)]),
     "pdc_phase_scan_ragged_dev": (_I, [_I, _I, _VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I,
                                        _VP, _VP, _L, _VP, _L]),
+    "pdc_stringlength_scan_ragged": (_I, [_VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _VP, _VP, _I]),
+    "pdc_stringlength_ragged_peaks": (_I, [_VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP,
+                                           _VP, _VP, _VP, _I]),
+    "pdc_stringlength_ragged_work_bytes": (_L, [_VP, _VP, _L]),
+    "pdc_test_sl_ragged_stats": (_I, [C.POINTER(_L), C.POINTER(_L), C.POINTER(_L)]),
+    "pdc_stringlength_scan_ragged_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _VP, _VP, _L, _VP,
+                                              _L]),
     "pdc_pdm_scan": (_I, [_VP, _VP, _L, _VP, _L, _I, _I, _D, _VP, _I]),
     "pdc_pdm_scan_dev": (_I, [_I, _VP, _VP, _VP, _L, _VP, _L, _I, _I, _D, _VP]),
     "pdc_aov_scan": (_I, [_VP, _VP, _L, _VP, _L, _I, _VP, _I]),
@@ -601,6 +608,41 @@ def phase_scan_ragged(kind, t, x, offsets, start, step, stop, p_offsets, nb, nc,
                                        _ptr(table["indices"]), _ptr(table["heights"]), _ptr(table["prominences"]),
                                        _ptr(table["half_lo"]), _ptr(table["half_hi"]), _ptr(out), _ptr(devs), devs.size))
     return out, table
+
+
+def stringlength_scan_ragged(t, m, offsets, start, step, stop, p_offsets, k=0, by_prominence=False,
+                             want_power=True, device=None, devices=None):
+    """StringLength over a batch of curves, each on its own grid ``1 / linspace(start[b], stop[b], P_b)``
+    (``pdc_stringlength_scan_ragged``; with ``k > 0`` ``pdc_stringlength_ragged_peaks``):
+    ``(out [p_offsets[-1]] | None, peak table dict | None)``."""
+    t, m = _f64(t, "t"), _f64(m, "m")
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    p_offsets = np.ascontiguousarray(p_offsets, dtype=np.int64)
+    start, step, stop = _f64(start, "start"), _f64(step, "step"), _f64(stop, "stop")
+    nb_ = offsets.size - 1
+    if nb_ < 1 or p_offsets.size != nb_ + 1 or any(a.size != nb_ for a in (start, step, stop)):
+        raise ValueError("offsets / p_offsets need n_curves + 1 entries, start / step / stop n_curves")
+    if offsets[-1] != t.size or m.size != t.size:
+        raise ValueError("Input arrays have incompatible lengths.")
+    out = np.empty(int(p_offsets[-1]), dtype=np.float64) if want_power else None
+    devs = _slots(device, devices)
+    common = (_ptr(t), _ptr(m), _ptr(offsets), nb_, _ptr(start), _ptr(step), _ptr(stop), _ptr(p_offsets))
+    if not k:
+        check(lib().pdc_stringlength_scan_ragged(*common, _ptr(out), _ptr(devs), devs.size))
+        return out, None
+    table = _topk_outputs(nb_, int(k))
+    check(lib().pdc_stringlength_ragged_peaks(*common, int(k), int(bool(by_prominence)), _ptr(table["count"]),
+                                              _ptr(table["indices"]), _ptr(table["heights"]),
+                                              _ptr(table["prominences"]), _ptr(table["half_lo"]),
+                                              _ptr(table["half_hi"]), _ptr(out), _ptr(devs), devs.size))
+    return out, table
+
+
+def sl_ragged_stats():
+    """Test hook: ``(groups, marked pairs, long curves)`` of the last StringLength batch call."""
+    g, mk, lc = C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib().pdc_test_sl_ragged_stats(C.byref(g), C.byref(mk), C.byref(lc)))
+    return g.value, mk.value, lc.value
 
 
 def pdm_scan(t, x, periods, nb, nc, sigma, device=None, devices=None):

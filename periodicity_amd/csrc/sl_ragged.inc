@@ -1,0 +1,682 @@
+// StringLength over a batch of light curves that each keep their OWN period grid ("ragged" grids):
+// StringLength.batch.  Included at the end of stringlength.hip: it needs the fast:: / duo:: / onecycle:: helpers,
+// sl_ranges.inc, sl_duo_body.inc and the single call's host ladder (stringlength_scan_impl, launch_fast_for).
+//
+// Every curve's trial periods are 1 / np.linspace(count * s, s, count), s = dphi / baseline_b (phase.py:
+// _string_periods): curve b owns samples [offsets[b], offsets[b+1]) and the periods 1 / linspace(start[b], stop[b],
+// P_b), P_b = p_offsets[b+1] - p_offsets[b], whose lengths go to out[p_offsets[b] + j] (period order).
+//
+// A curve of 1 <= N <= duo::kCapD samples takes, in the single call, the one-cycle pre-pass, sl_prep_kernel, the duo
+// kernel and sl_fast_kernel on the periods the duo kernel marked.  Here, for all such curves of a group at once:
+//   sl_ragged_periods_kernel  one thread per (curve, period): 1.0 / (j * step + start), exactly 1.0 / stop at the
+//                             last index - numpy's linspace rule (the unit is built with -ffp-contract=off), then an
+//                             IEEE division, as 1 / np.linspace(...) computes the single call's periods.
+//   sl_ragged_prep_kernel     one workgroup per curve: the AoS (t, m) records and the |t| flag of sl_prep_kernel and the
+//                             bad[0..1] words of sl_tame_kernel (OR reductions: any order gives the same words).
+//   sl_ragged_mark_kernel     one thread per (curve, period): sl_onecycle_mark_kernel's test with that curve's words.
+//   sl_ragged_onecycle_kernel one 1024-thread workgroup per listed (curve, period): sl_onecycle_kernel's sum, the same
+//                             reduction shape (so the same bits).
+//   sl_duo_ragged_kernel      persistent; the ticket counts (curve, period) items in a dispatch-order prefix table,
+//                             costliest curve first (ragged_order); a workgroup finds its curve by a scalar binary
+//                             search and runs sl_duo_body.inc - the text of sl_duo_kernel's period - on that curve's
+//                             slices.  One launch per instance the single call would pick (<16, 256, 512>, <16>,
+//                             <36>, <52>): P3c adds range lengths r = tid, tid + kB, ..., so the block size decides the
+//                             summation order.  A marked period increments its curve's counter.
+// Then the host reads the B counters and runs launch_fast_for<false> on the slices of every curve with marks; curves
+// the duo kernel does not take (N > kCapD, N = 0, or knobs that move the single call off it) run
+// stringlength_scan_impl on their slices, with the hints the host entry would compute.  Every value is therefore the
+// single call's, bit for bit.  sl_ragged_pitch_kernel writes the optional pitched copy for the peak table: FSeries
+// order (ascending frequency = the period index reversed on a descending frequency grid), negated (a string length
+// is minimal at the period).
+#include <algorithm>
+#include <atomic>
+
+namespace {
+
+namespace slr {
+
+constexpr int kMeta = 14;          // int64 arrays of B + 1 in the metadata upload (slr_group_dev)
+constexpr int kPrepBlock = 256;
+constexpr int kRangeGrid = 1024;   // duo workgroups at most (4 x 256 CUs): the range scratch is laid out for them
+constexpr int64_t kMarkGrid = 32;  // workgroups of the marked-period fallback (its scratch is laid out for them)
+constexpr int kLong = 4, kNone = 5;   // routes beyond the four duo instances
+
+struct Args {
+    const double *t, *m;            // every curve's samples
+    const int64_t *offsets, *poff;  // [B + 1]
+    const int64_t *route;           // [B] 0..3 duo instance, kLong, kNone
+    const double *start, *step, *stop;   // [B] the FREQUENCY linspace of every curve
+    int64_t n_curves, p_total;
+    double *periods;                // [p_total]
+    fast::rec_t *rec;               // [n_total]
+    unsigned *flags;                // [B] sl_prep_kernel's flag
+    unsigned *bad;                  // [B][2] sl_tame_kernel's words
+    unsigned char *skip, *todo;     // [p_total]
+    unsigned *list, *count;         // one-cycle periods (global index) and their number
+    unsigned *marked;               // [B] periods the duo kernel left to the one-workgroup kernel
+    double *ell;                    // [p_total]
+    double *pitched;                // [B][pitch] or nullptr
+    int64_t pitch;
+};
+
+__device__ __forceinline__ int64_t curve_of(const int64_t *poff, int64_t n_curves, int64_t q) {
+    int64_t lo = 0, hi = n_curves - 1;   // the last b with poff[b] <= q (empty curves share their start)
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (poff[mid] <= q) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void sl_ragged_periods_kernel(Args a) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= a.p_total) return;
+    const int64_t b = curve_of(a.poff, a.n_curves, q);
+    const int64_t j = q - a.poff[b], count = a.poff[b + 1] - a.poff[b];
+    const double f = count > 1 && j == count - 1 ? a.stop[b] : __dadd_rn(__dmul_rn((double)j, a.step[b]), a.start[b]);
+    a.periods[q] = 1.0 / f;
+}
+
+__global__ __launch_bounds__(kPrepBlock) void sl_ragged_prep_kernel(Args a) {
+    const int64_t b = blockIdx.x;
+    if (a.route[b] >= kLong) return;   // (workgroup-uniform)
+    __shared__ unsigned words[2];
+    if (threadIdx.x < 2) words[threadIdx.x] = 0u;
+    __syncthreads();
+    const int64_t off = a.offsets[b], n = a.offsets[b + 1] - off;
+    const double *t = a.t + off, *m = a.m + off;
+    bool mine = false, unsorted = false;
+    for (int64_t i = threadIdx.x; i < n; i += kPrepBlock) {
+        const double tv = t[i];
+        fast::rec_t v;
+        v.x = tv;
+        v.y = m[i];
+        a.rec[off + i] = v;
+        const double at = __builtin_fabs(tv);
+        mine = mine || !(at == 0.0 || (at >= 1e-150 && at <= 1e150));
+        unsorted = unsorted || (i > 0 && !(t[i - 1] <= tv));   // (NaN counts as unsorted)
+    }
+    if (mine) atomicOr(&words[0], 1u);
+    if (unsorted) atomicOr(&words[1], 1u);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a.flags[b] = words[0] ? 0u : 1u;
+        a.bad[2 * b + 0] = words[0];
+        a.bad[2 * b + 1] = words[1];
+    }
+}
+
+__global__ __launch_bounds__(256) void sl_ragged_mark_kernel(Args a) {
+    using namespace fast;
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= a.p_total) return;
+    const int64_t b = curve_of(a.poff, a.n_curves, q);
+    bool one = false;
+    if (a.route[b] < kLong) {
+        const int64_t off = a.offsets[b], n = a.offsets[b + 1] - off;
+        const unsigned *bad = a.bad + 2 * b;
+        if (bad[1] == 0u && n >= 2) {   // (sl_onecycle_mark_kernel, statement for statement)
+            const double period = a.periods[q];
+            const double y = 1.0 / period;
+            const bool safe = period_is_safe(period, bad[0] == 0u);
+            const double q0 = exact_quotient(a.t[off], period, y, safe), q1 = exact_quotient(a.t[off + n - 1], period, y, safe);
+            const double c0 = __builtin_floor(q0), c1 = __builtin_floor(q1);
+            one = period > 0.0 && (c1 - c0 == 0.0 || (c1 - c0 == 1.0 && q1 - c1 < q0 - c0));
+        }
+    }
+    a.skip[q] = one ? 1 : 0;
+    if (one) a.list[atomicAdd(a.count, 1u)] = (unsigned)q;
+}
+
+__global__ __launch_bounds__(kBlock) void sl_ragged_onecycle_kernel(Args a) {
+    using namespace fast;
+    __shared__ double red[kBlock / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned count = *a.count;
+    for (unsigned k = blockIdx.x; k < count; k += gridDim.x) {   // (workgroup-uniform)
+        const int64_t q = a.list[k];
+        const int64_t b = curve_of(a.poff, a.n_curves, q);
+        const int64_t off = a.offsets[b], n = a.offsets[b + 1] - off;
+        const double *t = a.t + off, *m = a.m + off;
+        const double period = a.periods[q];
+        const double y = 1.0 / period;
+        const bool safe = period_is_safe(period, a.bad[2 * b] == 0u);
+        double acc = 0.0;
+        for (int64_t i = tid + 1; i < n; i += kBlock) {          // segment (i - 1, i)
+            const double p1 = fast_phase(t[i], period, y, safe), p0 = fast_phase(t[i - 1], period, y, safe);
+            acc += short_hypot(m[i] - m[i - 1], p1 - p0);
+        }
+        acc = wave_sum_fixed(acc);
+        if (lane == 0) red[wave] = acc;
+        __syncthreads();
+        if (tid == 0) {
+            double total = 0.0;
+            for (int x = 0; x < kBlock / 64; ++x) total += red[x];
+            total += hypot(m[0] - m[n - 1], fast_phase(t[0], period, y, safe) - fast_phase(t[n - 1], period, y, safe));
+            a.ell[q] = total;
+        }
+        __syncthreads();
+    }
+}
+
+// FSeries order and sign for pdc_peaks_topk_dev: ascending frequency is the period index reversed when the frequency
+// grid descends (start > stop: the usual case), kept otherwise
+__global__ __launch_bounds__(256) void sl_ragged_pitch_kernel(Args a) {
+    const int64_t b = blockIdx.x;
+    const int64_t po = a.poff[b], np = a.poff[b + 1] - po;
+    const bool rev = a.start[b] > a.stop[b];
+    for (int64_t j = threadIdx.x; j < np; j += 256) a.pitched[b * a.pitch + (rev ? np - 1 - j : j)] = -a.ell[po + j];
+}
+
+}  // namespace slr
+
+namespace duo {
+
+struct RaggedDuoArgs {
+    const double *t, *m, *periods;
+    const rec_t *rec;
+    const int64_t *offsets, *poff;   // [B + 1]
+    const int64_t *order, *opre;     // this instance's curves in dispatch order [mc], their period prefix [mc + 1]
+    int64_t mc;
+    const unsigned *flags;           // [B]
+    unsigned *ticket;                // [0] next item (zeroed before the launch)
+    unsigned *marked;                // [B]
+    double *ell;
+    unsigned char *todo;
+    const unsigned char *skip;
+    double *rsum;                    // [grid][nr_pad][4]
+    int *rcnt;                       // [grid][nr_pad]
+    double *rlen;                    // [grid][nr_pad]
+    int64_t nr_pad;
+};
+
+// sl_duo_kernel over the (curve, period) items of every curve of one instance; the period body is the same text
+template <int KMAX, int BLK = duo::kB, int NBL = kNB>
+__global__ __launch_bounds__(BLK, 4) void sl_duo_ragged_kernel(RaggedDuoArgs ra) {
+    constexpr int kB = BLK, kW = BLK / 64;
+    constexpr int kDCap = BLK >= 512 ? ::kDCap : 1024;
+    static_assert(kW * kWaveB >= (NBL + 64) * 4 && kW * kWaveB >= kDCap * 10, "aliases must fit");
+    typedef unsigned short IdxT;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    unsigned char *wbuf = lds_raw;
+    unsigned *hist = reinterpret_cast<unsigned *>(lds_raw);
+    unsigned long long *bkeys = reinterpret_cast<unsigned long long *>(lds_raw);
+    IdxT *bidx = reinterpret_cast<IdxT *>(bkeys + kDCap);
+    unsigned short *bndb = reinterpret_cast<unsigned short *>(lds_raw + kW * kWaveB);
+    unsigned short *bnds = bndb + kRangesD + 8;
+    unsigned *defer = reinterpret_cast<unsigned *>(bnds + kRangesD + 8);
+    IdxT *order = reinterpret_cast<IdxT *>(defer + 16);
+    __shared__ unsigned wave_tot[kW];
+    __shared__ double red[kW];
+    __shared__ unsigned s_item, s_bad;
+    const int tid0 = threadIdx.x, lane = tid0 & 63, wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
+    double *rsum = ra.rsum + (int64_t)blockIdx.x * ra.nr_pad * 4;
+    int *rcnt = ra.rcnt + (int64_t)blockIdx.x * ra.nr_pad;
+    double *rlen = ra.rlen + (int64_t)blockIdx.x * ra.nr_pad;
+    const unsigned n_items = (unsigned)ra.opre[ra.mc];
+
+    unsigned long long *keys_w = reinterpret_cast<unsigned long long *>(wbuf + wave * kWaveB);
+    unsigned *fine_w = reinterpret_cast<unsigned *>(wbuf + wave * kWaveB + kRCap * 8);
+    IdxT *idx_w = reinterpret_cast<IdxT *>(wbuf + wave * kWaveB + kRCap * 8 + (kWFine + 4) * 4);
+
+    for (;;) {
+        __syncthreads();   // the previous item is done with LDS
+        if (tid0 == 0) {
+            s_item = atomicAdd(ra.ticket, 1u);
+            s_bad = 0u;
+        }
+        __syncthreads();
+        const unsigned item = (unsigned)__builtin_amdgcn_readfirstlane((int)s_item);
+        if (item >= n_items) break;
+        // dispatch position: the c with opre[c] <= item < opre[c + 1] (every listed curve has >= 1 period)
+        int64_t lo = 0, hi = ra.mc - 1;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) >> 1;
+            if (ra.opre[mid] <= (int64_t)item) lo = mid;
+            else hi = mid - 1;
+        }
+        const int64_t curve = ra.order[lo];
+        const int64_t p = (int64_t)item - ra.opre[lo];
+        const int64_t off = ra.offsets[curve], po = ra.poff[curve];
+        if (ra.skip[po + p]) continue;   // (workgroup-uniform)
+        const int n = (int)(ra.offsets[curve + 1] - off);
+        const bool t_safe = ra.flags[curve] != 0u;
+        unsigned *const marked = ra.marked + curve;
+        const struct {
+            const double *t, *m, *periods;
+            const rec_t *rec;
+            double *ell;
+            unsigned char *todo;
+            int64_t n;
+        } a{ra.t + off, ra.m + off, ra.periods + po, ra.rec + off, ra.ell + po, ra.todo + po, n};   // (the names the body reads)
+#include "sl_duo_body.inc"
+    }
+}
+
+}  // namespace duo
+
+// ---- host side ----------------------------------------------------------------------------------------------------
+// The route the single call takes for a curve of n samples and P periods: 0..3 = duo instance <16, 256, 512>, <16>,
+// <36>, <52> (sl_fast); kLong = anything else (stringlength_scan_impl on the curve's slices); kNone = no periods.
+int slr_route(int64_t n, int64_t P) {
+    if (P == 0) return slr::kNone;
+    const Knobs &k = knobs();
+    if (n < 1 || n > duo::kCapD || !k.slices || k.general_only || !k.duo || stream_takes(n) ||
+        n > k.fast_slices * (int64_t)fast::FL<unsigned>::capacity)
+        return slr::kLong;
+    if (k.quad && n <= duo::kCapQ) return 0;
+    const int64_t kd = (n + duo::kB - 1) / duo::kB;
+    return kd <= 16 ? 1 : (kd <= 36 ? 2 : 3);
+}
+
+// Bytes of the area a curve's fallback needs: the marked periods' scratch (sl_layout at kMarkGrid periods) or the
+// whole single-call workspace.  Call outside any WorkScale scope (the scan itself runs outside one).
+int64_t slr_fallback_bytes(int route, int64_t n, int64_t P, int hints) {
+    if (route == slr::kNone) return 0;
+    if (route == slr::kLong) return sorted_scan_work_bytes(3, n, P, hints);
+    return sl_layout(n, P < slr::kMarkGrid ? P : slr::kMarkGrid, false).total;
+}
+
+struct SlRaggedLayout {
+    int64_t meta, rec, flags, bad, periods, skip, todo, list, count, ell, range, fallback, total;
+};
+// nr_pad: range slots of the longest duo curve (0: none); fallback: the largest slr_fallback_bytes of the group
+SlRaggedLayout slr_layout(int64_t B, int64_t n_total, int64_t p_total, int64_t nr_pad, int64_t fallback) {
+    SlRaggedLayout w;
+    w.meta = 0;
+    w.rec = w.meta + up256(slr::kMeta * (B + 1) * 8);
+    w.flags = w.rec + up256(n_total * 16);
+    w.bad = w.flags + up256(B * 4);
+    w.periods = w.bad + up256(B * 8);
+    w.skip = w.periods + up256(p_total * 8);
+    w.todo = w.skip + up256(p_total);
+    w.list = w.todo + up256(p_total);
+    w.count = w.list + up256(p_total * 4);   // count | ticket | (256 on) marked [B]
+    w.ell = w.count + 256 + up256(B * 4);
+    w.range = w.ell + up256(p_total * 8);
+    w.fallback = w.range + up256((int64_t)slr::kRangeGrid * nr_pad * (32 + 4 + 8));
+    w.total = w.fallback + up256(fallback);
+    return w;
+}
+
+template <int KMAX, int BLK = duo::kB, int NBL = fast::kNB>
+int launch_duo_ragged(const duo::RaggedDuoArgs &a, int n_max, int64_t grid, hipStream_t st) {
+    const size_t fixed = (size_t)(BLK / 64) * duo::kWaveB + 2 * (duo::kRangesD + 8) * 2 + 64;
+    const size_t lds = fixed + (size_t)((n_max + 64 + 7) & ~7) * 2;
+    PDC_TRY(allow_dynamic_lds((const void *)duo::sl_duo_ragged_kernel<KMAX, BLK, NBL>, duo::kLdsWg - duo::kStaticD));
+    hipLaunchKernelGGL((duo::sl_duo_ragged_kernel<KMAX, BLK, NBL>), dim3((unsigned)grid), dim3(BLK), lds, st, a);
+    return PDC_OK;
+}
+
+struct SlrStats {
+    std::atomic<int64_t> marked{0}, long_curves{0};
+};
+SlrStats g_slr_stats;
+
+// Every launch of one group.  Metadata (offsets, p_offsets rebased to the group, the frequency linspace, per-curve
+// hints and fallback bytes) on the host; t, m, the outputs and the workspace on the device.  Waits for the stream once,
+// after the duo scan, to read the per-curve counts of marked periods.
+int slr_group_dev(int device, hipStream_t st, const double *d_t, const double *d_m, const int64_t *offsets,
+                  int64_t B, const double *start, const double *step, const double *stop, const int64_t *poff,
+                  const int *hints, double *d_out, double *d_pitched, int64_t pitch, void *work, int64_t work_bytes,
+                  std::vector<int64_t> &meta, bool wait_meta) {
+    const int64_t n_total = offsets[B], p_total = poff[B];
+    std::vector<int> route((size_t)B);
+    int64_t n_duo = 0, fb = 0;
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t n = offsets[b + 1] - offsets[b], P = poff[b + 1] - poff[b];
+        route[(size_t)b] = slr_route(n, P);
+        if (route[(size_t)b] < slr::kLong) n_duo = std::max(n_duo, n);
+        fb = std::max(fb, slr_fallback_bytes(route[(size_t)b], n, P, hints ? hints[b] : kHintLists));
+    }
+    const SlRaggedLayout w = slr_layout(B, n_total, p_total, n_duo > 0 ? range_slots(n_duo) : 0, fb);
+    PDC_REQUIRE(work && work_bytes >= w.total, "stringlength_ragged: workspace too small (%lld < %lld bytes)",
+                (long long)work_bytes, (long long)w.total);
+    PDC_REQUIRE(n_total == 0 || (d_t && d_m), "stringlength_ragged: t and m must not be NULL");
+    PDC_TRY(use_device(device));
+    if (p_total == 0) return PDC_OK;
+    char *base = static_cast<char *>(work);
+    // metadata: offsets | poff | route | order[4] | opre[4] | start | step | stop, B + 1 each
+    const int64_t B1 = B + 1;
+    meta.assign((size_t)(slr::kMeta * B1), 0);
+    int64_t *m_off = meta.data(), *m_poff = m_off + B1, *m_route = m_poff + B1, *m_order = m_route + B1,
+            *m_opre = m_order + 4 * B1;
+    double *m_dbl = reinterpret_cast<double *>(m_opre + 4 * B1);
+    for (int64_t b = 0; b <= B; ++b) {
+        m_off[b] = offsets[b];
+        m_poff[b] = poff[b];
+    }
+    int64_t mc[4], items[4];
+    int n_max[4] = {0, 0, 0, 0};
+    std::vector<int64_t> rows((size_t)B1);
+    for (int c = 0; c < 4; ++c) {   // each instance's curves, most samples first, and their period prefix
+        rows[0] = 0;
+        for (int64_t b = 0; b < B; ++b) {
+            rows[(size_t)b + 1] = rows[(size_t)b] + (route[(size_t)b] == c ? poff[b + 1] - poff[b] : 0);
+            if (route[(size_t)b] == c) n_max[c] = std::max(n_max[c], (int)(offsets[b + 1] - offsets[b]));
+        }
+        mc[c] = ragged_order(offsets, rows.data(), B, 1, m_order + c * B1, m_opre + c * B1);
+        items[c] = m_opre[c * B1 + mc[c]];
+    }
+    for (int64_t b = 0; b < B; ++b) {
+        m_route[b] = route[(size_t)b];
+        m_dbl[b] = start[b];
+        m_dbl[B1 + b] = step[b];
+        m_dbl[2 * B1 + b] = stop[b];
+    }
+    int64_t *d_meta = reinterpret_cast<int64_t *>(base + w.meta);
+    PDC_HIP(hipMemcpyAsync(d_meta, meta.data(), (size_t)(slr::kMeta * B1 * 8), hipMemcpyHostToDevice, st));
+    if (wait_meta) PDC_HIP(hipStreamSynchronize(st));   // (`meta` goes when the caller returns)
+    const double *d_dbl = reinterpret_cast<const double *>(d_meta + 11 * B1);
+
+    slr::Args a = {};
+    a.t = d_t;
+    a.m = d_m;
+    a.offsets = d_meta;
+    a.poff = d_meta + B1;
+    a.route = d_meta + 2 * B1;
+    a.start = d_dbl;
+    a.step = d_dbl + B1;
+    a.stop = d_dbl + 2 * B1;
+    a.n_curves = B;
+    a.p_total = p_total;
+    a.periods = ptr<double>(base, w.periods);
+    a.rec = ptr<fast::rec_t>(base, w.rec);
+    a.flags = ptr<unsigned>(base, w.flags);
+    a.bad = ptr<unsigned>(base, w.bad);
+    a.skip = ptr<unsigned char>(base, w.skip);
+    a.todo = ptr<unsigned char>(base, w.todo);
+    a.list = ptr<unsigned>(base, w.list);
+    a.count = ptr<unsigned>(base, w.count);
+    a.marked = ptr<unsigned>(base, w.count + 256);
+    a.ell = d_out ? d_out : ptr<double>(base, w.ell);
+    a.pitched = d_pitched;
+    a.pitch = pitch;
+    unsigned *ticket = a.count + 1;
+    PDC_HIP(hipMemsetAsync(a.count, 0, (size_t)(256 + B * 4), st));
+    const unsigned pgrid = (unsigned)((p_total + 255) / 256);
+    hipLaunchKernelGGL(slr::sl_ragged_periods_kernel, dim3(pgrid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(slr::sl_ragged_prep_kernel, dim3((unsigned)B), dim3(slr::kPrepBlock), 0, st, a);
+    hipLaunchKernelGGL(slr::sl_ragged_mark_kernel, dim3(pgrid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(slr::sl_ragged_onecycle_kernel, dim3(256), dim3(kBlock), 0, st, a);
+    PDC_HIP(hipGetLastError());
+
+    const bool any_duo = items[0] + items[1] + items[2] + items[3] > 0;
+    if (any_duo) {
+        duo::RaggedDuoArgs d;
+        d.t = d_t;
+        d.m = d_m;
+        d.periods = a.periods;
+        d.rec = a.rec;
+        d.offsets = a.offsets;
+        d.poff = a.poff;
+        d.flags = a.flags;
+        d.ticket = ticket;
+        d.marked = a.marked;
+        d.ell = a.ell;
+        d.todo = a.todo;
+        d.skip = a.skip;
+        d.nr_pad = range_slots(n_duo);
+        d.rsum = ptr<double>(base, w.range);
+        d.rcnt = ptr<int>(base, w.range + (int64_t)slr::kRangeGrid * d.nr_pad * 32);
+        d.rlen = ptr<double>(base, w.range + (int64_t)slr::kRangeGrid * d.nr_pad * 36);
+        const int cus = cu_count(device);
+        for (int c = 0; c < 4; ++c) {
+            if (items[c] == 0) continue;
+            d.order = d_meta + (3 + c) * B1;
+            d.opre = d_meta + (7 + c) * B1;
+            d.mc = mc[c];
+            int64_t grid = (c == 0 ? 4 : 2) * (int64_t)cus;
+            grid = std::min(grid, std::min(items[c], (int64_t)slr::kRangeGrid));
+            PDC_HIP(hipMemsetAsync(ticket, 0, 4, st));
+            if (c == 0) PDC_TRY((launch_duo_ragged<16, 256, 512>(d, n_max[c], grid, st)));
+            else if (c == 1) PDC_TRY(launch_duo_ragged<16>(d, n_max[c], grid, st));
+            else if (c == 2) PDC_TRY(launch_duo_ragged<36>(d, n_max[c], grid, st));
+            else PDC_TRY(launch_duo_ragged<52>(d, n_max[c], grid, st));
+            PDC_HIP(hipGetLastError());
+        }
+    }
+    // fallbacks on each curve's slices: the marked periods (sl_fast's one-workgroup kernel), the long curves
+    char *area = base + w.fallback;
+    if (any_duo) {
+        std::vector<unsigned> marks((size_t)B);
+        PDC_HIP(hipMemcpyAsync(marks.data(), a.marked, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+        PDC_HIP(hipStreamSynchronize(st));
+        for (int64_t b = 0; b < B; ++b) {
+            if (route[(size_t)b] >= slr::kLong || marks[(size_t)b] == 0) continue;
+            const int64_t off = offsets[b], po = poff[b], n = offsets[b + 1] - off, P = poff[b + 1] - po;
+            const SlLayout l = sl_layout(n, P < slr::kMarkGrid ? P : slr::kMarkGrid, false);
+            fast::FastArgs f = fast_args(l, area, d_t + off, d_m + off, a.periods + po, n, P, a.ell + po);
+            f.rec = a.rec + off;
+            f.flags = a.flags + b;
+            f.skip = a.skip + po;
+            f.todo = a.todo + po;
+            f.todo_count = a.marked + b;
+            PDC_TRY(launch_fast_for<false>(f, l.grid, st, knobs().p17));
+            PDC_HIP(hipGetLastError());
+            g_slr_stats.marked += marks[(size_t)b];
+        }
+    }
+    for (int64_t b = 0; b < B; ++b) {
+        if (route[(size_t)b] != slr::kLong) continue;
+        const int64_t off = offsets[b], po = poff[b], n = offsets[b + 1] - off, P = poff[b + 1] - po;
+        PDC_TRY(stringlength_scan_impl(device, st, d_t + off, d_m + off, n, a.periods + po, P, a.ell + po, area,
+                                       w.total - w.fallback, hints ? hints[b] : kHintLists));
+        ++g_slr_stats.long_curves;
+    }
+    if (d_pitched) {
+        hipLaunchKernelGGL(slr::sl_ragged_pitch_kernel, dim3((unsigned)B), dim3(256), 0, st, a);
+        PDC_HIP(hipGetLastError());
+    }
+    return PDC_OK;
+}
+
+// ---- host entries: ragged_run (ragged.hip) deals the curves to device slots and runs each slot's groups ----------
+RaggedSlots g_slr_slots;
+
+// Range maxima over the curves of a group in O(1) (make_groups asks for every prefix of a share)
+struct RangeMax {
+    std::vector<std::vector<int64_t>> lv;
+    explicit RangeMax(const std::vector<int64_t> &v) : lv{v} {
+        for (size_t h = 1; ((size_t)1 << h) <= v.size(); ++h) {
+            const std::vector<int64_t> &p = lv.back();
+            std::vector<int64_t> q(v.size() - ((size_t)1 << h) + 1);
+            for (size_t i = 0; i < q.size(); ++i) q[i] = std::max(p[i], p[i + ((size_t)1 << (h - 1))]);
+            lv.push_back(std::move(q));
+        }
+    }
+    int64_t operator()(int64_t c0, int64_t c1) const {   // max over [c0, c1), c1 > c0
+        size_t h = 0;
+        while (((size_t)2 << h) <= (size_t)(c1 - c0)) ++h;
+        return std::max(lv[h][(size_t)c0], lv[h][(size_t)c1 - ((size_t)1 << h)]);
+    }
+};
+
+struct SlJob : RaggedBatch {
+    const double *t, *m, *start, *step, *stop;
+    double *out;
+    std::vector<int> hints;            // per curve (long curves: host_hints, as pdc_stringlength_scan computes them)
+    const RangeMax *fb_max, *nr_max;   // per-curve fallback bytes, range slots of the duo curves
+
+    struct Bytes {
+        int64_t in_t, in_m, out, work, total;
+    };
+    Bytes bytes(int64_t c0, int64_t c1, int64_t p_max) const {
+        const int64_t n = offsets[c1] - offsets[c0], np = rows[c1] - rows[c0], B = c1 - c0;
+        Bytes g;
+        g.in_t = 0;
+        g.in_m = up256(n * 8);
+        g.out = g.in_m + up256(n * 8);
+        g.work = g.out + (out ? up256(np * 8) : 0);
+        g.total = g.work + slr_layout(B, n, np, (*nr_max)(c0, c1), (*fb_max)(c0, c1)).total +
+                  ragged_table_bytes(B, p_max, k);
+        return g;
+    }
+    int64_t group_bytes(int64_t c0, int64_t c1, int64_t p_max) const override { return bytes(c0, c1, p_max).total; }
+
+    int run_group(RaggedSlot &s, int64_t c0, int64_t c1, int64_t p_max, double *pitched) const override {
+        const int64_t B = c1 - c0, s0 = offsets[c0], n = offsets[c1] - s0, pb = rows[c0], np = rows[c1] - pb;
+        const Bytes g = bytes(c0, c1, p_max);
+        char *p = static_cast<char *>(s.buf);
+        hipStream_t st = s.stream;
+        if (n > 0) {
+            PDC_HIP(hipMemcpyAsync(p + g.in_t, t + s0, n * 8, hipMemcpyHostToDevice, st));
+            PDC_HIP(hipMemcpyAsync(p + g.in_m, m + s0, n * 8, hipMemcpyHostToDevice, st));
+        }
+        std::vector<int64_t> off((size_t)B + 1), poff((size_t)B + 1);
+        for (int64_t b = 0; b <= B; ++b) {
+            off[(size_t)b] = offsets[c0 + b] - s0;
+            poff[(size_t)b] = rows[c0 + b] - pb;
+        }
+        PDC_TRY(slr_group_dev(s.device, st, (const double *)(p + g.in_t), (const double *)(p + g.in_m), off.data(), B,
+                              start + c0, step + c0, stop + c0, poff.data(), hints.data() + c0,
+                              out ? (double *)(p + g.out) : nullptr, pitched, p_max, p + g.work,
+                              g.total - g.work - ragged_table_bytes(B, p_max, k), s.meta, false));
+        if (out && np > 0) PDC_HIP(hipMemcpyAsync(out + pb, p + g.out, np * 8, hipMemcpyDeviceToHost, st));
+        return PDC_OK;
+    }
+};
+
+int slr_validate(const char *what, const int64_t *offsets, int64_t n_curves, const double *start, const double *step,
+                 const double *stop, const int64_t *p_offsets) {
+    PDC_REQUIRE(offsets && start && step && stop && p_offsets, "%s: NULL argument", what);
+    auto curve = [&](int64_t b) {
+        PDC_REQUIRE(offsets[b + 1] - offsets[b] < ((int64_t)1 << 31), "%s: curve %lld has 2^31 samples or more", what,
+                    (long long)b);
+        return PDC_OK;
+    };
+    return ragged_validate(what, offsets, p_offsets, "p_offsets", n_curves, 1,
+                           "periods: the grids are too large for one launch", curve);
+}
+
+// The host-side periods of curve b (as the device writes them): what host_hints reads for a long curve
+int slr_hints(const double *t, int64_t n, double start, double step, double stop, int64_t P) {
+    std::vector<double> periods((size_t)P);
+    for (int64_t j = 0; j < P; ++j) {
+        const double f = P > 1 && j == P - 1 ? stop : (double)j * step + start;
+        periods[(size_t)j] = 1.0 / f;
+    }
+    return sorted_scan_hints(3, t, n, periods.data(), P);
+}
+
+int slr_host(SlJob &j, int64_t n_curves, const int *devices, int n_devices) {
+    PDC_REQUIRE(j.offsets[n_curves] == 0 || (j.t && j.m), "stringlength_ragged: t and m must not be NULL");
+    std::vector<int64_t> fb((size_t)n_curves), nr((size_t)n_curves);
+    j.hints.assign((size_t)n_curves, kHintLists);
+    for (int64_t b = 0; b < n_curves; ++b) {   // (outside any WorkScale scope: the sizes the scans will ask for)
+        const int64_t n = j.offsets[b + 1] - j.offsets[b], P = j.rows_of(b);
+        const int route = slr_route(n, P);
+        if (route == slr::kLong)
+            j.hints[(size_t)b] = slr_hints(j.t + j.offsets[b], n, j.start[b], j.step[b], j.stop[b], P);
+        fb[(size_t)b] = slr_fallback_bytes(route, n, P, j.hints[(size_t)b]);
+        nr[(size_t)b] = route < slr::kLong ? range_slots(n) : 0;
+    }
+    const RangeMax fb_max(fb), nr_max(nr);
+    j.fb_max = &fb_max;
+    j.nr_max = &nr_max;
+    g_slr_stats.marked = 0;
+    g_slr_stats.long_curves = 0;
+    PDC_TRY(ragged_run("stringlength_ragged", g_slr_slots, j, n_curves, devices, n_devices));
+    if (j.k > 0 && j.height)   // the table ranked -length: heights back to the lengths themselves
+        for (int64_t i = 0; i < n_curves * j.k; ++i) j.height[i] = -j.height[i];
+    return PDC_OK;
+}
+
+SlJob slr_job(const double *t, const double *m, const int64_t *offsets, const double *start, const double *step,
+              const double *stop, const int64_t *p_offsets) {
+    SlJob j;
+    j.offsets = offsets;
+    j.rows = p_offsets;
+    j.k = 0;
+    j.by_prominence = 0;
+    j.count = j.idx = j.lo = j.hi = nullptr;
+    j.height = j.prom = nullptr;
+    j.t = t;
+    j.m = m;
+    j.start = start;
+    j.step = step;
+    j.stop = stop;
+    j.out = nullptr;
+    j.fb_max = j.nr_max = nullptr;
+    return j;
+}
+
+}  // namespace
+
+// Frees the per-slot buffers and streams of the ragged StringLength host entries (pdc_release()).
+int pdc::release_sl_ragged() { return g_slr_slots.release(); }
+
+extern "C" {
+
+int pdc_test_sl_ragged_stats(int64_t *groups, int64_t *marked, int64_t *long_curves) {
+    PDC_REQUIRE(groups && marked && long_curves, "pdc_test_sl_ragged_stats: NULL argument");
+    std::lock_guard<std::mutex> lk(g_slr_slots.mutex);
+    *groups = g_slr_slots.groups;
+    *marked = g_slr_stats.marked;
+    *long_curves = g_slr_stats.long_curves;
+    return PDC_OK;
+}
+
+int64_t pdc_stringlength_ragged_work_bytes(const int64_t *offsets, const int64_t *p_offsets, int64_t n_curves) {
+    if (!offsets || !p_offsets || n_curves < 1) return -1;
+    int64_t n_duo = 0, fb = 0;
+    for (int64_t b = 0; b < n_curves; ++b) {
+        const int64_t n = offsets[b + 1] - offsets[b], P = p_offsets[b + 1] - p_offsets[b];
+        if (n < 0 || P < 0) return -1;
+        const int route = slr_route(n, P);
+        if (route < slr::kLong) n_duo = std::max(n_duo, n);
+        fb = std::max(fb, slr_fallback_bytes(route, n, P, kHintLists));
+    }
+    return slr_layout(n_curves, offsets[n_curves] - offsets[0], p_offsets[n_curves] - p_offsets[0],
+                      n_duo > 0 ? range_slots(n_duo) : 0, fb).total;
+}
+
+int pdc_stringlength_scan_ragged_dev(int device, void *stream, const double *d_t, const double *d_m,
+                                     const int64_t *offsets, int64_t n_curves, const double *start, const double *step,
+                                     const double *stop, const int64_t *p_offsets, double *d_out, double *d_pitched,
+                                     int64_t pitch, void *work, int64_t work_bytes) {
+    PDC_TRY(slr_validate("stringlength_ragged_dev", offsets, n_curves, start, step, stop, p_offsets));
+    PDC_REQUIRE(d_out || d_pitched, "stringlength_ragged_dev: no output requested");
+    if (d_pitched)
+        for (int64_t b = 0; b < n_curves; ++b)
+            PDC_REQUIRE(p_offsets[b + 1] - p_offsets[b] <= pitch,
+                        "stringlength_ragged_dev: curve %lld has more periods than the pitch", (long long)b);
+    std::vector<int64_t> meta;
+    return slr_group_dev(device, (hipStream_t)stream, d_t, d_m, offsets, n_curves, start, step, stop, p_offsets,
+                         nullptr, d_out, d_pitched, pitch, work, work_bytes, meta, true);
+}
+
+int pdc_stringlength_scan_ragged(const double *t, const double *m, const int64_t *offsets, int64_t n_curves,
+                                 const double *start, const double *step, const double *stop,
+                                 const int64_t *p_offsets, double *out, const int *devices, int n_devices) {
+    PDC_TRY(slr_validate("stringlength_ragged", offsets, n_curves, start, step, stop, p_offsets));
+    PDC_REQUIRE(out, "stringlength_ragged: no output requested");
+    SlJob j = slr_job(t, m, offsets, start, step, stop, p_offsets);
+    j.out = out;
+    return slr_host(j, n_curves, devices, n_devices);
+}
+
+int pdc_stringlength_ragged_peaks(const double *t, const double *m, const int64_t *offsets, int64_t n_curves,
+                                  const double *start, const double *step, const double *stop,
+                                  const int64_t *p_offsets, int k, int by_prominence, int64_t *count_out,
+                                  int64_t *idx_out, double *height_out, double *prominence_out, int64_t *half_lo_out,
+                                  int64_t *half_hi_out, double *out, const int *devices, int n_devices) {
+    PDC_TRY(slr_validate("stringlength_ragged_peaks", offsets, n_curves, start, step, stop, p_offsets));
+    PDC_REQUIRE(k >= 1 && k <= 1024, "stringlength_ragged_peaks: k must be 1..1024 (got %d)", k);
+    PDC_REQUIRE(count_out || idx_out || height_out || prominence_out || half_lo_out || half_hi_out || out,
+                "stringlength_ragged_peaks: no output requested");
+    SlJob j = slr_job(t, m, offsets, start, step, stop, p_offsets);
+    j.k = k;
+    j.by_prominence = by_prominence ? 1 : 0;
+    j.out = out;
+    j.count = count_out;
+    j.idx = idx_out;
+    j.height = height_out;
+    j.prom = prominence_out;
+    j.lo = half_lo_out;
+    j.hi = half_hi_out;
+    return slr_host(j, n_curves, devices, n_devices);
+}
+
+}  // extern "C"

@@ -12,6 +12,7 @@ one Python task per trial period over a ``multiprocessing.Pool`` (``phase.py:69-
 here a whole period grid is ONE kernel launch (``csrc/stringlength.hip``, ``csrc/pdm.hip``), so
 ``cores`` is kept only for signature compatibility.  No scan is ever computed on the CPU.
 """
+import operator
 from multiprocessing import cpu_count
 
 import numpy as np
@@ -21,7 +22,8 @@ from .core import FSeries, TSeries
 
 MAX_CORES = cpu_count()
 
-__all__ = ["StringLength", "PDM", "AOV", "ConditionalEntropy", "GregoryLoredo", "SuperSmoother", "PhaseBatch"]
+__all__ = ["StringLength", "PDM", "AOV", "ConditionalEntropy", "GregoryLoredo", "SuperSmoother", "PhaseBatch",
+           "StringLengthBatch"]
 
 
 # ---- host-side grid / scaling rules (O(N) or O(n_periods) numpy, as upstream) -----------------------
@@ -138,6 +140,94 @@ class PhaseBatch(object):
 
     def __len__(self):
         return self._p_offsets.size - 1
+
+
+def _string_grid(baselines, dphi, count):
+    """Per curve, the FREQUENCY linspace of ``_string_periods(baseline, dphi, count)``: ``(start, step, stop)`` with
+    ``1 / _linspace_at(start, step, stop, count, j)`` equal to its ``j``-th period, bit for bit."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        stop = dphi / np.asarray(baselines, dtype=np.float64)
+        start = count * stop
+        return start, _linspace_steps(start, stop, np.full(stop.shape, count, dtype=np.int64)), stop
+
+
+class StringLengthBatch(PhaseBatch):
+    """What ``StringLength.batch`` returns: a :class:`PhaseBatch` whose grids are reciprocal linspaces
+    (``_string_periods``): ``periods[b] = 1 / linspace(start[b], stop[b], P_b)``, and whose peak table's frequencies
+    are ``FSeries(1 / periods).frequency``, i.e. ``1 / (1 / f)``."""
+
+    @property
+    def periods(self):
+        if self._periods is None:
+            count = np.diff(self._p_offsets)
+            rows = np.repeat(np.arange(count.size), count)
+            j = np.arange(self._p_offsets[-1], dtype=np.int64) - np.repeat(self._p_offsets[:-1], count)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                flat = 1 / _linspace_at(self._start[rows], self._step[rows], self._stop[rows], count[rows], j)
+            self._periods = np.split(flat, self._p_offsets[1:-1])
+        return self._periods
+
+    def _frequency_at(self, rows, bins):
+        """Frequency of bin ``bins`` of ``periodograms[rows]``: ascending frequency, so the index reversed on a
+        descending frequency grid (the usual one) and kept otherwise."""
+        count = np.diff(self._p_offsets)[rows]
+        start, stop = self._start[rows], self._stop[rows]
+        j = np.where(start > stop, count - 1 - bins, bins)
+        return 1 / (1 / _linspace_at(start, self._step[rows], stop, count, j))
+
+
+def _string_batch(scan, signals, peaks, by_prominence, want_power):
+    """The batch of :class:`StringLength` (``pdc_stringlength_scan_ragged``): every curve scaled as the single call
+    scales it (``_quarter_scaled``) and scanned on exactly the grid ``_string_periods`` gives it."""
+    from .spectral import PeakTable
+    peaks = int(peaks)
+    if peaks < 0 or peaks > 1024:
+        raise ValueError("peaks must be 0 .. 1024")
+    if not want_power and peaks == 0:
+        raise ValueError("nothing requested: want_power=False needs peaks > 0")
+    coerced = []
+    for b, s in enumerate(signals):
+        try:
+            coerced.append(_coerce(s))
+        except IndexError:   # (an empty series has no baseline)
+            raise ValueError(f"curve {b} has no samples: StringLength cannot scale an empty curve") from None
+    signals = coerced
+    if not signals:
+        raise ValueError("StringLength.batch needs at least one signal")
+    count = operator.index(scan.n_periods)
+    if count < 0:
+        raise ValueError(f"Number of samples, {count}, must be non-negative.")
+    values = [np.asarray(s.values, dtype=float) for s in signals]
+    sizes = np.array([v.size for v in values], dtype=np.int64)
+    if (sizes == 0).any():
+        b = int(np.argmax(sizes == 0))
+        raise ValueError(f"curve {b} has no samples: StringLength cannot scale an empty curve")
+    offsets = np.zeros(len(signals) + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum(sizes)
+    x = np.concatenate(values)
+    # _quarter_scaled for every curve at once: np.nanmax / np.nanmin are np.fmax / np.fmin reductions
+    top = np.repeat(np.fmax.reduceat(x, offsets[:-1]), sizes)
+    bottom = np.repeat(np.fmin.reduceat(x, offsets[:-1]), sizes)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        m = (x - top) / (2 * (top - bottom)) + 0.25
+    t = np.concatenate([np.asarray(s.time, dtype=float) for s in signals])
+    baselines = np.array([s.baseline for s in signals], dtype=np.float64)
+    start, step, stop = _string_grid(baselines, scan.dphi, count)
+    if peaks:
+        ok = (count <= 1) | (np.isfinite(stop) & (stop > 0))
+        if not ok.all():
+            b = int(np.flatnonzero(~ok)[0])
+            raise ValueError(f"curve {b}: a peak table needs a frequency step dphi / baseline that is finite and "
+                             f"positive (got {stop[b]!r})")
+    p_offsets = np.arange(len(signals) + 1, dtype=np.int64) * count
+    devices = scan.devices if scan.devices else None
+    out, table = _cabi.stringlength_scan_ragged(t, m, offsets, start, step, stop, p_offsets, k=peaks,
+                                                by_prominence=by_prominence, want_power=want_power,
+                                                device=scan.device, devices=devices)
+    res = StringLengthBatch(start, step, stop, p_offsets, out, None)
+    if table is not None:
+        res.peaks = PeakTable(None, table, by_prominence, frequency_at=res._frequency_at)
+    return res
 
 
 _KINDS = {"pdm": 0, "aov": 1, "ce": 2}
@@ -286,6 +376,16 @@ class StringLength(object):
                                           devices=self.devices)
         self.periodogram = FSeries(1 / periods, lengths)
         return self.periodogram
+
+    def batch(self, signals, *, peaks=0, by_prominence=False, want_power=True):
+        return _string_batch(self, signals, peaks, by_prominence, want_power)
+
+    batch.__doc__ = _BATCH_DOC.format(cls="StringLength", find="find_dips",
+                                      what="deepest (``find_dips``) minima").replace(
+        "``_pdm_periods`` per curve", "``_string_periods`` per curve").replace(
+        "``pdc_phase_scan_ragged`` / ``pdc_phase_ragged_peaks``",
+        "``pdc_stringlength_scan_ragged`` / ``pdc_stringlength_ragged_peaks``").replace(
+        ":class:`PhaseBatch`", ":class:`StringLengthBatch`")
 
 
 class PDM(object):
