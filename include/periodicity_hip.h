@@ -577,6 +577,11 @@ int64_t pdc_supersmoother_work_bytes(int64_t n, int64_t n_periods);
 int pdc_supersmoother_scan_dev(int device, void *stream, const double *d_t, const double *d_y, int64_t n,
                                const double *d_periods, int64_t n_periods, double alpha, double *d_stat, void *work,
                                int64_t work_bytes);
+/* TEST HOOK (not for callers): the launch shape the device entry takes for (n, n_periods) under PDC_WORK_BUDGET_GB and
+ * the PDC_SS_* switches; out[10] = periods per batch, per sub-batch of the tiled smoother (0: not tiled), segments of
+ * the first two / last two sweeps, workgroups of the generic smoother / of the fallback sort, tiled, streamed sort,
+ * LDS sort, workspace bytes.  No device is touched. */
+int pdc_test_ss_shape(int64_t n, int64_t n_periods, int64_t *out);
 
 #ifdef __cplusplus
 }

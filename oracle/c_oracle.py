@@ -105,6 +105,25 @@ def stringlength_scan(t, m, periods):
     return out
 
 
+def ss_smooth(x, y, span, vsmlsq, cv):
+    """``scan_oracle.ss_smooth`` in C (``oracle_ss_smooth``): ``(smo, acvr)`` of one running-lines smooth."""
+    x, y = _f(x), _f(y)
+    smo, acvr = np.empty(x.size), np.zeros(x.size)
+    rc = lib().oracle_ss_smooth(_p(x), _p(y), C.c_int64(x.size), C.c_double(span), C.c_double(vsmlsq), C.c_int(bool(cv)),
+                                _p(smo), _p(acvr))
+    if rc:
+        raise ValueError("supersmoother: too few samples for the span")
+    return smo, acvr
+
+
+def supersmoother_scan(t, y, periods, alpha=0.0):
+    """``scan_oracle.supersmoother_scan`` in C, OpenMP over the periods: the checker for whole period grids."""
+    t, y, p = _f(t), _f(y), _f(periods)
+    out = np.empty(p.size)
+    lib().oracle_supersmoother_scan(_p(t), _p(y), C.c_int64(t.size), _p(p), C.c_int64(p.size), C.c_double(alpha), _p(out))
+    return out
+
+
 def gls_power_exact(t, values, err, frequency, fit_mean=True, psd=False):
     """Reference prologue/epilogue (numpy restatement) around the C long-double sums."""
     from . import scan_oracle as so

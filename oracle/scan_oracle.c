@@ -372,3 +372,215 @@ void oracle_gl_scan(const double *t, int64_t n, const double *periods, int64_t n
         free(counts); free(terms);
     }
 }
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Supersmoother period search (scan_oracle.py: ss_smooth / supersmoother / supersmoother_stat; Friedman 1984
+ * `supsmu` + `smooth`, periodic, unit weights; Reimann 1994) - the numpy oracle restated operation by operation in
+ * the same 80-bit type, for whole period grids: 0.4 s a period at 5e4 samples in numpy, one thread.  The reference
+ * has no Supersmoother.  Pinned to the numpy form in tests/test_oracle_golden.py.
+ * ---------------------------------------------------------------------------------------------------------- */
+static const double kSsSpans[3] = {0.05, 0.2, 0.5};
+
+/* numpy's add.reduce over a contiguous double array (pairwise, blocks of 128, eight partial sums): the sums of
+ * ss_average_ties and the final mean are taken with it, so that long tied runs round as they do there. */
+static double np_pairwise_sum(const double *a, int64_t n) {
+    if (n < 8) {
+        double res = 0.0;
+        for (int64_t i = 0; i < n; ++i) res += a[i];
+        return res;
+    }
+    if (n <= 128) {
+        double r[8];
+        int64_t i;
+        for (int k = 0; k < 8; ++k) r[k] = a[k];
+        for (i = 8; i < n - (n % 8); i += 8)
+            for (int k = 0; k < 8; ++k) r[k] += a[i + k];
+        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; ++i) res += a[i];
+        return res;
+    }
+    int64_t n2 = n / 2;
+    n2 -= n2 % 8;
+    return np_pairwise_sum(a, n2) + np_pairwise_sum(a + n2, n - n2);
+}
+
+static int64_t ss_half_width(int64_t n, double span) {
+    const int64_t ibw = (int64_t)(0.5 * span * (double)n + 0.5);
+    return ibw > 2 ? ibw : 2;
+}
+
+/* `smooth`, label 90-110 */
+static void ss_average_ties(const double *x, double *smo, int64_t n) {
+    int64_t j = 0;
+    while (j < n) {
+        const int64_t j0 = j;
+        while (j + 1 < n && x[j + 1] <= x[j]) ++j;
+        if (j > j0) {
+            const double mean = np_pairwise_sum(smo + j0, j - j0 + 1) / (double)(j - j0 + 1);
+            for (int64_t i = j0; i <= j; ++i) smo[i] = mean;
+        }
+        ++j;
+    }
+}
+
+typedef struct {
+    long double *xc, *cx, *cxx, *cy, *cxy; /* n, then four prefix arrays of n + 1 */
+} ss_work;
+
+static int ss_work_alloc(ss_work *w, int64_t n) {
+    const size_t m = (size_t)(n > 0 ? n : 1) + 1;
+    w->xc = (long double *)malloc(sizeof(long double) * m * 5);
+    if (!w->xc) return 0;
+    w->cx = w->xc + m;
+    w->cxx = w->cx + m;
+    w->cy = w->cxx + m;
+    w->cxy = w->cy + m;
+    return 1;
+}
+
+/* abscissae relative to x[n / 2] and their two prefix sums: the same for every smooth of one folded curve */
+static void ss_prefix_x(ss_work *w, const double *x, int64_t n) {
+    w->cx[0] = w->cxx[0] = 0.0L;
+    for (int64_t i = 0; i < n; ++i) {
+        w->xc[i] = (long double)(x[i] - x[n / 2]);
+        w->cx[i + 1] = w->cx[i] + w->xc[i];
+        w->cxx[i + 1] = w->cxx[i] + w->xc[i] * w->xc[i];
+    }
+}
+
+/* scan_oracle.ss_smooth, statement by statement; `smo` and `acvr` must not alias `y` */
+static void ss_smooth_core(ss_work *w, const double *x, const double *y, int64_t n, double span, double vsmlsq, int cv,
+                           double *smo, double *acvr) {
+    const int64_t ibw = ss_half_width(n, span);
+    const long double *xc = w->xc, *cx = w->cx, *cxx = w->cxx;
+    long double *cy = w->cy, *cxy = w->cxy;
+    cy[0] = cxy[0] = 0.0L;
+    for (int64_t i = 0; i < n; ++i) {
+        const long double yl = (long double)y[i];
+        cy[i + 1] = cy[i] + yl;
+        cxy[i + 1] = cxy[i] + xc[i] * yl;
+    }
+    const long double fbw = (long double)(2 * ibw + 1), v = (long double)vsmlsq;
+    for (int64_t j = 0; j < n; ++j) {
+        const int64_t lo = j - ibw, hi = j + ibw + 1;
+        const int low = lo < 0, high = hi > n;
+        const int64_t wl = low ? n + lo : 0, wh = low ? n : (high ? hi - n : 0);
+        const long double sh = low ? -1.0L : (high ? 1.0L : 0.0L), cw = (long double)(wh - wl);
+        const int64_t lo_c = lo > 0 ? lo : 0, hi_c = hi < n ? hi : n;
+        const long double mx = cx[hi_c] - cx[lo_c], ux = cx[wh] - cx[wl];
+        const long double mxx = cxx[hi_c] - cxx[lo_c], uxx = cxx[wh] - cxx[wl];
+        const long double my = cy[hi_c] - cy[lo_c], uy = cy[wh] - cy[wl];
+        const long double mxy = cxy[hi_c] - cxy[lo_c], uxy = cxy[wh] - cxy[wl];
+        const long double sx = mx + (ux + sh * cw), sxx = mxx + (uxx + 2.0L * sh * ux + cw);
+        const long double sy = my + uy, sxy = mxy + (uxy + sh * uy);
+        const long double xm = sx / fbw, ym = sy / fbw;
+        const long double var = sxx - fbw * xm * xm, cvar = sxy - fbw * xm * ym;
+        const long double a = var > v ? cvar / var : 0.0L;
+        const long double s = a * (xc[j] - xm) + ym;
+        smo[j] = (double)s;
+        if (cv) {
+            const long double d = xc[j] - xm;
+            const long double h = 1.0L / fbw + (var > v ? d * d / var : 0.0L);
+            const long double a1 = 1.0L - h;
+            if (a1 > 0.0L)
+                acvr[j] = (double)(fabsl((long double)y[j] - s) / a1);
+            else
+                acvr[j] = j > 0 ? acvr[j - 1] : 0.0; /* `smooth`, label 70: carried over from the point before */
+        } else if (acvr) {
+            acvr[j] = 0.0;
+        }
+    }
+    ss_average_ties(x, smo, n);
+}
+
+/* returns 0, or -1 when the window of 2 ibw + 1 points does not fit (scan_oracle.ss_smooth raises) */
+int oracle_ss_smooth(const double *x, const double *y, int64_t n, double span, double vsmlsq, int cv, double *smo,
+                     double *acvr) {
+    if (n < 1 || 2 * ss_half_width(n, span) + 1 > n) return -1;
+    ss_work w;
+    if (!ss_work_alloc(&w, n)) return -2;
+    ss_prefix_x(&w, x, n);
+    ss_smooth_core(&w, x, y, n, span, vsmlsq, cv, smo, acvr);
+    free(w.xc);
+    return 0;
+}
+
+/* scan_oracle.supersmoother on a sorted folded curve; buf holds 9 arrays of n doubles; the fit lands in buf[0 .. n) */
+static void ss_supsmu(ss_work *w, const double *x, const double *y, int64_t n, double alpha, double *buf) {
+    double *out = buf, *sm[3] = {buf + n, buf + 2 * n, buf + 3 * n}, *res[3] = {buf + 4 * n, buf + 5 * n, buf + 6 * n};
+    double *acvr = buf + 7 * n, *tmp = buf + 8 * n;
+    int64_t i = n / 4, j = 3 * (n / 4); /* 1-based in the Fortran: x(i), x(j) */
+    double scale = x[j - 1] - x[(i > 1 ? i : 1) - 1];
+    while (scale <= 0.0) { /* `supsmu`, label 30 */
+        if (j < n) ++j;
+        if (i > 1) --i;
+        if (j >= n && i <= 1) break;
+        scale = x[j - 1] - x[i - 1];
+    }
+    const double e = 1.0e-3 * scale, vsmlsq = e * e;
+    ss_prefix_x(w, x, n);
+    for (int k = 0; k < 3; ++k) {
+        ss_smooth_core(w, x, y, n, kSsSpans[k], vsmlsq, 1, sm[k], acvr);
+        ss_smooth_core(w, x, acvr, n, kSsSpans[1], vsmlsq, 0, res[k], NULL);
+    }
+    const int bass = alpha > 0.0 && alpha <= 10.0;
+    for (int64_t q = 0; q < n; ++q) {
+        int best = 0; /* first minimum: `if (sc(j,2i) < resmin)` */
+        for (int k = 1; k < 3; ++k)
+            if (res[k][q] < res[best][q]) best = k;
+        const double resmin = res[best][q];
+        double span = kSsSpans[best];
+        if (bass && resmin < res[2][q] && resmin > 0.0) { /* R's guard: see scan_oracle.supersmoother */
+            double ratio = resmin / res[2][q];
+            if (ratio < 1.0e-7) ratio = 1.0e-7;
+            span = span + (kSsSpans[2] - span) * pow(ratio, 10.0 - alpha);
+        }
+        tmp[q] = span;
+    }
+    ss_smooth_core(w, x, tmp, n, kSsSpans[1], vsmlsq, 0, acvr, NULL); /* acvr: the smoothed spans */
+    for (int64_t q = 0; q < n; ++q) {
+        double s = acvr[q];
+        s = s < kSsSpans[0] ? kSsSpans[0] : (s > kSsSpans[2] ? kSsSpans[2] : s);
+        const double f = s - kSsSpans[1];
+        if (f >= 0.0) {
+            const double fu = f / (kSsSpans[2] - kSsSpans[1]);
+            tmp[q] = (1.0 - fu) * sm[1][q] + fu * sm[2][q];
+        } else {
+            const double fd = -f / (kSsSpans[1] - kSsSpans[0]);
+            tmp[q] = (1.0 - fd) * sm[1][q] + fd * sm[0][q];
+        }
+    }
+    ss_smooth_core(w, x, tmp, n, kSsSpans[0], vsmlsq, 0, out, NULL);
+}
+
+/* scan_oracle.supersmoother_scan: fold and stable sort as for StringLength, `supsmu`, mean absolute residual.
+ * n < 5 (no room for the woofer window) gives NaN. */
+void oracle_supersmoother_scan(const double *t, const double *y, int64_t n, const double *periods, int64_t n_periods,
+                               double alpha, double *out) {
+    if (n < 5) {
+        for (int64_t p = 0; p < n_periods; ++p) out[p] = NAN;
+        return;
+    }
+#pragma omp parallel
+    {
+        sl_item *it = (sl_item *)malloc(sizeof(sl_item) * (size_t)n);
+        double *xs = (double *)malloc(sizeof(double) * (size_t)n * 11), *ys = xs + n, *buf = ys + n;
+        ss_work w;
+        const int ok = ss_work_alloc(&w, n) && it && xs;
+#pragma omp for schedule(dynamic, 1)
+        for (int64_t p = 0; p < n_periods; ++p) {
+            if (!ok) { out[p] = NAN; continue; }
+            for (int64_t i = 0; i < n; ++i) {
+                it[i].phi = mod1((t[i] - 0.0) / periods[p]);
+                it[i].m = y[i];
+                it[i].idx = i;
+            }
+            qsort(it, (size_t)n, sizeof(sl_item), sl_cmp);
+            for (int64_t i = 0; i < n; ++i) { xs[i] = it[i].phi; ys[i] = it[i].m; }
+            ss_supsmu(&w, xs, ys, n, alpha, buf);
+            for (int64_t i = 0; i < n; ++i) buf[n + i] = fabs(ys[i] - buf[i]);
+            out[p] = np_pairwise_sum(buf + n, n) / (double)n;
+        }
+        free(it); free(xs); free(w.xc);
+    }
+}

@@ -130,6 +130,7 @@ PROTOTYPES = {
     "pdc_supersmoother_scan_multi": (_I, [_VP, _VP, _L, _VP, _L, _D, _VP, _VP, _I]),
     "pdc_supersmoother_work_bytes": (_L, [_L, _L]),
     "pdc_supersmoother_scan_dev": (_I, [_I, _VP, _VP, _VP, _L, _VP, _L, _D, _VP, _VP, _L]),
+    "pdc_test_ss_shape": (_I, [_L, _L, C.POINTER(_L)]),
 }
 
 
@@ -495,7 +496,7 @@ def _topk_outputs(nb, k):
 
 
 def peaks_topk(power, k=1, by_prominence=False, device=None):
-    """The ``k`` (<= 1024; beyond 64 in launches of 64 ranks) highest, or most prominent, ``find_peaks`` maxima of each row of ``power`` with
+    """The ``k`` (<= 1024; beyond 128 in launches of 128 ranks) highest, or most prominent, ``find_peaks`` maxima of each row of ``power`` with
     prominences and half-maximum crossings (``pdc_peaks_topk``); a dict of arrays shaped ``[rows, k]``
     (``count``: ``[rows]``), ranked descending, padded with -1 / NaN."""
     power = np.ascontiguousarray(power, dtype=np.float64)

@@ -3565,6 +3565,17 @@ int pdc_stringlength_scan(const double *t, const double *m, int64_t n, const dou
 // ---- Supersmoother period search (spectral.py:8, a TODO upstream; Friedman 1984 + Reimann 1994) -----------------
 int64_t pdc_supersmoother_work_bytes(int64_t n, int64_t n_periods) { return sorted_scan_work_bytes(5, n, n_periods, kHintLists); }
 
+// TEST HOOK: the launch shape supersmoother_scan_impl takes for (n, n_periods) under PDC_WORK_BUDGET_GB and the PDC_SS_*
+// switches - so a test can tell which batch / sub-batch seams a period grid crosses.  No device involved.
+int pdc_test_ss_shape(int64_t n, int64_t n_periods, int64_t *out) {
+    PDC_REQUIRE(out && n >= 0 && n_periods >= 0, "pdc_test_ss_shape: bad argument");
+    WorkScale ws(work_budget(), [&] { return ss_shape(n, n_periods, true).total; });
+    const SsShape z = ss_shape(n, n_periods, true);
+    const int64_t v[10] = {z.batch, z.tiled ? z.sb : 0, z.seg, z.seg34, z.grid_ss, z.grid_fb, z.tiled, z.streamed, z.fastsort, z.total};
+    for (int i = 0; i < 10; ++i) out[i] = v[i];
+    return PDC_OK;
+}
+
 int pdc_supersmoother_scan_dev(int device, void *stream, const double *d_t, const double *d_y, int64_t n,
                                const double *d_periods, int64_t n_periods, double alpha, double *d_stat, void *work,
                                int64_t work_bytes) {

@@ -104,3 +104,46 @@ def test_dump_outputs_keeps_small_arrays_whole_and_samples_large_ones_the_same_w
     assert got.dtype == idx.dtype == np.float64 and got.nbytes + idx.nbytes <= bench.DUMP_LIMIT_BYTES
     assert np.array_equal(got, big[idx.astype(np.int64)]) and np.all(np.diff(idx) > 0)
     assert np.array_equal(got, np.load(tmp_path / "c" / "power.npy"))
+
+
+def test_ss_oracle_full_grids_put_every_kind_of_period_in_every_batch_and_sub_batch():
+    """tools/ss_oracle_full.py without a GPU: its spec parser, and the grid builder's promise for every spec of the seam
+    test - a period beyond the baseline in each batch, with even sampling a commensurate one in each sub-batch and 40+
+    consecutive commensurate periods inside one batch beyond its first 64 slots; the launch shape is asked of the
+    library's own pdc_test_ss_shape (no device involved)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("ss_oracle_full", os.path.join(ROOT, "tools", "ss_oracle_full.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    from test_supersmoother_gpu import SEAM_SPECS, SWITCH_SPECS
+    assert tool.parse_spec("4097x787e@3") == (4097, 787, "e", 3.0) and tool.parse_spec("300000x203du") == (300000, 203, "du", 0.0)
+    for bad in ("4097", "10x10q", "x5"):
+        try:
+            tool.parse_spec(bad)
+            raise AssertionError(bad)
+        except ValueError:
+            pass
+    for text in [s for specs in SEAM_SPECS.values() for s in specs] + SWITCH_SPECS:
+        n, n_per, flags, _ = tool.parse_spec(text)
+        gt, gy, t, y = tool.make_curve(n, n_per, flags)
+        assert np.all(np.diff(t) >= 0) and sorted(gt) == list(t)
+        periods, kind = tool.build_grid(t, n_per, flags)
+        base = t[-1] - t[0]
+        assert periods.size == n_per and np.all(periods > 0) and np.all((periods > base) == (kind == 1)), text
+        z = tool.shape_of(n, n_per)
+        if text in SWITCH_SPECS:
+            continue
+        assert n_per > z["batch"], (text, z)                           # at least one batch seam
+        assert n_per % z["batch"] != 0 or text == "50000x4096", text   # a partial last batch (the bench shape is whole)
+        if z["sb"]:
+            assert (n_per % z["batch"]) % z["sb"] % 8 != 0 or text == "50000x4096", (text, z)
+        for p0 in range(0, n_per, z["batch"]):
+            assert np.any(kind[p0:p0 + z["batch"]] == 1), (text, p0)
+            for q0 in range(p0, min(p0 + z["batch"], n_per), z["sb"] or z["batch"]):
+                if "e" in flags:
+                    assert np.any(kind[q0:min(q0 + (z["sb"] or z["batch"]), p0 + z["batch"])] == 2), (text, q0)
+        if "e" in flags:
+            lo, hi = tool.STRETCH
+            assert hi - lo >= 40 and np.all(kind[lo:hi] == 2) and lo >= 64 and hi <= z["batch"], (text, z)
+    assert any(tool.shape_of(*tool.parse_spec(s)[:2])["sb"] not in (0, tool.shape_of(*tool.parse_spec(s)[:2])["batch"])
+               for s in SEAM_SPECS["lds_tiled"] + SEAM_SPECS["bench"])      # some spec does cross a sub-batch seam

@@ -404,9 +404,11 @@ def test_gls_shared_time_axis_random(seed=23):
 def test_supersmoother_random_cases(seed=29):
     """The Supersmoother through both smoothers (generic below 4096 samples, tiled above) on random curves: uneven and
     even sampling, duplicated stamps, Julian offsets, periods from a fraction of the cadence to thousands of baselines,
-    the bass control anywhere in [0, 10]."""
+    the bass control anywhere in [0, 10]; 10 to 600 periods a call (600: past a batch of 384 / 256 and several
+    sub-batches of the tiled smoother) against the C oracle, and one case per run against the numpy oracle too."""
     rng = np.random.default_rng(seed)
-    for n in (int(rng.integers(5, 60)), int(rng.integers(60, 4096)), int(rng.integers(4096, 9000)), int(rng.integers(9000, 30000))):
+    for case, n in enumerate((int(rng.integers(5, 60)), int(rng.integers(60, 4096)), int(rng.integers(4096, 9000)),
+                              int(rng.integers(9000, 30000)))):
         even = rng.random() < 0.25
         t = np.arange(float(n)) * 0.1 if even else np.sort(rng.uniform(0, 0.1 * n, n))
         if rng.random() < 0.5:
@@ -415,10 +417,14 @@ def test_supersmoother_random_cases(seed=29):
             t[5:n:7] = t[4:n - 1:7]
         y = np.sin(2 * np.pi * t / 7.3) + 0.3 * rng.standard_normal(n)
         base = max(t[-1] - t[0], 1.0)
-        periods = np.concatenate([rng.uniform(0.05, 40.0, 5), base * rng.uniform(0.3, 3000.0, 3), [10.0, 7.3]])
+        count = int(rng.choice([10, 70, 300, 600]))
+        periods = np.concatenate([rng.uniform(0.05, 40.0, count - 5), base * rng.uniform(0.3, 3000.0, 3), [10.0, 7.3]])
         alpha = float(rng.choice([0.0, rng.uniform(0.1, 10.0)]))
         got = _cabi.supersmoother_scan(t, y, periods, alpha)
-        np.testing.assert_allclose(got, so.supersmoother_scan(t, y, periods, alpha), rtol=1e-9, err_msg=f"n={n} even={even} alpha={alpha}")
+        msg = f"n={n} even={even} alpha={alpha} periods={count}"
+        np.testing.assert_allclose(got, co.supersmoother_scan(t, y, periods, alpha), rtol=1e-9, err_msg=msg)
+        if case == 1:
+            np.testing.assert_allclose(got, so.supersmoother_scan(t, y, periods, alpha), rtol=1e-9, err_msg=msg)
 
 
 def test_bglst_random_cases(seed=31):

@@ -1,6 +1,8 @@
 """Long randomised parity run on a GPU box: the seeded sweeps of tests/test_random_gpu.py with
 fresh seeds.  ``python tools/fuzz_gpu.py --seeds 20 [--start 1000]`` prints one line per failure
-(seed + test) and a summary; exit code 1 if anything failed."""
+(seed + test) and a summary; exit code 1 if anything failed.  The sweeps draw small grids; whole period grids across
+the host drivers' batch seams are the business of tools/sl_oracle_full.py (StringLength) and tools/ss_oracle_full.py
+(Supersmoother), which take their sizes on the command line."""
 import argparse
 import os
 import sys
