@@ -69,6 +69,7 @@ PROTOTYPES = {
     "pdc_gls_work_bytes": (_L, [_L, _L, _L]),
     "pdc_gls_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _L, _L, _I, _D, _D, _L, _L, _I, _I,
                               _VP, _VP, _VP, _VP, _L]),
+    "pdc_test_gls_last_dispatch": (_I, [c_int64_p]),
     "pdc_gls_fft_work_bytes": (_L, [_L, _L]),
     "pdc_gls_scan_fft": (_I, [_VP, _VP, _VP, _L, _D, _D, _L, _I, _I, _VP, _I]),
     "pdc_gls_scan_fft_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _D, _D, _L, _I, _I, _VP, _VP, _L]),
@@ -312,6 +313,21 @@ def gls_bootstrap(t, y, dy, picks, f0, delta, nf, fit_mean=True, psd=False, meth
                                   int(nf), int(bool(fit_mean)), int(bool(psd)), 1 if method == "fft" else 0,
                                   _ptr(amax), _ptr(argmax), _ptr(devs), devs.size))
     return amax, argmax
+
+
+GLS_ROUTES = ("none", "general", "parts", "balanced", "shared", "shared2")
+_GLS_DISPATCH_FIELDS = ("route", "K", "S", "tiles", "parts", "parts_by_xcd", "bal_slots", "wide_prep", "bpad", "groups",
+                        "z_len", "bal_chunks")
+
+
+def gls_last_dispatch():
+    """TEST HOOK (``pdc_test_gls_last_dispatch``): the route the calling thread's last direct-sum GLS scan took and its
+    launch shape, as a dict (``route`` by name, see ``GLS_ROUTES``)."""
+    out = (C.c_int64 * len(_GLS_DISPATCH_FIELDS))()
+    check(lib().pdc_test_gls_last_dispatch(out))
+    rec = dict(zip(_GLS_DISPATCH_FIELDS, (int(v) for v in out)))
+    rec["route"] = GLS_ROUTES[rec["route"]]
+    return rec
 
 
 def gls_scan_multi(t, y, dy, f0, delta, nf, fit_mean=True, psd=False, devices=(0,)):

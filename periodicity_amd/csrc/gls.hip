@@ -1182,6 +1182,14 @@ struct WorkLayout {
     int64_t rec, scal, parts, blk_max, blk_arg, partial, total;
 };
 
+// TEST HOOK (pdc_test_gls_last_dispatch): the route scan_dev took and its launch shape, written on the host just
+// before the launches.  One record per host thread: a thread reads what ITS last scan chose, whatever other threads
+// scan meanwhile.
+enum Route { ROUTE_NONE = 0, ROUTE_GENERAL = 1, ROUTE_PARTS = 2, ROUTE_BALANCED = 3, ROUTE_SHARED = 4, ROUTE_SHARED2 = 5 };
+struct Dispatch {
+    int64_t route, K, S, tiles, parts, parts_by_xcd, bal_slots, wide_prep, bpad, groups, z_len, bal_chunks;
+};
+thread_local Dispatch g_last_dispatch = {};
 
 WorkLayout layout(int64_t n_total, int64_t n_curves, int64_t nf) {
     auto up = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
@@ -1219,6 +1227,9 @@ int scan_dev(int device, hipStream_t st, const double *d_t, const double *d_y, c
     if (nf == 0) return PDC_OK;
     PDC_TRY(use_device(device));
     char *base = static_cast<char *>(work);
+    Dispatch &rec = g_last_dispatch;
+    rec = Dispatch{};
+    rec.parts = 1;
 
     PrepArgs p;
     p.t = d_t;
@@ -1276,6 +1287,11 @@ int scan_dev(int device, hipStream_t st, const double *d_t, const double *d_y, c
                 const int64_t G2 = sa.groups * ((nf + 127) / 128);
                 PDC_REQUIRE(G2 < (int64_t)1 << 31, "gls: grid too large");
                 const dim3 grid2((unsigned)(((G2 + 7) / 8) * 8));
+                rec.route = ROUTE_SHARED2;
+                rec.K = 2;
+                rec.tiles = (nf + 127) / 128;
+                rec.bpad = bpad;
+                rec.groups = sa.groups;
                 if (mode == MODE_FIT_MEAN) {
                     PDC_TRY(allow_dynamic_lds((const void *)gls_shared2_kernel<true>, (int)kSh2Lds));
                     hipLaunchKernelGGL((gls_shared2_kernel<true>), grid2, dim3(kSh2Block), kSh2Lds, st, sa);
@@ -1294,6 +1310,11 @@ int scan_dev(int device, hipStream_t st, const double *d_t, const double *d_y, c
             const int64_t G = sa.groups * sa.tiles;
             PDC_REQUIRE(G < (int64_t)1 << 31, "gls: grid too large");
             const dim3 grid((unsigned)(((G + 7) / 8) * 8));
+            rec.route = ROUTE_SHARED;
+            rec.K = 1;
+            rec.tiles = sa.tiles;
+            rec.bpad = bpad;
+            rec.groups = sa.groups;
             if (mode == MODE_FIT_MEAN) {
                 if (uni) hipLaunchKernelGGL((gls_shared_kernel<true, true>), grid, dim3(kShBlock), 0, st, sa);
                 else hipLaunchKernelGGL((gls_shared_kernel<true, false>), grid, dim3(kShBlock), 0, st, sa);
@@ -1316,6 +1337,7 @@ int scan_dev(int device, hipStream_t st, const double *d_t, const double *d_y, c
         wp.nparts = (int)((n_total + 4 * kBlock - 1) / (4 * kBlock));
         wp.nparts = wp.nparts > kPrepParts ? kPrepParts : wp.nparts;
         wp.part = reinterpret_cast<double *>(base + w.parts);
+        rec.wide_prep = 1;
         hipLaunchKernelGGL(gls_prep_wide_a, dim3(wp.nparts), dim3(kBlock), 0, st, wp);
         hipLaunchKernelGGL(gls_prep_wide_b, dim3(wp.nparts), dim3(kBlock), 0, st, wp);
         hipLaunchKernelGGL(gls_prep_wide_c, dim3(1), dim3(kBlock), 0, st, wp);
@@ -1367,6 +1389,13 @@ int scan_dev(int device, hipStream_t st, const double *d_t, const double *d_y, c
             grid.y = (unsigned)parts;
         }
     }
+    rec.route = parts > 1 ? ROUTE_PARTS : ROUTE_GENERAL;
+    rec.K = K;
+    rec.S = S;
+    rec.tiles = a.tiles;
+    rec.parts = parts;
+    rec.parts_by_xcd = a.parts_by_xcd;
+    rec.z_len = a.z_len;
     // Balanced pieces (one long curve on a long grid, K = 16): a workgroup slot holds 4 waves at 2 waves per
     // SIMD, 2 per CU, 512 on the chip, and the tiles rarely fill their last round of slots - C2's 489 tiles
     // leave 23 slots idle for the whole launch, C4's slabs end with a round of 197.  When that costs more than
@@ -1389,6 +1418,9 @@ int scan_dev(int device, hipStream_t st, const double *d_t, const double *d_y, c
             a.bal_tile_freqs = tile_freqs;
             a.partial = reinterpret_cast<double *>(base + w.partial);
             grid = dim3((unsigned)(((w_bal + 7) / 8) * 8));
+            rec.route = ROUTE_BALANCED;
+            rec.bal_slots = w_bal;
+            rec.bal_chunks = nchunks;
             if (mode == MODE_FIT_MEAN) {
                 if (S == 2) hipLaunchKernelGGL((gls_scan_kernel<16, MODE_FIT_MEAN, 2, true>), grid, dim3(kBlock), 0, st, a);
                 else hipLaunchKernelGGL((gls_scan_kernel<16, MODE_FIT_MEAN, 4, true>), grid, dim3(kBlock), 0, st, a);
@@ -1431,6 +1463,15 @@ int scan_dev(int device, hipStream_t st, const double *d_t, const double *d_y, c
 }  // namespace
 
 extern "C" {
+
+int pdc_test_gls_last_dispatch(int64_t *out) {
+    PDC_REQUIRE(out, "pdc_test_gls_last_dispatch: NULL argument");
+    const Dispatch &d = g_last_dispatch;
+    const int64_t v[12] = {d.route, d.K, d.S, d.tiles, d.parts, d.parts_by_xcd, d.bal_slots, d.wide_prep,
+                           d.bpad, d.groups, d.z_len, d.bal_chunks};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return PDC_OK;
+}
 
 int64_t pdc_gls_work_bytes(int64_t n_total, int64_t n_curves, int64_t nf) {
     if (n_total < 0 || n_curves < 1 || nf < 0) return -1;
