@@ -203,6 +203,22 @@ int pdc_bglst_scan_dev(int device, void *stream, const double *d_t, const double
                        double f0, double delta, int64_t j_begin, int64_t nf, const double *scalars,
                        double *d_loglik, void *work, int64_t work_bytes);
 
+/* ---- multi-harmonic generalised Lomb-Scargle (Schwarzenberg-Czerny 1996, ApJ 460, L107; Palmer 2009, ApJ 695, 496) -----
+ * The reference has no such class - PARITY UNPINNED BY THE REFERENCE.  Per trial frequency f_j = f0 + (j_begin + j) delta
+ * the weighted least-squares fit of a Fourier series of `nterms` (1 .. 4) harmonics, theta_i = 2 pi f (t_i - t_0):
+ * design columns cos(h theta), sin(h theta), h = 1 .. nterms, and a constant when fit_mean; weights, centring of y
+ * (fit_mean) and the grid rule as pdc_gls_scan.  With M = Phi^T diag(w) Phi, b = Phi^T diag(w) y, YY = sum w y^2:
+ *     power_out[j] = b^T M^-1 b / YY        (psd: b^T M^-1 b * 0.5 * sum dy^-2),
+ * for nterms = 1 the GLS power.  A bin whose M is not positive definite to rounding (a Cholesky pivot that is not > 0
+ * or not finite) is NaN.  n must be at least the number of columns + 1; delta finite and > 0.  dy == NULL: unit
+ * uncertainties.  The `_dev` form enqueues on `stream` and keeps its own workspace per (device, stream). */
+int pdc_mhgls_scan(const double *t, const double *y, const double *dy, int64_t n,
+                   double f0, double delta, int64_t j_begin, int64_t nf, int nterms, int fit_mean, int psd,
+                   double *power_out, int device);
+int pdc_mhgls_scan_dev(int device, void *stream, const double *d_t, const double *d_y, const double *d_dy, int64_t n,
+                       double f0, double delta, int64_t j_begin, int64_t nf, int nterms, int fit_mean, int psd,
+                       double *d_power);
+
 /* Device-resident form used by bench.py: inputs already in HBM, no synchronisation.
  * `work` is scratch of at least pdc_gls_work_bytes(n_total, n_curves, nf) bytes on the same
  * device (non-decreasing in n_total and in nf: a buffer sized for the largest call serves all; for a

@@ -46,6 +46,8 @@ PROTOTYPES = {
     "pdc_clock_probe": (_I, [_I, _VP, _I, C.POINTER(C.c_float), C.POINTER(_D), C.POINTER(_D)]),
     "pdc_bglst_scan": (_I, [_VP, _VP, _VP, _L, _D, _D, _L, _L, _VP, _VP, _I]),
     "pdc_bglst_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _D, _D, _L, _L, _VP, _VP, _VP, _L]),
+    "pdc_mhgls_scan": (_I, [_VP, _VP, _VP, _L, _D, _D, _L, _L, _I, _I, _I, _VP, _I]),
+    "pdc_mhgls_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _D, _D, _L, _L, _I, _I, _I, _VP]),
     "pdc_gls_scan": (_I, [_VP, _VP, _VP, _L, _D, _D, _L, _L, _I, _I, _VP, _I]),
     "pdc_gls_scan_batch": (_I, [_VP, _VP, _VP, _VP, _L, _I, _D, _D, _L, _L, _I, _I,
                                 _VP, _VP, _VP, _I]),
@@ -257,6 +259,20 @@ def bglst_scan(t, y, dy, f0, delta, nf, scalars, j_begin=0, device=None):
     out = np.empty(nf, dtype=np.float64)
     dev = default_device() if device is None else device
     check(lib().pdc_bglst_scan(_ptr(t), _ptr(y), _ptr(dy), t.size, f0, delta, j_begin, nf, _ptr(scalars), _ptr(out), dev))
+    return out
+
+
+def mhgls_scan(t, y, dy, f0, delta, nf, nterms=2, fit_mean=True, psd=False, j_begin=0, device=None):
+    """Multi-harmonic GLS power per trial frequency (``pdc_mhgls_scan``): the weighted least-squares fit of a
+    Fourier series of ``nterms`` harmonics, with a floating mean when ``fit_mean``."""
+    t, y = _f64(t, "t"), _f64(y, "y")
+    dy = None if dy is None else _f64(dy, "dy")
+    if y.size != t.size or (dy is not None and dy.size != t.size):
+        raise ValueError("Input arrays have incompatible lengths.")
+    out = np.empty(nf, dtype=np.float64)
+    dev = default_device() if device is None else device
+    check(lib().pdc_mhgls_scan(_ptr(t), _ptr(y), _ptr(dy), t.size, f0, delta, j_begin, nf, int(nterms),
+                               int(bool(fit_mean)), int(bool(psd)), _ptr(out), dev))
     return out
 
 

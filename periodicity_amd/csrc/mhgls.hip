@@ -1,0 +1,446 @@
+// Multi-harmonic generalised Lomb-Scargle (Schwarzenberg-Czerny 1996; Palmer 2009; the `nterms` of other packages) as
+// an exact direct summation on gfx950: per trial frequency the weighted least-squares fit of a Fourier series of H
+// harmonics (plus a floating mean), power = b^T M^-1 b / YY.
+//
+// The reference (/root/reference/src/periodicity/spectral.py) has no such class: PARITY UNPINNED BY THE REFERENCE.
+// The weights, the centring and the two normalisations are those of GLS (spectral.py:99-108, 129-132).
+//
+// Decomposition
+//   mhgls_prep_kernel   one workgroup: weights, weighted mean, YY, and one 48-byte record per sample
+//                       {w y, w, cos(2 pi delta t'), sin(2 pi delta t'), 2 cos(2 pi delta t'), t' = t - t0}.
+//   mhgls_scan_kernel   the skeleton of gls_scan_kernel (gls.hip): each thread owns K consecutive frequencies, the
+//                       records come through the scalar cache, the seed of a (sample, thread) is one plane rotation of
+//                       two LDS table entries built per 64-sample chunk from exact cycle reductions, and a rotation
+//                       plus the three-term recurrence walk the K frequencies.  (sin, cos) are carried UNscaled here:
+//                       harmonics 2 .. 2H of every (sample, frequency) follow from them by the Chebyshev recurrence
+//                       x[m+1] = 2 cos(theta) x[m] - x[m-1], and 6H running sums per frequency take one fma each:
+//                       C_m = sum w cos(m theta), S_m = sum w sin(m theta), m = 1 .. 2H; YC_h = sum w y cos(h theta),
+//                       YS_h = sum w y sin(h theta), h = 1 .. H.  The product-to-sum rules turn them into M and b, and
+//                       an unrolled Cholesky in registers is the epilogue: only power[nf] is written.
+//
+// One workgroup per tile of 256 K frequencies streams the whole curve (as the MODE_TREND instances of gls.hip do); no
+// sample parts, no balanced pieces, one device.
+#include "pdc_internal.h"
+
+#include <cmath>
+
+using namespace pdc;
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kPrepBlock = 1024;
+constexpr int kChunk = 64;   // samples per rotation-table chunk
+constexpr int kMaxTerms = 4;
+
+struct MhPrepArgs {
+    const double *t, *y, *dy;
+    int64_t n;
+    int fit_mean;
+    double delta;
+    double *rec;    // [n + 2][6] (the scan reads one record ahead)
+    double *scal;   // {YY, sum w, sum err^-2, sum w y}
+};
+
+struct MhArgs {
+    const double *rec, *scal;
+    int64_t n, tiles;
+    double f0, delta;
+    int64_t j_begin, nf;
+    int fit_mean, psd;
+    double *power;
+};
+
+// ---- prologue: weights, centring and YY as GLS takes them (spectral.py:99-108, 120) ---------------------------------
+__global__ __launch_bounds__(kPrepBlock) void mhgls_prep_kernel(MhPrepArgs a) {
+    __shared__ double red[kPrepBlock / 64];
+    const int tid = threadIdx.x;
+    const double t0 = a.n > 0 ? a.t[0] : 0.0;
+    double acc = 0.0;
+    for (int64_t i = tid; i < a.n; i += kPrepBlock) {
+        const double e = a.dy ? a.dy[i] : 1.0;
+        acc += 1.0 / (e * e);
+    }
+    const double W = block_sum<kPrepBlock>(acc, red);
+    double ybar = 0.0;
+    if (a.fit_mean) {
+        acc = 0.0;
+        for (int64_t i = tid; i < a.n; i += kPrepBlock) {
+            const double e = a.dy ? a.dy[i] : 1.0;
+            acc += (1.0 / (e * e)) / W * a.y[i];
+        }
+        ybar = block_sum<kPrepBlock>(acc, red);
+    }
+    double yy = 0.0, wsum = 0.0, y1 = 0.0;
+    for (int64_t i = tid; i < a.n + 2; i += kPrepBlock) {
+        double2 *r = reinterpret_cast<double2 *>(a.rec + i * 6);
+        if (i >= a.n) {   // the read-ahead records: finite, never accumulated
+            r[0] = r[1] = r[2] = make_double2(0.0, 0.0);
+            continue;
+        }
+        const double tp = a.t[i] - t0;
+        const double e = a.dy ? a.dy[i] : 1.0;
+        const double w = (1.0 / (e * e)) / W;
+        const double yc = a.y[i] - ybar;
+        const double wy = w * yc;
+        yy += wy * yc;
+        wsum += w;
+        y1 += wy;
+        double sd, cd;
+        sincos_cycles(frac_product(a.delta, tp), sd, cd);
+        r[0] = make_double2(wy, w);
+        r[1] = make_double2(cd, sd);
+        r[2] = make_double2(cd + cd, tp);
+    }
+    yy = block_sum<kPrepBlock>(yy, red);
+    wsum = block_sum<kPrepBlock>(wsum, red);
+    y1 = block_sum<kPrepBlock>(y1, red);
+    if (tid == 0) {
+        a.scal[0] = yy;
+        a.scal[1] = wsum;
+        a.scal[2] = W;
+        a.scal[3] = y1;
+    }
+}
+
+// ---- epilogue: b^T M^-1 b by an unrolled Cholesky (as bglst_loglik in gls.hip does it for 4 x 4) ----------------------
+// Basis order (cos th, sin th, ..., cos H th, sin H th, 1): the constant comes LAST, so the model without a floating
+// mean is the same factorisation stopped one column early.  Cs[m] = sum w cos(m th), Ss[m] = sum w sin(m th) for
+// m = 0 .. 2H (Cs[0] = sum w, Ss[0] = 0); b = {YC_1, YS_1, ..., YC_H, YS_H, sum w y}.
+// Entry (r, c), r >= c, of M by the product-to-sum rules.
+template <int H>
+__device__ __forceinline__ double mh_entry(const double (&Cs)[2 * H + 1], const double (&Ss)[2 * H + 1], int r, int c) {
+    const int hc = c / 2 + 1;
+    if (r == 2 * H) return c == 2 * H ? Cs[0] : ((c & 1) ? Ss[hc] : Cs[hc]);
+    const int hr = r / 2 + 1;
+    if ((r & 1) == (c & 1)) {
+        const double far = Cs[hr + hc], near = Cs[hr - hc];
+        return (r & 1) ? 0.5 * (near - far) : 0.5 * (near + far);
+    }
+    // sin(hr th) cos(hc th) = (sin((hr + hc) th) + sin((hr - hc) th)) / 2;  cos(hr th) sin(hc th): minus
+    return (r & 1) ? 0.5 * (Ss[hr + hc] + Ss[hr - hc]) : 0.5 * (Ss[hr + hc] - Ss[hr - hc]);
+}
+
+// A pivot that is not > 0, or is not finite, makes the bin NaN (the fit is singular there to rounding).
+template <int H>
+__device__ __forceinline__ double mh_quadratic(const double (&Cs)[2 * H + 1], const double (&Ss)[2 * H + 1],
+                                               const double (&b)[2 * H + 1], int fit_mean) {
+    constexpr int D = 2 * H + 1;
+    double L[D][D], z[D];
+    double quad = 0.0;
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        if (j < D - 1 || fit_mean) {
+            double d = mh_entry<H>(Cs, Ss, j, j);
+#pragma unroll
+            for (int q = 0; q < j; ++q) d -= L[j][q] * L[j][q];
+            bad = bad || !(d > 0.0) || !(d < HUGE_VAL);
+            const double inv = 1.0 / __builtin_sqrt(d);
+            double zj = b[j];
+#pragma unroll
+            for (int q = 0; q < j; ++q) zj -= L[j][q] * z[q];
+            z[j] = zj * inv;
+            quad += z[j] * z[j];
+#pragma unroll
+            for (int i = j + 1; i < D; ++i) {
+                double v = mh_entry<H>(Cs, Ss, i, j);
+#pragma unroll
+                for (int q = 0; q < j; ++q) v -= L[i][q] * L[j][q];
+                L[i][j] = v * inv;
+            }
+        }
+    }
+    return bad ? __builtin_nan("") : quad;
+}
+
+// ---- the scan -----------------------------------------------------------------------------------------------------
+// H = harmonics, K = trial frequencies per thread: 6 H K accumulators (12 H K VGPRs).
+template <int H, int K>
+__global__ __launch_bounds__(kBlock) void mhgls_scan_kernel(MhArgs a) {
+    constexpr int COLS = kBlock / 64;   // 64-lane columns of the tile
+    // per sample: {sin, cos} of theta_tile + 8 q Theta, q < 8 COLS (the seed of lanes 8q .. 8q+7 before their own
+    // offset) | {sin, cos}(b Theta), b < 8
+    __shared__ double2 tab[kChunk + 1][COLS * 8 + 8 + 1];   // + 1: rows start 16 B apart modulo 128 B (bank spread)
+
+    // Workgroup p runs on XCD p % 8 (observed dispatch rule, used for speed only): a contiguous run of tiles per XCD.
+    const int64_t per_xcd = (a.tiles + 7) / 8;
+    const int64_t tile = (int64_t)(blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
+    if (tile >= a.tiles) return;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int col = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t n = a.n;
+    // first local frequency of the tile and of this thread
+    const int64_t jt = tile * kBlock * (int64_t)K;
+    const int64_t jl = jt + (int64_t)tid * K;
+    // numpy's arange fill rule: start + i*delta, two roundings (no fma)
+    const double f_tile = __dadd_rn(a.f0, __dmul_rn((double)(a.j_begin + jt), a.delta));
+    const double kdelta = (double)K * a.delta;   // spacing of the threads' first frequencies (exact)
+
+    double Cm[2 * H][K], Sm[2 * H][K], YC[H][K], YS[H][K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+        for (int m = 0; m < 2 * H; ++m) Cm[m][k] = Sm[m][k] = 0.0;
+#pragma unroll
+        for (int h = 0; h < H; ++h) YC[h][k] = YS[h][k] = 0.0;
+    }
+
+    // plane rotation of {sin, cos} pairs: angle(x) + angle(y)
+    auto rot = [](const double2 x, const double2 y) {
+        return make_double2(__builtin_fma(x.x, y.y, x.y * y.x), __builtin_fma(x.y, y.y, -(x.x * y.x)));
+    };
+    const int slot_a = col * 8 + (lane >> 3), slot_b = COLS * 8 + (lane & 7);
+    for (int64_t base = 0; base < n; base += kChunk) {
+        __syncthreads();   // everyone is done with the previous chunk's tables
+        // ---- per-sample rotation tables (two threads per sample), as in gls_scan_kernel ----------------------------
+        // Thread (col, lane) starts at phase theta_tile + (64 col + 8 a + b) Theta, a = lane / 8, b = lane % 8,
+        // Theta = 2 pi K delta t'.  The even thread of a sample makes {sin, cos}(b Theta) and the tile's base phase,
+        // the odd thread walks that base in steps of 8 Theta.
+        if (tid < 2 * kChunk) {
+            const int il = tid >> 1;
+            // (rows past the end of the curve are never accumulated; they only need finite input)
+            const double tp = base + il < n ? a.rec[(base + il) * 6 + 5] : 0.0;
+            double2 step1, cur = make_double2(0.0, 0.0);
+            if ((tid & 1) == 0) {
+                sincos_cycles(frac_product(kdelta, tp), step1.x, step1.y);
+                tab[il][COLS * 8] = make_double2(0.0, 1.0);
+                tab[il][COLS * 8 + 1] = step1;
+                cur = step1;
+#pragma unroll
+                for (int q = 2; q < 8; ++q) {
+                    cur = rot(cur, step1);
+                    tab[il][COLS * 8 + q] = cur;
+                }
+                sincos_cycles(frac_product(f_tile, tp), cur.x, cur.y);
+            } else {
+                sincos_cycles(frac_product(8.0 * kdelta, tp), step1.x, step1.y);
+            }
+            double2 b0;
+            b0.x = __shfl_xor(cur.x, 1, 64);
+            b0.y = __shfl_xor(cur.y, 1, 64);
+            if (tid & 1) {
+                tab[il][0] = b0;
+#pragma unroll
+                for (int q = 1; q < COLS * 8; ++q) {
+                    b0 = rot(b0, step1);
+                    tab[il][q] = b0;
+                }
+            }
+        }
+        __syncthreads();
+        const int cnt = (int)((n - base) < kChunk ? (n - base) : kChunk);
+        // Software pipeline of gls_scan_kernel: everything sample i+1 needs is requested while sample i is
+        // accumulated, two samples per trip with two register sets that swap roles.  The record fields are
+        // wave-uniform: they come through the scalar cache (constant address space) and feed the fmas as SGPR
+        // operands.  (The read-ahead touches one record past the curve - the prologue wrote it - and the padding row
+        // of the table.)
+        using d4 = double __attribute__((ext_vector_type(4)));
+        using cd4 = __attribute__((address_space(4))) const d4;
+        using cdbl = __attribute__((address_space(4))) const double;
+        const cd4 *srec = reinterpret_cast<const cd4 *>(reinterpret_cast<uintptr_t>(a.rec + base * 6));
+        struct Ahead {
+            d4 r;   // {w y, w, cos, sin (2 pi delta t')}
+            double cd2;
+            double2 qa, qt;
+        };
+        auto fetch = [&](const int i) {
+            Ahead h;
+            h.qa = tab[i][slot_a];
+            h.qt = tab[i][slot_b];
+            const cd4 *rp = reinterpret_cast<const cd4 *>(reinterpret_cast<const cdbl *>(srec) + i * 6);
+            h.r = rp[0];
+            h.cd2 = reinterpret_cast<const cdbl *>(rp)[4];
+            return h;
+        };
+        auto accumulate = [&](const Ahead &h) {
+            const double2 seed = rot(h.qa, h.qt);
+            const double wy = h.r[0], w = h.r[1], cd = h.r[2], sd = h.r[3], cd2 = h.cd2;
+            double s = seed.x, c = seed.y;
+            double sp = 0.0, cp = 0.0;   // previous step of the recurrence over the grid
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                // harmonics of this (sample, frequency): Chebyshev recurrence on the unscaled (sin, cos)
+                const double c2 = c + c;
+                double sm = s, cm = c, sl = 0.0, cl = 1.0;   // harmonic m and m - 1
+#pragma unroll
+                for (int m = 1; m <= 2 * H; ++m) {
+                    Cm[m - 1][k] = __builtin_fma(w, cm, Cm[m - 1][k]);
+                    Sm[m - 1][k] = __builtin_fma(w, sm, Sm[m - 1][k]);
+                    if (m <= H) {
+                        YC[m - 1][k] = __builtin_fma(wy, cm, YC[m - 1][k]);
+                        YS[m - 1][k] = __builtin_fma(wy, sm, YS[m - 1][k]);
+                    }
+                    if (m < 2 * H) {
+                        const double cn = __builtin_fma(c2, cm, -cl), sn = __builtin_fma(c2, sm, -sl);
+                        cl = cm;
+                        sl = sm;
+                        cm = cn;
+                        sm = sn;
+                    }
+                }
+                if (k + 1 < K) {
+                    double sn, cn;
+                    if (k == 0) {
+                        // first grid step: plane rotation by 2 pi delta t'
+                        cn = __builtin_fma(c, cd, -(s * sd));
+                        sn = __builtin_fma(s, cd, c * sd);
+                    } else {
+                        // later steps: x[k+1] = 2 cos(2 pi delta t') x[k] - x[k-1]
+                        cn = __builtin_fma(cd2, c, -cp);
+                        sn = __builtin_fma(cd2, s, -sp);
+                    }
+                    cp = c;
+                    sp = s;
+                    c = cn;
+                    s = sn;
+                }
+            }
+        };
+        Ahead A = fetch(0);
+        int i = 0;
+        for (; i + 1 < cnt; i += 2) {
+            __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): set A has arrived
+            Ahead B = fetch(i + 1);
+            __builtin_amdgcn_sched_barrier(0);
+            accumulate(A);
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_waitcnt(0xc07f);
+            A = fetch(i + 2);
+            __builtin_amdgcn_sched_barrier(0);
+            accumulate(B);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (i < cnt) accumulate(A);
+    }
+
+    const double YY = a.scal[0], Wsum = a.scal[1], Werr = a.scal[2], Y1 = a.scal[3];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int64_t j = jl + k;
+        if (j < a.nf) {
+            double Cs[2 * H + 1], Ss[2 * H + 1], b[2 * H + 1];
+            Cs[0] = Wsum;
+            Ss[0] = 0.0;
+#pragma unroll
+            for (int m = 1; m <= 2 * H; ++m) {
+                Cs[m] = Cm[m - 1][k];
+                Ss[m] = Sm[m - 1][k];
+            }
+#pragma unroll
+            for (int h = 0; h < H; ++h) {
+                b[2 * h] = YC[h][k];
+                b[2 * h + 1] = YS[h][k];
+            }
+            b[2 * H] = Y1;
+            double p = mh_quadratic<H>(Cs, Ss, b, a.fit_mean);
+            // the two normalisations of GLS (gls_epilogue.h)
+            if (a.psd) p *= 0.5 * Werr;
+            else p /= YY;
+            a.power[j] = p;
+        }
+    }
+}
+
+// Frequencies per thread, for every H: the 6 H K running sums are 12 H K registers - 192 at H = 4, the budget of the
+// headline kernel - and a tile is 1024 frequencies whatever H is.
+constexpr int kFreqs = 4;
+
+int64_t mh_work_bytes(int64_t n) { return up256((n + 2) * 48) + 256; }
+
+int mh_validate(const char *what, int64_t n, double delta, int64_t j_begin, int64_t nf, int nterms, int fit_mean) {
+    PDC_REQUIRE(n >= 0 && nf >= 0 && j_begin >= 0, "%s: negative size", what);
+    PDC_REQUIRE(nterms >= 1 && nterms <= kMaxTerms, "%s: nterms must be 1 .. %d (got %d)", what, kMaxTerms, nterms);
+    PDC_REQUIRE(std::isfinite(delta) && delta > 0.0, "%s: the grid step must be finite and positive", what);
+    const int cols = 2 * nterms + (fit_mean ? 1 : 0);
+    PDC_REQUIRE(n >= cols + 1, "%s: %d parameters are fitted, at least %d samples are needed (got %lld)", what, cols,
+                cols + 1, (long long)n);
+    PDC_REQUIRE((nf + kBlock * kFreqs - 1) / (kBlock * kFreqs) < ((int64_t)1 << 31) - 8, "%s: grid too large", what);
+    return PDC_OK;
+}
+
+int mh_enqueue(hipStream_t st, const double *d_t, const double *d_y, const double *d_dy, int64_t n, double f0, double delta,
+               int64_t j_begin, int64_t nf, int nterms, int fit_mean, int psd, double *d_power, void *work) {
+    MhPrepArgs p;
+    p.t = d_t;
+    p.y = d_y;
+    p.dy = d_dy;
+    p.n = n;
+    p.fit_mean = fit_mean;
+    p.delta = delta;
+    p.rec = static_cast<double *>(work);
+    p.scal = reinterpret_cast<double *>(static_cast<char *>(work) + up256((n + 2) * 48));
+    hipLaunchKernelGGL(mhgls_prep_kernel, dim3(1), dim3(kPrepBlock), 0, st, p);
+    PDC_HIP(hipGetLastError());
+    MhArgs a;
+    a.rec = p.rec;
+    a.scal = p.scal;
+    a.n = n;
+    a.tiles = (nf + kBlock * kFreqs - 1) / (kBlock * kFreqs);
+    a.f0 = f0;
+    a.delta = delta;
+    a.j_begin = j_begin;
+    a.nf = nf;
+    a.fit_mean = fit_mean;
+    a.psd = psd;
+    a.power = d_power;
+    const dim3 grid((unsigned)((a.tiles + 7) / 8 * 8));
+    switch (nterms) {
+        case 1: hipLaunchKernelGGL((mhgls_scan_kernel<1, kFreqs>), grid, dim3(kBlock), 0, st, a); break;
+        case 2: hipLaunchKernelGGL((mhgls_scan_kernel<2, kFreqs>), grid, dim3(kBlock), 0, st, a); break;
+        case 3: hipLaunchKernelGGL((mhgls_scan_kernel<3, kFreqs>), grid, dim3(kBlock), 0, st, a); break;
+        default: hipLaunchKernelGGL((mhgls_scan_kernel<4, kFreqs>), grid, dim3(kBlock), 0, st, a); break;
+    }
+    PDC_HIP(hipGetLastError());
+    return PDC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pdc_mhgls_scan_dev(int device, void *stream, const double *d_t, const double *d_y, const double *d_dy, int64_t n,
+                       double f0, double delta, int64_t j_begin, int64_t nf, int nterms, int fit_mean, int psd,
+                       double *d_power) {
+    PDC_REQUIRE(d_t && d_y && (d_power || nf == 0), "mhgls: NULL argument");
+    PDC_TRY(mh_validate("mhgls", n, delta, j_begin, nf, nterms, fit_mean));
+    if (nf == 0) return PDC_OK;
+    PDC_TRY(use_device(device));
+    hipStream_t st = (hipStream_t)stream;
+    void *work = nullptr;
+    PDC_TRY(stream_scratch(device, st, mh_work_bytes(n), &work));
+    ScratchPin pin;
+    pin.device = device;
+    pin.stream = st;
+    pin.held = true;
+    return mh_enqueue(st, d_t, d_y, d_dy, n, f0, delta, j_begin, nf, nterms, fit_mean, psd, d_power, work);
+}
+
+int pdc_mhgls_scan(const double *t, const double *y, const double *dy, int64_t n, double f0, double delta, int64_t j_begin,
+                   int64_t nf, int nterms, int fit_mean, int psd, double *power_out, int device) {
+    PDC_REQUIRE(t && y && (power_out || nf == 0), "mhgls: NULL argument");
+    PDC_TRY(mh_validate("mhgls", n, delta, j_begin, nf, nterms, fit_mean));
+    if (nf == 0) return PDC_OK;
+    PDC_TRY(use_device(device));
+    DeviceLock lock(device);
+    void *d_t, *d_y, *d_dy = nullptr, *d_out, *d_work;
+    PDC_TRY(cached(device, SLOT_IN0, n * 8, &d_t));
+    PDC_TRY(cached(device, SLOT_IN1, n * 8, &d_y));
+    if (dy) PDC_TRY(cached(device, SLOT_IN2, n * 8, &d_dy));
+    PDC_TRY(cached(device, SLOT_OUT0, nf * 8, &d_out));
+    PDC_TRY(cached(device, SLOT_WORK, mh_work_bytes(n), &d_work));
+    hipStream_t st = nullptr;
+    PDC_TRY(host_stream(device, &st));
+    PDC_HIP(hipMemcpyAsync(d_t, t, n * 8, hipMemcpyHostToDevice, st));
+    PDC_HIP(hipMemcpyAsync(d_y, y, n * 8, hipMemcpyHostToDevice, st));
+    if (dy) PDC_HIP(hipMemcpyAsync(d_dy, dy, n * 8, hipMemcpyHostToDevice, st));
+    PDC_TRY(mh_enqueue(st, (double *)d_t, (double *)d_y, (double *)d_dy, n, f0, delta, j_begin, nf, nterms, fit_mean, psd,
+                       (double *)d_out, d_work));
+    PDC_HIP(hipMemcpyAsync(power_out, d_out, nf * 8, hipMemcpyDeviceToHost, st));
+    PDC_HIP(hipStreamSynchronize(st));
+    return PDC_OK;
+}
+
+}  // extern "C"

@@ -19,7 +19,7 @@ import numpy as np
 from . import _cabi
 from .core import FSeries, TSeries
 
-__all__ = ["GLS", "LombScargle", "BGLST", "GLSBatch", "PeakTable"]
+__all__ = ["GLS", "LombScargle", "BGLST", "MultiHarmonicGLS", "GLSBatch", "PeakTable"]
 
 
 def _as_tseries(signal):
@@ -411,3 +411,83 @@ class BGLST(GLS):
 
     def batch(self, *args, **kwargs):
         raise NotImplementedError("BGLST.batch is not implemented: the ragged-grid batch computes GLS power only")
+
+
+class MultiHarmonicGLS(GLS):
+    """Multi-harmonic generalised Lomb-Scargle periodogram: at every trial frequency the weighted least-squares fit
+    of a truncated Fourier series (Schwarzenberg-Czerny 1996, ApJ 460, L107; Palmer 2009, ApJ 695, 496 - what other
+    packages expose as ``nterms``), for variables that are periodic but not sinusoidal (eclipses, RR Lyrae, spots).
+
+    The reference has no such class - **parity unpinned by the reference**.  Grid, weights, centring and the two
+    normalisations are those of ``GLS`` (``spectral.py:88-108,129-132``): with ``theta = 2 pi f (t - t[0])``, design
+    columns ``cos(h theta), sin(h theta)`` for ``h = 1 .. nterms`` plus a constant when ``fit_mean``,
+    ``M = Phi^T diag(w) Phi``, ``b = Phi^T diag(w) y`` and ``YY = sum w y**2``,
+
+        ``power(f) = b^T M^-1 b / YY``   (``psd``: ``b^T M^-1 b * 0.5 * sum err**-2``),
+
+    which for ``nterms=1`` is the GLS power.  At the lowest few frequencies the harmonics are nearly constant over
+    the baseline and ``M`` is close to singular: such a bin is badly conditioned, and NaN where a Cholesky pivot
+    is not positive.  Evaluated by ``csrc/mhgls.hip``; nothing here computes a periodogram on the CPU.
+
+    Parameters
+    ----------
+    fmin, fmax, n, psd: as ``GLS``.
+    nterms: int, keyword-only, optional
+        Harmonics of the model, 1 .. 4 (default 2).
+    device: int, keyword-only, optional
+    """
+
+    MAX_TERMS = 4
+
+    def __init__(self, fmin=None, fmax=None, n=5, psd=False, *, nterms=2, device=None):
+        if isinstance(nterms, bool) or nterms != int(nterms) or not 1 <= int(nterms) <= self.MAX_TERMS:
+            raise ValueError(f"nterms must be an integer 1 .. {self.MAX_TERMS}")
+        super().__init__(fmin, fmax, n, psd, device=device)
+        self.nterms = int(nterms)
+
+    def __call__(self, signal, err=None, fit_mean=True):
+        """``FSeries(frequency, power)`` on the grid of ``GLS``; ``period_at_highest_peak`` etc. as for ``GLS``."""
+        signal = _as_tseries(signal)
+        self.frequency = self._grid(signal)
+        f0, delta, nf = _cabi.grid_params(self.frequency)
+        if nf < 2:   # a grid of one bin has no step of its own; any positive step rebuilds it
+            delta = 1.0
+        have_err = err is not None
+        if not have_err:
+            err = np.ones_like(signal.values)
+        dy = np.asarray(err, dtype=float) if have_err else None
+        t = np.asarray(signal.time, dtype=float)
+        y = np.asarray(signal.values, dtype=float)
+        dev = _cabi.pick_device(self.device, None)
+        power = _cabi.mhgls_scan(t, y, dy, f0, delta, nf, self.nterms, fit_mean, self.psd, device=dev)
+        self.err = err
+        self.fit_mean = bool(fit_mean)
+        self.signal = signal
+        self.periodogram = FSeries(self.frequency, power)
+        return self.periodogram
+
+    def _design(self, times, f0):
+        """Design columns of the last call's model at frequency ``f0``, one row per time."""
+        arg = 2 * np.pi * f0 * (np.asarray(times, dtype=float) - float(self.signal.time[0]))
+        cols = [np.ones_like(arg)] if self.fit_mean else []
+        for h in range(1, self.nterms + 1):
+            cols += [np.cos(h * arg), np.sin(h * arg)]
+        return np.stack(cols, axis=1)
+
+    def model(self, tf, f0):
+        """The fitted Fourier series of the last call (its ``err`` and ``fit_mean``) at frequency ``f0``, evaluated
+        at times ``tf``.  O(N) host arithmetic, not part of the scan."""
+        sigma = np.asarray(self.err, dtype=float)
+        y = np.asarray(self.signal.values, dtype=float)
+        y_mean = np.dot(y, sigma ** -2.0) / np.sum(sigma ** -2.0) if self.fit_mean else 0.0
+        A = self._design(self.signal.time, f0) / sigma[:, None]
+        theta = np.linalg.solve(A.T @ A, A.T @ ((y - y_mean) / sigma))
+        return TSeries(tf, y_mean + self._design(tf, f0) @ theta)
+
+    def bootstrap(self, *args, **kwargs):
+        raise NotImplementedError("MultiHarmonicGLS has no bootstrap yet: the batched replicate kernels compute GLS power only")
+
+    fap = fal = bootstrap
+
+    def batch(self, *args, **kwargs):
+        raise NotImplementedError("MultiHarmonicGLS.batch is not implemented: the ragged-grid batch computes GLS power only")
