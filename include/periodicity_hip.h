@@ -242,6 +242,10 @@ int pdc_gls_scan_dev(int device, void *stream,
  * (0: not balanced), 1 when the grid-wide prologue ran, curves per padded row of the shared weight table, its curve
  * groups, samples per part, 128-sample chunks per tile of the balanced launch. */
 int pdc_test_gls_last_dispatch(int64_t *out);
+/* TEST HOOK (not for callers): whether the CALLING THREAD's last direct-sum scan ran the mirrored-pair kernel (K = 16 in
+ * the two GLS modes; PDC_GLS_PAIR=0 in the environment keeps the plain kernel), per host thread like the record above.
+ * out[2] = 1 when it did (0 otherwise), bytes of the per-sample offset table it read from the workspace. */
+int pdc_test_gls_last_pair(int64_t *out);
 
 /* ---- generalized Lomb-Scargle by the reference's own algorithm ("Tier F") ------
  * Same inputs/outputs as pdc_gls_scan, but the three _trig_sum calls (spectral.py:109-112) are

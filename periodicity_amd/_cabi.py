@@ -72,6 +72,7 @@ PROTOTYPES = {
     "pdc_gls_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _L, _L, _I, _D, _D, _L, _L, _I, _I,
                               _VP, _VP, _VP, _VP, _L]),
     "pdc_test_gls_last_dispatch": (_I, [c_int64_p]),
+    "pdc_test_gls_last_pair": (_I, [c_int64_p]),
     "pdc_gls_fft_work_bytes": (_L, [_L, _L]),
     "pdc_gls_scan_fft": (_I, [_VP, _VP, _VP, _L, _D, _D, _L, _I, _I, _VP, _I]),
     "pdc_gls_scan_fft_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _D, _D, _L, _I, _I, _VP, _VP, _L]),
@@ -344,6 +345,14 @@ def gls_last_dispatch():
     rec = dict(zip(_GLS_DISPATCH_FIELDS, (int(v) for v in out)))
     rec["route"] = GLS_ROUTES[rec["route"]]
     return rec
+
+
+def gls_last_pair():
+    """TEST HOOK (``pdc_test_gls_last_pair``): ``(ran, table_bytes)`` - whether the calling thread's last direct-sum GLS
+    scan ran the mirrored-pair kernel, and the bytes of its per-sample offset table."""
+    out = (C.c_int64 * 2)()
+    check(lib().pdc_test_gls_last_pair(out))
+    return bool(out[0]), int(out[1])
 
 
 def gls_scan_multi(t, y, dy, f0, delta, nf, fit_mean=True, psd=False, devices=(0,)):

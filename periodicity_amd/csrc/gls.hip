@@ -81,6 +81,9 @@ struct GlsArgs {
     // two tiles, a tile falls into at most three runs (`partial` = [3][6][nf]), gls_finish_kernel adds them
     int64_t bal_slots = 0, bal_units = 0, bal_chunks = 0, bal_tile_freqs = 0;
     TrendScalars trend = {};   // MODE_TREND only
+    // mirrored pairs (gls_scan_kernel<..., PAIR = true>): [n_total + 2][8][4] = {cos, sin, cos 2, sin 2}(psi_m),
+    // psi_m = 2 pi (m + 1/2) delta t' (gls_pair_table_kernel)
+    const double *pair_tab = nullptr;
 };
 
 // balanced pieces: run s covers the units [s U / W, (s + 1) U / W); the run that holds unit x
@@ -269,6 +272,35 @@ __global__ __launch_bounds__(kBlock) void gls_prep_wide_c(WidePrepArgs a) {
     }
 }
 
+// ---- mirrored pairs: the per-sample offset table ------------------------------------------------------------
+// A thread of gls_scan_kernel<16, ..., PAIR> owns its sixteen frequencies as a centre (7.5 grid steps above the
+// first) and eight mirrored offsets +-(m + 1/2) delta.  The sine and cosine of the offset angles
+// psi_m = 2 pi (m + 1/2) delta t' and of 2 psi_m depend on the sample and on m only - not on the lane, the tile, the
+// slab or the curve's values - so they are made here, once per call, and reach the scan as scalar operands.
+// One thread per (sample, m); the phase in cycles with the exact product: delta / 2 is exact, (delta / 2) t' is
+// carried as hi + lo, and so is (2 m + 1) hi.  Two zero rows follow the last sample (the scan reads one ahead).
+constexpr int kPairM = 8;                  // mirrored offsets per thread (K / 2)
+constexpr int kPairRow = kPairM * 4;       // doubles per sample
+
+__global__ __launch_bounds__(kBlock) void gls_pair_table_kernel(const double *rec, double *tab, int64_t n_total, double delta) {
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t i = g / kPairM;
+    if (i >= n_total + 2) return;
+    double c = 0.0, s = 0.0, c2 = 0.0, s2 = 0.0;
+    if (i < n_total) {
+        const double tp = rec[i * 6 + 5];
+        const double k = (double)(2 * (int)(g % kPairM) + 1), h = 0.5 * delta;
+        const double hi = h * tp, lo = __builtin_fma(h, tp, -hi);
+        const double p = k * hi, pe = __builtin_fma(k, hi, -p);
+        const double r = (p - __builtin_rint(p)) + __builtin_fma(k, lo, pe);   // |r| <= 1/2 + a few ulp
+        sincos_cycles(r, s, c);
+        sincos_cycles(r + r, s2, c2);
+    }
+    double2 *o = reinterpret_cast<double2 *>(tab + g * 4);
+    o[0] = make_double2(c, s);
+    o[1] = make_double2(c2, s2);
+}
+
 // ---- epilogue: spectral.py:113-132 (gls_epilogue.h); the 2-omega sums come from the double-angle
 // identities sin 2a = 2 sin a cos a, cos 2a = 1 - 2 sin^2 a ------------------------------------------
 template <int MODE>
@@ -325,8 +357,22 @@ __device__ __forceinline__ double bglst_loglik(double Sh, double Ch, double S, d
 // tile and split every staged chunk of samples between them (S = 1, 2 or 4), so that a short grid
 // still puts >= 2 waves on every SIMD; their partial sums are combined through LDS in a fixed
 // order before the epilogue, so results do not depend on timing.
-template <int K, int MODE, int SPLIT, bool BAL = false>
+//
+// PAIR (K = 16, MODE_FIT_MEAN / MODE_NO_MEAN): no recurrence.  The thread's seed a = sqrt(w) sin phi, b = sqrt(w) cos phi
+// is taken at the CENTRE of its sixteen frequencies, and frequency centre +- (m + 1/2) delta has
+//     u+- = a c_m +- b s_m,   v+- = b c_m -+ a s_m        (c_m, s_m: cos, sin psi_m from gls_pair_table_kernel).
+// With A1 = (sqrt(w) y) a, B1 = (sqrt(w) y) b, A2 = sqrt(w) a, B2 = sqrt(w) b, a2 = a a, ab = a b (six products per
+// (sample, thread)) every running sum is ONE fma of a table scalar and one of those products, twelve per two
+// frequencies:
+//     Sh+- = sum A1 c +- sum B1 s      Ch+- = sum B1 c -+ sum A1 s      (S+-, C+- the same with A2, B2)
+//     SS+- = sum a2 c2 + G_m +- sum ab s2,           G_m = sum w s_m^2
+//     SC+- = sum ab c2 +- (F_m / 2 - sum a2 s2),     F_m = sum w s2_m        (both from a^2 + b^2 = w)
+// G_m and F_m do not depend on the thread: the table fill adds each chunk's sixteen values into a workgroup
+// accumulator (fixed order), and they enter when the twelve sums are recombined into the six per frequency after the
+// chunk loop.  From there on - the SPLIT fold, partial sums, epilogue, maxima - nothing differs.
+template <int K, int MODE, int SPLIT, bool BAL = false, bool PAIR = false>
 __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(GlsArgs a) {
+    static_assert(!PAIR || (K == 2 * kPairM && (MODE == MODE_FIT_MEAN || MODE == MODE_NO_MEAN)), "mirrored pairs: K = 16, the two GLS modes");
     constexpr int FT = kBlock / SPLIT;        // frequency-owning threads per workgroup
     constexpr bool TIGHT = BAL || K >= 16;    // 192 accumulators: nothing loop-invariant may stay in registers across the loops (see the table fill)
     constexpr int COLS = FT / 64;             // 64-lane columns of the tile
@@ -337,6 +383,9 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
     __shared__ double red_v[4];
     __shared__ long long red_i[4];
     __shared__ double2 sc_k[6];   // TIGHT: the sincos coefficients of the table fill (pdc_device.h: sincos_cycles_k)
+    // PAIR: {G_m, m < 8 | F_m, m < 8} - a chunk's sixteen stretches of samples, and the sums over the chunks so far
+    __shared__ double gf_red[PAIR ? 16 : 1][16];
+    __shared__ double gf_acc[16];
     const int tid_ = threadIdx.x;
     if (TIGHT && tid_ < 6) sc_k[tid_] = sincos_coefficient(tid_);   // (read after the chunk loop's first barrier)
 
@@ -404,6 +453,13 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
     double TS[K], TC[K];   // MODE_TREND: sum w t' sin, sum w t' cos (dead code in the other instances)
 #pragma unroll
     for (int k = 0; k < K; ++k) Sh[k] = Ch[k] = S[k] = C[k] = SS[k] = SC[k] = TS[k] = TC[k] = 0.0;
+    // PAIR: offset m accumulates in the slots of its two frequencies, k = 8 + m ("P": the cosine-table sums) and
+    // k = 7 - m ("Q": the sine-table sums), which are recombined in place after the chunk loop
+    if (PAIR) {
+        int t16 = tid_;
+        asm volatile("" : "+v"(t16));   // (opaque: the mask is not kept across the loops)
+        if (t16 < 16) gf_acc[t16] = 0.0;   // (touched by this thread alone until the barrier after the chunk loop)
+    }
 
     // plane rotation of {sin, cos} pairs: angle(x) + angle(y)
     auto rot = [](const double2 x, const double2 y) {
@@ -421,6 +477,26 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
         if (TIGHT) asm volatile("" : "+v"(tid));
         const int lane = tid & 63;
         const int slot_a = col * 8 + (lane >> 3), slot_b = COLS * 8 + (lane & 7);
+        if (PAIR) {
+            // this chunk's G_m = sum w s_m^2 and F_m = sum w s2_m: thread (stretch, m16) adds its stretch of kChunk / 16
+            // samples in order; after the barrier sixteen threads add the stretches in order.  (These loads also bring
+            // the chunk's table rows into L2 ahead of the scalar loads of the accumulation loop.)
+            constexpr int SPP = kChunk / 16;
+            const int m16 = tid & 15, seg = tid >> 4;
+            const int64_t i0 = base + seg * SPP;
+            const double *tp_ = a.pair_tab + (off + i0) * kPairRow + (m16 & 7) * 4 + (m16 < 8 ? 1 : 3);
+            const double *rp_ = a.rec + (off + i0) * 6 + 1;
+            double acc = 0.0;
+#pragma unroll
+            for (int q = 0; q < SPP; ++q) {
+                const bool live = i0 + q < s_end;
+                const double sq = live ? rp_[q * 6] : 0.0;
+                const double v = live ? tp_[q * kPairRow] : 0.0;
+                acc = __builtin_fma(sq * sq, m16 < 8 ? v * v : v, acc);
+            }
+            gf_red[seg][m16] = acc;
+            __builtin_amdgcn_sched_barrier(0);   // (done before the fill's own registers are live)
+        }
         // ---- per-sample rotation tables (two threads per sample) ------------------------------------
         // Thread (col, lane) starts at phase theta_tile + (64 col + 8 a + b) Theta with a = lane / 8,
         // b = lane % 8 and Theta = 2 pi K delta t': its seed is tab[8 col + a] rotated by tab[8 COLS + b]
@@ -457,7 +533,14 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
                     cur = rot(cur, step1);
                     tab[il][COLS * 8 + q] = cur;
                 }
-                sincos_fill(frac_product(f_tile, tp), cur.x, cur.y);
+                double r_base = frac_product(f_tile, tp);
+                // PAIR: the base phase is lane 0's centre, f_tile + 7.5 delta = f_tile + 8 delta - delta / 2 (both exact)
+                if (PAIR) {
+                    double dl = a.delta;
+                    asm volatile("" : "+v"(dl));   // (opaque: its multiples are made here, not kept across the loops)
+                    r_base += frac_product(8.0 * dl, tp) - frac_product(0.5 * dl, tp);
+                }
+                sincos_fill(r_base, cur.x, cur.y);
                 if (MODE == MODE_FIT_MEAN || MODE == MODE_NO_MEAN || MODE == MODE_TREND) {
                     // carry u = sqrt(w) sin, v = sqrt(w) cos: rotations and the recurrence are linear,
                     // and every sum becomes one fma (the record holds sqrt(w) and sqrt(w) y)
@@ -484,6 +567,89 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
         const int cnt = (int)((s_end - base) < kChunk ? (s_end - base) : kChunk);
         const int i_end = cnt < (part + 1) * (kChunk / SPLIT) ? cnt : (part + 1) * (kChunk / SPLIT);
         const int i_beg = part * (kChunk / SPLIT);
+        if constexpr (PAIR) {
+            if (tid < 16) {   // the chunk's sixteen remainders, stretches in order
+                double g = gf_red[0][tid];
+#pragma unroll
+                for (int q = 1; q < 16; ++q) g += gf_red[q][tid];
+                gf_acc[tid] += g;
+            }
+            // Scalar pipeline.  A sample's table row is 64 SGPRs, too many to hold twice: it comes in two halves
+            // (m < 4, m >= 4; two s_load_dwordx16 each).  Per sample: wait | request the second half | seed, products
+            // and the 48 fmas of the first half | wait | request the next sample's first half, record and two LDS
+            // entries | the 48 fmas of the second half.  (Reads one row past the stretch: the table carries two
+            // spare rows, the LDS table one.)
+            using d8 = double __attribute__((ext_vector_type(8)));
+            using cd8 = __attribute__((address_space(4))) const d8;
+            using d2 = double __attribute__((ext_vector_type(2)));
+            using cd2 = __attribute__((address_space(4))) const d2;
+            // (wave-uniform addresses and trip count, said so: `off` arrives through a vector load)
+            auto uniform = [](const double *p) {
+                const uintptr_t u = reinterpret_cast<uintptr_t>(p);
+                const uint32_t lo_ = __builtin_amdgcn_readfirstlane((uint32_t)u), hi_ = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
+                return ((uintptr_t)hi_ << 32) | lo_;
+            };
+            const cd8 *stab = reinterpret_cast<const cd8 *>(uniform(a.pair_tab + (off + base) * kPairRow));
+            const cd2 *srec = reinterpret_cast<const cd2 *>(uniform(a.rec + (off + base) * 6));
+            const int i_last = __builtin_amdgcn_readfirstlane(i_end);
+            d8 h0a, h0b, h1a, h1b;   // {c, s, c2, s2} of m = 0, 1 | 2, 3 | 4, 5 | 6, 7
+            d2 r;                    // {sqrt(w) y, sqrt(w)}
+            double2 qa, qt;
+            auto request_first = [&](const int i) {
+                h0a = stab[i * 4];
+                h0b = stab[i * 4 + 1];
+                r = srec[i * 3];
+                qa = tab[i][slot_a];
+                qt = tab[i][slot_b];
+            };
+            double A1, B1, A2, B2, a2, ab;
+            auto pair_fmas = [&](const d8 &h, const int m0) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const int hi = K / 2 + m0 + q, lo = K / 2 - 1 - m0 - q;
+                    const double c = h[4 * q], s = h[4 * q + 1], c2 = h[4 * q + 2], s2 = h[4 * q + 3];
+                    Sh[hi] = __builtin_fma(c, A1, Sh[hi]);
+                    Sh[lo] = __builtin_fma(s, B1, Sh[lo]);
+                    Ch[hi] = __builtin_fma(c, B1, Ch[hi]);
+                    Ch[lo] = __builtin_fma(s, A1, Ch[lo]);
+                    if (mode_sums_w(MODE)) {
+                        S[hi] = __builtin_fma(c, A2, S[hi]);
+                        S[lo] = __builtin_fma(s, B2, S[lo]);
+                        C[hi] = __builtin_fma(c, B2, C[hi]);
+                        C[lo] = __builtin_fma(s, A2, C[lo]);
+                    }
+                    SS[hi] = __builtin_fma(c2, a2, SS[hi]);
+                    SS[lo] = __builtin_fma(s2, ab, SS[lo]);
+                    SC[hi] = __builtin_fma(c2, ab, SC[hi]);
+                    SC[lo] = __builtin_fma(s2, a2, SC[lo]);
+                }
+            };
+            if (i_beg < i_last) {
+                request_first(i_beg);
+                for (int i = i_beg; i < i_last; ++i) {
+                    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the first half, the record and the seed entries
+                    h1a = stab[i * 4 + 2];
+                    h1b = stab[i * 4 + 3];
+                    __builtin_amdgcn_sched_barrier(0);
+                    const double2 seed = rot(qa, qt);
+                    A1 = r[0] * seed.x;
+                    B1 = r[0] * seed.y;
+                    A2 = r[1] * seed.x;
+                    B2 = r[1] * seed.y;
+                    a2 = seed.x * seed.x;
+                    ab = seed.x * seed.y;
+                    pair_fmas(h0a, 0);
+                    pair_fmas(h0b, 2);
+                    __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_s_waitcnt(0xc07f);  // the second half
+                    request_first(i + 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                    pair_fmas(h1a, 4);
+                    pair_fmas(h1b, 6);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        } else {
         // Software pipeline: everything sample i+1 needs is requested while sample i is accumulated;
         // two samples per trip with two register sets (A, B) that swap roles, so the read-ahead costs
         // no register copies.  The record fields are wave-uniform: they come through the scalar
@@ -567,6 +733,45 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
             __builtin_amdgcn_sched_barrier(0);
         }
         if (i < i_end) accumulate(A);
+        }
+    }
+
+    if constexpr (PAIR) {
+        // the twelve sums of offset m -> the six sums of its two frequencies; the sample-only remainders enter once per
+        // tile piece, in the waves whose sums survive the SPLIT fold
+        __syncthreads();   // gf_acc is complete
+        const bool keeps = part == 0;
+#pragma unroll
+        for (int m = 0; m < K / 2; ++m) {
+            const int hi = K / 2 + m, lo = K / 2 - 1 - m;
+            const double G = keeps ? gf_acc[m] : 0.0, Fh = keeps ? 0.5 * gf_acc[8 + m] : 0.0;
+            double p = Sh[hi], q = Sh[lo];
+            Sh[hi] = p + q;
+            Sh[lo] = p - q;
+            p = Ch[hi], q = Ch[lo];
+            Ch[hi] = p - q;
+            Ch[lo] = p + q;
+            if (mode_sums_w(MODE)) {
+                p = S[hi], q = S[lo];
+                S[hi] = p + q;
+                S[lo] = p - q;
+                p = C[hi], q = C[lo];
+                C[hi] = p - q;
+                C[lo] = p + q;
+            }
+            p = SS[hi] + G, q = SS[lo];
+            SS[hi] = p + q;
+            SS[lo] = p - q;
+            p = SC[hi], q = Fh - SC[lo];
+            SC[hi] = p + q;
+            SC[lo] = p - q;
+            // (one offset at a time, here: sunk into the SPLIT fold frequency by frequency, every offset's inputs AND
+            // results stay live across it - 62 to 104 spilled VGPRs)
+            asm volatile("" : "+v"(Sh[hi]), "+v"(Sh[lo]), "+v"(Ch[hi]), "+v"(Ch[lo]), "+v"(SS[hi]), "+v"(SS[lo]), "+v"(SC[hi]), "+v"(SC[lo]));
+            if (mode_sums_w(MODE)) asm volatile("" : "+v"(S[hi]), "+v"(S[lo]), "+v"(C[hi]), "+v"(C[lo]));
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();   // (BAL: before the next piece clears gf_acc)
     }
 
     const int tid = tid_;
@@ -1162,10 +1367,28 @@ void tile_shape(int64_t n_curves, int64_t nf, int64_t n_total, bool may_split, i
 
 template <int MODE, int S>
 void launch_scan_ks(int K, dim3 grid, hipStream_t st, const GlsArgs &a) {
+    if constexpr (MODE == MODE_FIT_MEAN || MODE == MODE_NO_MEAN) {
+        if (K == 16 && a.pair_tab) {
+            hipLaunchKernelGGL((gls_scan_kernel<16, MODE, S, false, true>), grid, dim3(kBlock), 0, st, a);
+            return;
+        }
+    }
     switch (K) {
         case 4: hipLaunchKernelGGL((gls_scan_kernel<4, MODE, S>), grid, dim3(kBlock), 0, st, a); break;
         case 16: hipLaunchKernelGGL((gls_scan_kernel<16, MODE, S>), grid, dim3(kBlock), 0, st, a); break;
         default: hipLaunchKernelGGL((gls_scan_kernel<8, MODE, S>), grid, dim3(kBlock), 0, st, a); break;
+    }
+}
+
+// balanced pieces (K = 16, S = 2 or 4)
+template <int MODE>
+void launch_scan_balanced(int S, dim3 grid, hipStream_t st, const GlsArgs &a) {
+    if (a.pair_tab) {
+        if (S == 2) hipLaunchKernelGGL((gls_scan_kernel<16, MODE, 2, true, true>), grid, dim3(kBlock), 0, st, a);
+        else hipLaunchKernelGGL((gls_scan_kernel<16, MODE, 4, true, true>), grid, dim3(kBlock), 0, st, a);
+    } else {
+        if (S == 2) hipLaunchKernelGGL((gls_scan_kernel<16, MODE, 2, true>), grid, dim3(kBlock), 0, st, a);
+        else hipLaunchKernelGGL((gls_scan_kernel<16, MODE, 4, true>), grid, dim3(kBlock), 0, st, a);
     }
 }
 
@@ -1179,7 +1402,7 @@ void launch_scan(int K, int S, dim3 grid, hipStream_t st, const GlsArgs &a) {
 }
 
 struct WorkLayout {
-    int64_t rec, scal, parts, blk_max, blk_arg, partial, total;
+    int64_t rec, scal, parts, blk_max, blk_arg, partial, pair, total;
 };
 
 // TEST HOOK (pdc_test_gls_last_dispatch): the route scan_dev took and its launch shape, written on the host just
@@ -1190,6 +1413,11 @@ struct Dispatch {
     int64_t route, K, S, tiles, parts, parts_by_xcd, bal_slots, wide_prep, bpad, groups, z_len, bal_chunks;
 };
 thread_local Dispatch g_last_dispatch = {};
+// TEST HOOK (pdc_test_gls_last_pair): whether that scan ran the mirrored-pair kernel, and the bytes of its offset table
+struct PairUse {
+    int64_t ran, table_bytes;
+};
+thread_local PairUse g_last_pair = {};
 
 WorkLayout layout(int64_t n_total, int64_t n_curves, int64_t nf) {
     auto up = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
@@ -1204,7 +1432,8 @@ WorkLayout layout(int64_t n_total, int64_t n_curves, int64_t nf) {
     // (grows with nf: a plan sized for a long grid also serves short ones)
     int64_t cells = kPartsMax * nf < kPartialCells ? kPartsMax * nf : kPartialCells;
     cells = cells > 3 * nf ? cells : 3 * nf;   // balanced pieces: up to three partial sums per frequency
-    w.total = w.partial + (n_curves == 1 ? up(cells * 6 * 8) : 0);
+    w.pair = w.partial + (n_curves == 1 ? up(cells * 6 * 8) : 0);
+    w.total = w.pair + up((n_total + 2) * kPairRow * 8);   // the mirrored-pair offset table + the two rows read ahead
     return w;
 }
 
@@ -1230,6 +1459,7 @@ int scan_dev(int device, hipStream_t st, const double *d_t, const double *d_y, c
     Dispatch &rec = g_last_dispatch;
     rec = Dispatch{};
     rec.parts = 1;
+    g_last_pair = PairUse{};
 
     PrepArgs p;
     p.t = d_t;
@@ -1360,6 +1590,20 @@ int scan_dev(int device, hipStream_t st, const double *d_t, const double *d_y, c
     a.scal = p.scal;
     a.n_total = n_total;
     a.n_curves = n_curves;
+    // Mirrored pairs: wherever K = 16 scans one of the two GLS modes.  PDC_GLS_PAIR=0/1 forces the plain kernel /
+    // states the default (read once per process).
+    static const int env_pair = [] { const char *e = getenv("PDC_GLS_PAIR"); return e ? atoi(e) : -1; }();
+    if (K == 16 && (mode == MODE_FIT_MEAN || mode == MODE_NO_MEAN) && env_pair != 0) {
+        double *tab = reinterpret_cast<double *>(base + w.pair);
+        const int64_t cells = (n_total + 2) * kPairM;
+        PDC_REQUIRE((cells + kBlock - 1) / kBlock < (int64_t)1 << 31, "gls: too many samples for the offset table");
+        hipLaunchKernelGGL(gls_pair_table_kernel, dim3((unsigned)((cells + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                           (const double *)p.rec, tab, n_total, delta);
+        PDC_HIP(hipGetLastError());
+        a.pair_tab = tab;
+        g_last_pair.ran = 1;
+        g_last_pair.table_bytes = (n_total + 2) * kPairRow * 8;
+    }
     const int64_t tile_freqs = (int64_t)(kBlock / S) * K;
     a.tiles = (nf + tile_freqs - 1) / tile_freqs;
     a.f0 = f0;
@@ -1421,13 +1665,8 @@ int scan_dev(int device, hipStream_t st, const double *d_t, const double *d_y, c
             rec.route = ROUTE_BALANCED;
             rec.bal_slots = w_bal;
             rec.bal_chunks = nchunks;
-            if (mode == MODE_FIT_MEAN) {
-                if (S == 2) hipLaunchKernelGGL((gls_scan_kernel<16, MODE_FIT_MEAN, 2, true>), grid, dim3(kBlock), 0, st, a);
-                else hipLaunchKernelGGL((gls_scan_kernel<16, MODE_FIT_MEAN, 4, true>), grid, dim3(kBlock), 0, st, a);
-            } else {
-                if (S == 2) hipLaunchKernelGGL((gls_scan_kernel<16, MODE_NO_MEAN, 2, true>), grid, dim3(kBlock), 0, st, a);
-                else hipLaunchKernelGGL((gls_scan_kernel<16, MODE_NO_MEAN, 4, true>), grid, dim3(kBlock), 0, st, a);
-            }
+            if (mode == MODE_FIT_MEAN) launch_scan_balanced<MODE_FIT_MEAN>(S, grid, st, a);
+            else launch_scan_balanced<MODE_NO_MEAN>(S, grid, st, a);
         }
     }
     if (balanced) {
@@ -1470,6 +1709,13 @@ int pdc_test_gls_last_dispatch(int64_t *out) {
     const int64_t v[12] = {d.route, d.K, d.S, d.tiles, d.parts, d.parts_by_xcd, d.bal_slots, d.wide_prep,
                            d.bpad, d.groups, d.z_len, d.bal_chunks};
     for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return PDC_OK;
+}
+
+int pdc_test_gls_last_pair(int64_t *out) {
+    PDC_REQUIRE(out, "pdc_test_gls_last_pair: NULL argument");
+    out[0] = g_last_pair.ran;
+    out[1] = g_last_pair.table_bytes;
     return PDC_OK;
 }
 
