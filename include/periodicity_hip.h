@@ -219,6 +219,35 @@ int pdc_mhgls_scan_dev(int device, void *stream, const double *d_t, const double
                        double f0, double delta, int64_t j_begin, int64_t nf, int nterms, int fit_mean, int psd,
                        double *d_power);
 
+/* ---- BLS: box least squares (Kovacs, Zucker & Mazeh 2002, A&A 391, 369) ----------------------------------------------
+ * The reference has no such class - PARITY UNPINNED BY THE REFERENCE.  The search for a box-shaped dip (a transit, a
+ * detached eclipse): per trial period the best two-level model of the folded curve.  Weights and centring as
+ * pdc_gls_scan: w = dy^-2 / sum dy^-2 (dy == NULL: unit uncertainties), y' = y - sum w y, YY = sum w y'^2.  Phase
+ * phi = (t / P) % 1 in n_bins bins [k / n_bins, (k + 1) / n_bins) with numpy's membership (the edges are the doubles
+ * k / n_bins, phi == 1.0 joins the last bin).  A box is a start bin i (0 .. n_bins - 1) and a length of L
+ * (len_min .. len_max) bins, wrapping past phase 1, with r = sum w, s = sum w y', c = count over its samples; it is
+ * admissible when c >= min_points, N_binned - c >= min_points and 0 < r < 1 (dips_only: also s < 0).  Per period
+ *     power[j]     = max over admissible boxes of SR / YY,  SR = s^2 / (r (1 - r))   (in [0, 1])
+ *     start_bin[j], box_bins[j] = the maximising (i, L); among equal SR the smaller L, then the smaller i
+ *     depth[j]     = -s / (r (1 - r)) of that box: out-of-box level minus in-box level, positive for a dip.
+ * No admissible box: NaN, NaN, -1, -1.  A non-finite t, y or dy, dy == 0 or YY == 0 anywhere: every output NaN / -1;
+ * a period at which a phase is NaN (0, NaN): NaN / -1 at that period only.  Limits, checked before any device work:
+ * 2 <= n_bins <= 2048, 1 <= len_min <= len_max <= n_bins - 1, min_points >= 1, 0 <= slices <= 1024, n and n_periods
+ * in 0 .. 2^31 - 1.  The sums are 64-bit fixed point (weights scaled by 2^60): exact and independent of order, so
+ * every `slices` gives the same bits; a window sum is within n 2^-61 of the real one on a scale where the total
+ * weight is 1.  slices: workgroups that share the samples of one trial period (1: one workgroup bins and searches; > 1:
+ * through a global histogram of n_periods n_bins 20 bytes in the workspace, an error when that does not fit the
+ * workspace budget); 0 chooses from the shape.  depth, start_bin and box_bins may be NULL.  The `_dev` form takes
+ * device pointers, enqueues on `stream` and keeps its own workspace per (device, stream). */
+int pdc_bls_scan(const double *t, const double *y, const double *dy, int64_t n,
+                 const double *periods, int64_t n_periods, int n_bins, int len_min, int len_max, int min_points,
+                 int dips_only, int slices,
+                 double *power, double *depth, int32_t *start_bin, int32_t *box_bins, int device);
+int pdc_bls_scan_dev(int device, void *stream, const double *d_t, const double *d_y, const double *d_dy, int64_t n,
+                     const double *d_periods, int64_t n_periods, int n_bins, int len_min, int len_max, int min_points,
+                     int dips_only, int slices,
+                     double *d_power, double *d_depth, int32_t *d_start_bin, int32_t *d_box_bins);
+
 /* Device-resident form used by bench.py: inputs already in HBM, no synchronisation.
  * `work` is scratch of at least pdc_gls_work_bytes(n_total, n_curves, nf) bytes on the same
  * device (non-decreasing in n_total and in nf: a buffer sized for the largest call serves all; for a

@@ -48,6 +48,8 @@ PROTOTYPES = {
     "pdc_bglst_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _D, _D, _L, _L, _VP, _VP, _VP, _L]),
     "pdc_mhgls_scan": (_I, [_VP, _VP, _VP, _L, _D, _D, _L, _L, _I, _I, _I, _VP, _I]),
     "pdc_mhgls_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _D, _D, _L, _L, _I, _I, _I, _VP]),
+    "pdc_bls_scan": (_I, [_VP, _VP, _VP, _L, _VP, _L, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _I]),
+    "pdc_bls_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _VP, _L, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "pdc_gls_scan": (_I, [_VP, _VP, _VP, _L, _D, _D, _L, _L, _I, _I, _VP, _I]),
     "pdc_gls_scan_batch": (_I, [_VP, _VP, _VP, _VP, _L, _I, _D, _D, _L, _L, _I, _I,
                                 _VP, _VP, _VP, _I]),
@@ -275,6 +277,23 @@ def mhgls_scan(t, y, dy, f0, delta, nf, nterms=2, fit_mean=True, psd=False, j_be
     check(lib().pdc_mhgls_scan(_ptr(t), _ptr(y), _ptr(dy), t.size, f0, delta, j_begin, nf, int(nterms),
                                int(bool(fit_mean)), int(bool(psd)), _ptr(out), dev))
     return out
+
+
+def bls_scan(t, y, dy, periods, n_bins, len_min, len_max, min_points=5, dips_only=False, slices=0, device=None):
+    """Box least squares at every trial period (``pdc_bls_scan``): ``(power, depth, start_bin, box_bins)`` of the best
+    box of ``len_min .. len_max`` of ``n_bins`` phase bins; ``slices``: workgroups that share one period's samples
+    (0: chosen from the shape; every value gives the same bits)."""
+    t, y, periods = _f64(t, "t"), _f64(y, "y"), _f64(periods, "periods")
+    dy = None if dy is None else _f64(dy, "dy")
+    if y.size != t.size or (dy is not None and dy.size != t.size):
+        raise ValueError("Input arrays have incompatible lengths.")
+    power, depth = np.empty(periods.size, dtype=np.float64), np.empty(periods.size, dtype=np.float64)
+    start, box = np.empty(periods.size, dtype=np.int32), np.empty(periods.size, dtype=np.int32)
+    dev = default_device() if device is None else device
+    check(lib().pdc_bls_scan(_ptr(t), _ptr(y), _ptr(dy), t.size, _ptr(periods), periods.size, int(n_bins), int(len_min),
+                             int(len_max), int(min_points), int(bool(dips_only)), int(slices), _ptr(power), _ptr(depth),
+                             _ptr(start), _ptr(box), dev))
+    return power, depth, start, box
 
 
 def gls_scan_batch(t, y, dy, offsets, f0, delta, nf, fit_mean=True, psd=False, shared_t=False,

@@ -22,7 +22,7 @@ from .core import FSeries, TSeries
 
 MAX_CORES = cpu_count()
 
-__all__ = ["StringLength", "PDM", "AOV", "ConditionalEntropy", "GregoryLoredo", "SuperSmoother", "PhaseBatch",
+__all__ = ["StringLength", "PDM", "AOV", "ConditionalEntropy", "GregoryLoredo", "SuperSmoother", "BLS", "PhaseBatch",
            "StringLengthBatch"]
 
 
@@ -638,4 +638,105 @@ class GregoryLoredo(object):
             terms.append(self.log_s[m] + gammaln(n + 1) + gammaln(m) - gammaln(n + m))
         log_odds = logsumexp(np.array(terms), axis=0) - np.log(self.m_max - 1)
         self.periodogram = FSeries(1 / self.periods, log_odds)
+        return self.periodogram
+
+
+class BLS(object):
+    """Box least squares transit search (Kovacs, Zucker & Mazeh 2002, A&A 391, 369), shaped like :class:`AOV`: the
+    scan for a box-shaped dip - a planetary transit, a detached eclipse - that is flat for most of the phase and low
+    for the rest.  The reference has no such class - **parity unpinned by the reference**.
+
+    Weights and centring are those of ``GLS``: ``w = err**-2 / sum(err**-2)``, ``y' = y - sum(w y)``,
+    ``YY = sum(w y'**2)``.  Per trial period the samples are folded (``(t / P) % 1``, no time origin) into ``n_bins``
+    phase bins; a box is a start bin and a length of ``len_min .. len_max`` bins, wrapping past phase 1, with
+    ``r = sum w``, ``s = sum w y'`` and ``c`` samples inside.  Over the boxes with at least ``min_points`` samples
+    inside and outside (``dips_only``: and ``s < 0``),
+
+        ``power(P) = max s**2 / (r (1 - r)) / YY``,
+
+    the share of the weighted variance the best two-level model removes (in [0, 1], like the normalised GLS power),
+    and ``depth = -s / (r (1 - r))`` is the out-of-box level minus the in-box level of that box.  Evaluated by
+    ``csrc/bls.hip`` in 64-bit fixed point (bit-identical from call to call); nothing here computes a periodogram on
+    the CPU.
+
+    Parameters
+    ----------
+    n_bins: int, optional
+        Phase bins, 2 .. 2048 (the default is 200).
+    q_min, q_max: float, optional
+        Shortest and longest box as a fraction of the period, ``0 < q_min <= q_max < 1`` (defaults 0.01 and 0.1):
+        ``len_min = max(1, floor(q_min n_bins))``, ``len_max = min(n_bins - 1, max(len_min, ceil(q_max n_bins)))``.
+    p_min, p_max, n_periods, oversample, cores:
+        The trial-period grid, exactly as for :class:`PDM` (``phase.py:167-180``).
+    min_points: int, optional
+        Samples a box must have inside and leave outside (the default is 5).
+    dips_only: bool, optional
+        Only boxes below the out-of-box level.
+    device: int, keyword-only
+        GPU ordinal.
+
+    After a call: ``.signal .t .x .err .periods .periodogram`` and, aligned with ``.periods``, ``.power .depth
+    .duration .transit_time`` (mid-box time modulo the period) ``.start_bin .box_bins`` - NaN where a period has no
+    admissible box - and ``.best``, the ``period, power, depth, duration, transit_time`` at the highest power.
+    """
+
+    MAX_BINS = 2048
+
+    def __init__(self, n_bins=200, q_min=0.01, q_max=0.1, p_min=None, p_max=None, n_periods=1000, oversample=1,
+                 min_points=5, dips_only=False, cores=None, *, device=None):
+        self.n_bins = n_bins
+        self.q_min, self.q_max = q_min, q_max
+        self.p_min, self.p_max = p_min, p_max
+        self.n_periods = n_periods
+        self.oversample = oversample
+        self.min_points = min_points
+        self.dips_only = bool(dips_only)
+        self.cores = cores
+        self.device = device
+        self.box_lengths()
+
+    def box_lengths(self):
+        """``(len_min, len_max)`` in bins; raises ``ValueError`` for parameters the scan does not take."""
+        for name in ("n_bins", "min_points"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or v != int(v):
+                raise ValueError(f"{name} must be an integer")
+        if not 2 <= int(self.n_bins) <= self.MAX_BINS:
+            raise ValueError(f"n_bins must be 2 .. {self.MAX_BINS}")
+        if int(self.min_points) < 1:
+            raise ValueError("min_points must be at least 1")
+        if not 0 < self.q_min <= self.q_max < 1:
+            raise ValueError("box fractions need 0 < q_min <= q_max < 1")
+        n_bins = int(self.n_bins)
+        len_min = max(1, int(np.floor(self.q_min * n_bins)))
+        len_max = min(n_bins - 1, max(len_min, int(np.ceil(self.q_max * n_bins))))
+        if not 1 <= len_min <= len_max <= n_bins - 1:
+            raise ValueError("box lengths need 1 <= len_min <= len_max <= n_bins - 1")
+        return len_min, len_max
+
+    def __call__(self, signal, err=None):
+        len_min, len_max = self.box_lengths()
+        signal = _coerce(signal)
+        t = np.asarray(signal.time, dtype=float)
+        x = np.asarray(signal.values, dtype=float)
+        have_err = err is not None
+        err = np.asarray(err, dtype=float) if have_err else np.ones_like(x)
+        if err.shape != x.shape:
+            raise ValueError("Input arrays have incompatible lengths.")
+        periods, _, _ = _pdm_periods(signal, self.p_min, self.p_max, self.n_periods, self.oversample)
+        n_bins = int(self.n_bins)
+        power, depth, start, box = _cabi.bls_scan(t, x, err if have_err else None, periods, n_bins, len_min, len_max,
+                                                  int(self.min_points), self.dips_only, device=self.device)
+        self.signal, self.t, self.x, self.err, self.periods = signal, t, x, err, periods
+        found = start >= 0
+        self.power, self.depth = power, depth
+        self.start_bin = np.where(found, start, np.nan)
+        self.box_bins = np.where(found, box, np.nan)
+        self.duration = self.box_bins / n_bins * periods
+        self.transit_time = ((self.start_bin + self.box_bins / 2) / n_bins % 1) * periods
+        j = int(np.nanargmax(power)) if np.any(~np.isnan(power)) else None
+        self.best = {name: (float("nan") if j is None else float(values[j])) for name, values in
+                     (("period", periods), ("power", power), ("depth", depth), ("duration", self.duration),
+                      ("transit_time", self.transit_time))}
+        self.periodogram = FSeries(1 / periods, power)
         return self.periodogram
