@@ -28,6 +28,7 @@
 //   bls_search          the search both routes share: prefix sums of the extended histogram, the windows dealt to the
 //                       threads, admissibility on the integers, a max-reduction that carries the (L, i) key.
 #include "pdc_internal.h"
+#include "gls_sums.h"
 
 #include <climits>
 #include <cmath>
@@ -108,8 +109,7 @@ __global__ __launch_bounds__(kPrepBlock) void bls_prep_kernel(BlsPrepArgs a) {
     }
     acc = 0.0;
     for (int64_t i = tid; i < a.n; i += kPrepBlock) {
-        const double e = a.dy ? a.dy[i] : 1.0;
-        acc += (1.0 / (e * e)) / W * a.y[i];
+        acc += inv_var(a.dy, i) / W * a.y[i];
     }
     const double ybar = block_sum<kPrepBlock>(acc, red);
     double amax = 0.0;
@@ -120,8 +120,7 @@ __global__ __launch_bounds__(kPrepBlock) void bls_prep_kernel(BlsPrepArgs a) {
     const double A = block_max<kPrepBlock>(amax, red);
     double yy = 0.0;
     for (int64_t i = tid; i < a.n; i += kPrepBlock) {
-        const double e = a.dy ? a.dy[i] : 1.0;
-        const double w = (1.0 / (e * e)) / W;
+        const double w = inv_var(a.dy, i) / W;
         const double yc = a.y[i] - ybar;
         yy += (w * yc) * yc;
         BlsRec r;

@@ -29,6 +29,7 @@
 // cost is the transcendental/rotation work on the vector ALU.
 #include "pdc_internal.h"
 #include "gls_epilogue.h"
+#include "gls_sums.h"
 
 #include <cstdlib>
 
@@ -209,8 +210,7 @@ __global__ __launch_bounds__(kBlock) void gls_prep_wide_a(WidePrepArgs a) {
     double sw = 0.0, swy = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.p.n_total;
          i += (int64_t)gridDim.x * kBlock) {
-        const double e = a.p.dy ? a.p.dy[i] : 1.0;
-        const double wr = 1.0 / (e * e);
+        const double wr = inv_var(a.p.dy, i);
         sw += wr;
         swy += wr * a.p.y[i];
     }
@@ -237,8 +237,7 @@ __global__ __launch_bounds__(kBlock) void gls_prep_wide_b(WidePrepArgs a) {
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.p.n_total;
          i += (int64_t)gridDim.x * kBlock) {
         const double tp = a.p.t[i] - t0;
-        const double e = a.p.dy ? a.p.dy[i] : 1.0;
-        const double w = (1.0 / (e * e)) / W;
+        const double w = inv_var(a.p.dy, i) / W;
         const double yc = a.p.y[i] - ybar;
         const double wy = w * yc;
         yy += wy * yc;
@@ -461,10 +460,6 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
         if (t16 < 16) gf_acc[t16] = 0.0;   // (touched by this thread alone until the barrier after the chunk loop)
     }
 
-    // plane rotation of {sin, cos} pairs: angle(x) + angle(y)
-    auto rot = [](const double2 x, const double2 y) {
-        return make_double2(__builtin_fma(x.x, y.y, x.y * y.x), __builtin_fma(x.y, y.y, -(x.x * y.x)));
-    };
     const int64_t s_begin = BAL ? bal_c0 * kChunk : (a.partial ? (int64_t)zpart * a.z_len : 0);
     const int64_t s_stop = BAL ? s_begin + bal_take * kChunk : s_begin + a.z_len;
     const int64_t s_end = (BAL || a.partial) ? (s_stop < n ? s_stop : n) : n;
@@ -530,7 +525,7 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
                 cur = step1;
 #pragma unroll
                 for (int q = 2; q < 8; ++q) {
-                    cur = rot(cur, step1);
+                    cur = rot2(cur, step1);
                     tab[il][COLS * 8 + q] = cur;
                 }
                 double r_base = frac_product(f_tile, tp);
@@ -558,7 +553,7 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
                 tab[il][0] = b0;
 #pragma unroll
                 for (int q = 1; q < COLS * 8; ++q) {
-                    b0 = rot(b0, step1);
+                    b0 = rot2(b0, step1);
                     tab[il][q] = b0;
                 }
             }
@@ -631,7 +626,7 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
                     h1a = stab[i * 4 + 2];
                     h1b = stab[i * 4 + 3];
                     __builtin_amdgcn_sched_barrier(0);
-                    const double2 seed = rot(qa, qt);
+                    const double2 seed = rot2(qa, qt);
                     A1 = r[0] * seed.x;
                     B1 = r[0] * seed.y;
                     A2 = r[1] * seed.x;
@@ -678,13 +673,10 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
             return h;
         };
         auto accumulate = [&](const Ahead &h) {
-            const double2 seed = rot(h.qa, h.qt);
+            const double2 seed = rot2(h.qa, h.qt);
             const double wy = h.r[0], w = h.r[1], cd = h.r[2], sd = h.r[3], cd2 = h.cd2;
             const double wt = MODE == MODE_TREND ? w * h.tp : 0.0;   // sqrt(w) t': s and c carry the other sqrt(w)
-            double s = seed.x, c = seed.y;
-            double sp = 0.0, cp = 0.0;  // previous step of the recurrence
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
+            walk_grid<K>(seed, cd, sd, cd2, [&](const int k, const double s, const double c) {
                 Sh[k] = __builtin_fma(wy, s, Sh[k]);
                 Ch[k] = __builtin_fma(wy, c, Ch[k]);
                 if (MODE != MODE_RAW) {
@@ -699,24 +691,7 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
                     SS[k] = __builtin_fma(s, s, SS[k]);
                     SC[k] = __builtin_fma(s, c, SC[k]);
                 }
-                if (k + 1 < K) {
-                    double sn, cn;
-                    if (k == 0) {
-                        // first grid step: plane rotation by 2 pi delta t'
-                        cn = __builtin_fma(c, cd, -(s * sd));
-                        sn = __builtin_fma(s, cd, c * sd);
-                    } else {
-                        // later steps: x[k+1] = 2 cos(theta) x[k] - x[k-1]  (1 fma per component;
-                        // rounding grows like K^2 eps, far below the 1e-6 gate for K <= 16)
-                        cn = __builtin_fma(cd2, c, -cp);
-                        sn = __builtin_fma(cd2, s, -sp);
-                    }
-                    cp = c;
-                    sp = s;
-                    c = cn;
-                    s = sn;
-                }
-            }
+            });
         };
         Ahead A = fetch(i_beg);
         int i = i_beg;

@@ -13,8 +13,8 @@
 //                            of gls_prep_kernel, and the same 48-byte record per sample, rotated by the
 //                            curve's own delta[b].
 //   gls_ragged_scan_kernel   one workgroup per (curve, tile of 1024 bins), found by a scalar binary search
-//                            in a tile prefix table.  The running sums, the rotation tables and the
-//                            three-term recurrence are those of gls_scan_kernel (K = 8, one wave per
+//                            in a tile prefix table.  The rotation tables, the scalar pipeline and the
+//                            three-term recurrence are the shared ones of gls_sums.h (K = 8, one wave per
 //                            64-lane column, two columns); the epilogue (gls_epilogue.h) is fused.  Tiles
 //                            are dispatched costliest curve first (ragged_order, cost ~ n_b), so that the long
 //                            curves do not run alone at the end of the launch.  Optionally also writes a pitched
@@ -28,6 +28,7 @@
 // no balanced pieces (one huge curve has its own path in gls.hip).
 #include "pdc_internal.h"
 #include "gls_epilogue.h"
+#include "gls_sums.h"
 
 #include <cmath>
 #include <vector>
@@ -68,7 +69,7 @@ struct RaggedArgs {
     int64_t *blk_arg;
 };
 
-// ---- prologue: spectral.py:99-108, 120, per curve (gls_prep_kernel with the curve's own delta) ---------------
+// ---- prologue: spectral.py:99-108, 120, per curve, rotated by the curve's own delta (gls_sums.h) ---------------
 __global__ __launch_bounds__(kRPrepBlock) void gls_ragged_prep_kernel(RaggedPrepArgs a) {
     __shared__ double red[kRPrepBlock / 64];
     const int tid = threadIdx.x;
@@ -80,38 +81,19 @@ __global__ __launch_bounds__(kRPrepBlock) void gls_ragged_prep_kernel(RaggedPrep
     const double *dy = a.dy ? a.dy + off : nullptr;
     const double t0 = n > 0 ? t[0] : 0.0;
     const double delta = a.delta[b];
-    double acc = 0.0;  // w = err**-2 ; w.sum()
-    for (int64_t i = tid; i < n; i += kRPrepBlock) {
-        const double e = dy ? dy[i] : 1.0;
-        acc += 1.0 / (e * e);
-    }
-    const double W = block_sum<kRPrepBlock>(acc, red);
-    double ybar = 0.0;
-    if (a.fit_mean) {  // np.dot(w / w.sum(), values)
-        acc = 0.0;
-        for (int64_t i = tid; i < n; i += kRPrepBlock) {
-            const double e = dy ? dy[i] : 1.0;
-            acc += (1.0 / (e * e)) / W * y[i];
-        }
-        ybar = block_sum<kRPrepBlock>(acc, red);
-    }
+    double W, ybar;
+    weights_and_mean<kRPrepBlock>(y, dy, n, a.fit_mean, red, W, ybar);
     double yy = 0.0, wsum = 0.0;
     double *rec = a.rec + off * 6;
     for (int64_t i = tid; i < n; i += kRPrepBlock) {
         const double tp = t[i] - t0;
-        const double e = dy ? dy[i] : 1.0;
-        const double w = (1.0 / (e * e)) / W;
+        const double w = inv_var(dy, i) / W;
         const double yc = y[i] - ybar;
         const double wy = w * yc;
         yy += wy * yc;
         wsum += w;
-        double sd, cd;
-        sincos_cycles(frac_product(delta, tp), sd, cd);
         const double rw = sqrt(w);  // the scan carries sqrt(w) sin / sqrt(w) cos
-        double2 *r = reinterpret_cast<double2 *>(rec + i * 6);
-        r[0] = make_double2(rw * yc, rw);
-        r[1] = make_double2(cd, sd);
-        r[2] = make_double2(cd + cd, tp);
+        put_record(rec + i * 6, rw * yc, rw, delta, tp);
     }
     yy = block_sum<kRPrepBlock>(yy, red);
     wsum = block_sum<kRPrepBlock>(wsum, red);
@@ -124,7 +106,7 @@ __global__ __launch_bounds__(kRPrepBlock) void gls_ragged_prep_kernel(RaggedPrep
     }
 }
 
-// ---- the scan: gls_scan_kernel<K = 8, SPLIT = 1> with a (curve, tile) lookup per workgroup ------------------
+// ---- the scan: a (curve, tile) lookup per workgroup, then the pieces of gls_sums.h at K = 8 -----------------
 template <bool FIT_MEAN>
 __global__ __launch_bounds__(kRBlock) void gls_ragged_scan_kernel(RaggedArgs a) {
     // per sample: {sin, cos} of theta_tile + 8 q Theta, q < 8 COLS, scaled by sqrt(w) | {sin, cos}(b Theta), b < 8
@@ -160,124 +142,41 @@ __global__ __launch_bounds__(kRBlock) void gls_ragged_scan_kernel(RaggedArgs a) 
 #pragma unroll
     for (int k = 0; k < kRK; ++k) Sh[k] = Ch[k] = S[k] = C[k] = SS[k] = SC[k] = 0.0;
 
-    auto rot = [](const double2 x, const double2 y) {
-        return make_double2(__builtin_fma(x.x, y.y, x.y * y.x), __builtin_fma(x.y, y.y, -(x.x * y.x)));
-    };
     const int slot_a = col * 8 + (lane >> 3), slot_b = kRCols * 8 + (lane & 7);
     for (int64_t base = 0; base < n; base += kRChunk) {
         __syncthreads();  // everyone is done with the previous chunk's tables
-        // rotation tables, two threads per sample (see gls_scan_kernel): the even thread makes {sin, cos}(b Theta)
-        // and the tile's base phase (scaled by sqrt(w)), the odd one walks the base in steps of 8 Theta
-        {
+        {   // rotation tables, two threads per sample: the whole block
             const int il = tid >> 1;
             const bool live = base + il < n;   // (rows past the end are never accumulated; they need finite input)
             const double tp = live ? a.rec[(off + base + il) * 6 + 5] : 0.0;
             const double sqw = live ? a.rec[(off + base + il) * 6 + 1] : 0.0;
-            double2 step1, cur;
-            if ((tid & 1) == 0) {
-                sincos_cycles(frac_product(kdelta, tp), step1.x, step1.y);
-                tab[il][kRCols * 8] = make_double2(0.0, 1.0);
-                tab[il][kRCols * 8 + 1] = step1;
-                cur = step1;
-#pragma unroll
-                for (int q = 2; q < 8; ++q) {
-                    cur = rot(cur, step1);
-                    tab[il][kRCols * 8 + q] = cur;
-                }
-                sincos_cycles(frac_product(f_tile, tp), cur.x, cur.y);
-                cur.x *= sqw;
-                cur.y *= sqw;
-            } else {
-                sincos_cycles(frac_product(8.0 * kdelta, tp), step1.x, step1.y);
-            }
-            double2 b0;
-            b0.x = __shfl_xor(cur.x, 1, 64);
-            b0.y = __shfl_xor(cur.y, 1, 64);
-            if (tid & 1) {
-                tab[il][0] = b0;
-#pragma unroll
-                for (int q = 1; q < kRCols * 8; ++q) {
-                    b0 = rot(b0, step1);
-                    tab[il][q] = b0;
-                }
-            }
+            fill_rotation_tables<kRCols>(tab[il], tid & 1, tp, kdelta, f_tile, sqw);
         }
         __syncthreads();
         const int cnt = (int)((n - base) < kRChunk ? (n - base) : kRChunk);
-        // software pipeline of gls_scan_kernel: record fields through the scalar cache (wave-uniform), two
-        // register sets that swap roles; the read-ahead touches one record past the curve (the workspace keeps
-        // two spare records after the last curve) and the padding table row
-        using d4 = double __attribute__((ext_vector_type(4)));
-        using cd4 = __attribute__((address_space(4))) const d4;
-        using cdbl = __attribute__((address_space(4))) const double;
-        const cd4 *srec = reinterpret_cast<const cd4 *>(reinterpret_cast<uintptr_t>(a.rec + (off + base) * 6));
-        struct Ahead {
-            d4 r;  // {sqrt(w) y, sqrt(w), cos, sin (2 pi delta t')}
-            double cd2;
-            double2 qa, qt;
-        };
-        auto fetch = [&](const int i) {
-            Ahead h;
-            h.qa = tab[i][slot_a];
-            h.qt = tab[i][slot_b];
-            const cd4 *rp = reinterpret_cast<const cd4 *>(reinterpret_cast<const cdbl *>(srec) + i * 6);
-            h.r = rp[0];
-            h.cd2 = reinterpret_cast<const cdbl *>(rp)[4];
-            return h;
-        };
-        auto accumulate = [&](const Ahead &h) {
-            const double2 seed = rot(h.qa, h.qt);
-            const double wy = h.r[0], w = h.r[1], cd = h.r[2], sd = h.r[3], cd2 = h.cd2;
-            double s = seed.x, c = seed.y;
-            double sp = 0.0, cp = 0.0;
-#pragma unroll
-            for (int k = 0; k < kRK; ++k) {
-                Sh[k] = __builtin_fma(wy, s, Sh[k]);
-                Ch[k] = __builtin_fma(wy, c, Ch[k]);
-                if (FIT_MEAN) {
-                    S[k] = __builtin_fma(w, s, S[k]);
-                    C[k] = __builtin_fma(w, c, C[k]);
-                }
-                SS[k] = __builtin_fma(s, s, SS[k]);
-                SC[k] = __builtin_fma(s, c, SC[k]);
-                if (k + 1 < kRK) {
-                    double sn, cn;
-                    if (k == 0) {   // first grid step: plane rotation by 2 pi delta t'
-                        cn = __builtin_fma(c, cd, -(s * sd));
-                        sn = __builtin_fma(s, cd, c * sd);
-                    } else {        // x[k+1] = 2 cos(theta) x[k] - x[k-1]
-                        cn = __builtin_fma(cd2, c, -cp);
-                        sn = __builtin_fma(cd2, s, -sp);
+        // (the read-ahead touches one record past the curve: the workspace keeps two spare records after the last curve)
+        const double *rec = a.rec + (off + base) * 6;
+        two_set_pipeline(
+            0, cnt, [&](const int i) { return fetch_sample(tab, rec, i, slot_a, slot_b); },
+            [&](const Ahead &h) {
+                const double wy = h.r[0], w = h.r[1];
+                walk_grid<kRK>(rot2(h.qa, h.qt), h.r[2], h.r[3], h.cd2, [&](const int k, const double s, const double c) {
+                    Sh[k] = __builtin_fma(wy, s, Sh[k]);
+                    Ch[k] = __builtin_fma(wy, c, Ch[k]);
+                    if (FIT_MEAN) {
+                        S[k] = __builtin_fma(w, s, S[k]);
+                        C[k] = __builtin_fma(w, c, C[k]);
                     }
-                    cp = c;
-                    sp = s;
-                    c = cn;
-                    s = sn;
-                }
-            }
-        };
-        Ahead A = fetch(0);
-        int i = 0;
-        for (; i + 1 < cnt; i += 2) {
-            __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): set A has arrived
-            Ahead B = fetch(i + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            accumulate(A);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            A = fetch(i + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            accumulate(B);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (i < cnt) accumulate(A);
+                    SS[k] = __builtin_fma(s, s, SS[k]);
+                    SC[k] = __builtin_fma(s, c, SC[k]);
+                });
+            });
     }
 
     // fused epilogue (spectral.py:113-132); the 2-omega sums from sin 2a = 2 sin a cos a, cos 2a = 1 - 2 sin^2 a
     const double *sc = a.scal + curve * 4;
     const double YY = sc[0], Wsum = sc[1], Werr = sc[2];
-    double best = 0.0;
-    long long best_j = -1;
+    ArgMax best;
 #pragma unroll
     for (int k = 0; k < kRK; ++k) {
         const int64_t j = jl + k;
@@ -286,39 +185,13 @@ __global__ __launch_bounds__(kRBlock) void gls_ragged_scan_kernel(RaggedArgs a) 
                                                            YY, Werr, a.psd);
             if (a.power) a.power[fo + j] = p;
             if (a.pitched) a.pitched[curve * a.pitch + j] = p;
-            if (p == p && (best_j < 0 || p > best)) {
-                best = p;
-                best_j = j;
-            }
+            best.take(p, j);
         }
     }
-    if (a.blk_max) {
-        // NaN-aware max with lowest-index ties (np.nanargmax): lanes hold ascending index ranges
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double ov = __shfl_down(best, o, 64);
-            const long long oj = __shfl_down(best_j, o, 64);
-            if (oj >= 0 && (best_j < 0 || ov > best || (ov == best && oj < best_j))) {
-                best = ov;
-                best_j = oj;
-            }
-        }
-        if (lane == 0) {
-            red_v[col] = best;
-            red_i[col] = best_j;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int wv = 1; wv < kRBlock / 64; ++wv) {
-                if (red_i[wv] >= 0 && (best_j < 0 || red_v[wv] > best)) {
-                    best = red_v[wv];
-                    best_j = red_i[wv];
-                }
-            }
-            const int64_t at = a.ctile[curve] + tile;
-            a.blk_max[at] = best;
-            a.blk_arg[at] = best_j;
-        }
+    if (a.blk_max && best.block_fold<kRBlock / 64>(red_v, red_i, lane, col)) {   // lanes hold ascending index ranges
+        const int64_t at = a.ctile[curve] + tile;
+        a.blk_max[at] = best.v;
+        a.blk_arg[at] = best.j;
     }
 }
 
@@ -327,28 +200,12 @@ __global__ __launch_bounds__(64) void gls_ragged_peak_kernel(const double *blk_m
                                                              const int64_t *ctile, double *amax, int64_t *argmax) {
     const int64_t curve = blockIdx.x;
     const int64_t t0 = ctile[curve], t1 = ctile[curve + 1];
-    double best = 0.0;
-    long long best_j = -1;
-    for (int64_t i = t0 + threadIdx.x; i < t1; i += 64) {
-        const double v = blk_max[i];
-        const long long j = blk_arg[i];
-        if (j >= 0 && (best_j < 0 || v > best)) {
-            best = v;
-            best_j = j;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_down(best, o, 64);
-        const long long oj = __shfl_down(best_j, o, 64);
-        if (oj >= 0 && (best_j < 0 || ov > best || (ov == best && oj < best_j))) {
-            best = ov;
-            best_j = oj;
-        }
-    }
+    ArgMax best;
+    for (int64_t i = t0 + threadIdx.x; i < t1; i += 64) best.take_later(blk_max[i], blk_arg[i]);
+    best.wave_fold();
     if (threadIdx.x == 0) {
-        if (amax) amax[curve] = best_j >= 0 ? best : __builtin_nan("");
-        if (argmax) argmax[curve] = best_j;
+        if (amax) amax[curve] = best.j >= 0 ? best.v : __builtin_nan("");
+        if (argmax) argmax[curve] = best.j;
     }
 }
 

@@ -18,6 +18,7 @@
 //   glsfft_epilogue_kernel undo the tmin shift (:35-37), scale by nfft (:38-39), epilogue
 #include "pdc_internal.h"
 #include "gls_epilogue.h"
+#include "gls_sums.h"
 
 #include <cstdlib>
 #include <vector>
@@ -315,8 +316,7 @@ __global__ __launch_bounds__(kBlock) void glsfft_prep_c_kernel(FftPrepArgs a) {
     const double disorder = reduce_partials(a.part + 4 * kMaxPart, a.nparts, red);
     double yy = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * kBlock) {
-        const double e = a.dy ? a.dy[i] : 1.0;
-        const double w = (1.0 / (e * e)) / W;
+        const double w = inv_var(a.dy, i) / W;
         const double yc = a.y[i] - ybar;
         a.w[i] = w;
         a.wy[i] = w * yc;

@@ -8,7 +8,7 @@
 // Decomposition
 //   mhgls_prep_kernel   one workgroup: weights, weighted mean, YY, and one 48-byte record per sample
 //                       {w y, w, cos(2 pi delta t'), sin(2 pi delta t'), 2 cos(2 pi delta t'), t' = t - t0}.
-//   mhgls_scan_kernel   the skeleton of gls_scan_kernel (gls.hip): each thread owns K consecutive frequencies, the
+//   mhgls_scan_kernel   the skeleton of gls_sums.h: each thread owns K consecutive frequencies, the
 //                       records come through the scalar cache, the seed of a (sample, thread) is one plane rotation of
 //                       two LDS table entries built per 64-sample chunk from exact cycle reductions, and a rotation
 //                       plus the three-term recurrence walk the K frequencies.  (sin, cos) are carried UNscaled here:
@@ -21,6 +21,7 @@
 // One workgroup per tile of 256 K frequencies streams the whole curve (as the MODE_TREND instances of gls.hip do); no
 // sample parts, no balanced pieces, one device.
 #include "pdc_internal.h"
+#include "gls_sums.h"
 
 #include <cmath>
 
@@ -56,21 +57,8 @@ __global__ __launch_bounds__(kPrepBlock) void mhgls_prep_kernel(MhPrepArgs a) {
     __shared__ double red[kPrepBlock / 64];
     const int tid = threadIdx.x;
     const double t0 = a.n > 0 ? a.t[0] : 0.0;
-    double acc = 0.0;
-    for (int64_t i = tid; i < a.n; i += kPrepBlock) {
-        const double e = a.dy ? a.dy[i] : 1.0;
-        acc += 1.0 / (e * e);
-    }
-    const double W = block_sum<kPrepBlock>(acc, red);
-    double ybar = 0.0;
-    if (a.fit_mean) {
-        acc = 0.0;
-        for (int64_t i = tid; i < a.n; i += kPrepBlock) {
-            const double e = a.dy ? a.dy[i] : 1.0;
-            acc += (1.0 / (e * e)) / W * a.y[i];
-        }
-        ybar = block_sum<kPrepBlock>(acc, red);
-    }
+    double W, ybar;
+    weights_and_mean<kPrepBlock>(a.y, a.dy, a.n, a.fit_mean, red, W, ybar);
     double yy = 0.0, wsum = 0.0, y1 = 0.0;
     for (int64_t i = tid; i < a.n + 2; i += kPrepBlock) {
         double2 *r = reinterpret_cast<double2 *>(a.rec + i * 6);
@@ -79,18 +67,13 @@ __global__ __launch_bounds__(kPrepBlock) void mhgls_prep_kernel(MhPrepArgs a) {
             continue;
         }
         const double tp = a.t[i] - t0;
-        const double e = a.dy ? a.dy[i] : 1.0;
-        const double w = (1.0 / (e * e)) / W;
+        const double w = inv_var(a.dy, i) / W;
         const double yc = a.y[i] - ybar;
         const double wy = w * yc;
         yy += wy * yc;
         wsum += w;
         y1 += wy;
-        double sd, cd;
-        sincos_cycles(frac_product(a.delta, tp), sd, cd);
-        r[0] = make_double2(wy, w);
-        r[1] = make_double2(cd, sd);
-        r[2] = make_double2(cd + cd, tp);
+        put_record(a.rec + i * 6, wy, w, a.delta, tp);
     }
     yy = block_sum<kPrepBlock>(yy, red);
     wsum = block_sum<kPrepBlock>(wsum, red);
@@ -188,132 +171,45 @@ __global__ __launch_bounds__(kBlock) void mhgls_scan_kernel(MhArgs a) {
         for (int h = 0; h < H; ++h) YC[h][k] = YS[h][k] = 0.0;
     }
 
-    // plane rotation of {sin, cos} pairs: angle(x) + angle(y)
-    auto rot = [](const double2 x, const double2 y) {
-        return make_double2(__builtin_fma(x.x, y.y, x.y * y.x), __builtin_fma(x.y, y.y, -(x.x * y.x)));
-    };
     const int slot_a = col * 8 + (lane >> 3), slot_b = COLS * 8 + (lane & 7);
     for (int64_t base = 0; base < n; base += kChunk) {
         __syncthreads();   // everyone is done with the previous chunk's tables
-        // ---- per-sample rotation tables (two threads per sample), as in gls_scan_kernel ----------------------------
-        // Thread (col, lane) starts at phase theta_tile + (64 col + 8 a + b) Theta, a = lane / 8, b = lane % 8,
-        // Theta = 2 pi K delta t'.  The even thread of a sample makes {sin, cos}(b Theta) and the tile's base phase,
-        // the odd thread walks that base in steps of 8 Theta.
-        if (tid < 2 * kChunk) {
+        if (tid < 2 * kChunk) {   // rotation tables, two threads per sample; (sin, cos) unscaled
             const int il = tid >> 1;
             // (rows past the end of the curve are never accumulated; they only need finite input)
             const double tp = base + il < n ? a.rec[(base + il) * 6 + 5] : 0.0;
-            double2 step1, cur = make_double2(0.0, 0.0);
-            if ((tid & 1) == 0) {
-                sincos_cycles(frac_product(kdelta, tp), step1.x, step1.y);
-                tab[il][COLS * 8] = make_double2(0.0, 1.0);
-                tab[il][COLS * 8 + 1] = step1;
-                cur = step1;
-#pragma unroll
-                for (int q = 2; q < 8; ++q) {
-                    cur = rot(cur, step1);
-                    tab[il][COLS * 8 + q] = cur;
-                }
-                sincos_cycles(frac_product(f_tile, tp), cur.x, cur.y);
-            } else {
-                sincos_cycles(frac_product(8.0 * kdelta, tp), step1.x, step1.y);
-            }
-            double2 b0;
-            b0.x = __shfl_xor(cur.x, 1, 64);
-            b0.y = __shfl_xor(cur.y, 1, 64);
-            if (tid & 1) {
-                tab[il][0] = b0;
-#pragma unroll
-                for (int q = 1; q < COLS * 8; ++q) {
-                    b0 = rot(b0, step1);
-                    tab[il][q] = b0;
-                }
-            }
+            fill_rotation_tables<COLS>(tab[il], tid & 1, tp, kdelta, f_tile, 1.0);
         }
         __syncthreads();
         const int cnt = (int)((n - base) < kChunk ? (n - base) : kChunk);
-        // Software pipeline of gls_scan_kernel: everything sample i+1 needs is requested while sample i is
-        // accumulated, two samples per trip with two register sets that swap roles.  The record fields are
-        // wave-uniform: they come through the scalar cache (constant address space) and feed the fmas as SGPR
-        // operands.  (The read-ahead touches one record past the curve - the prologue wrote it - and the padding row
-        // of the table.)
-        using d4 = double __attribute__((ext_vector_type(4)));
-        using cd4 = __attribute__((address_space(4))) const d4;
-        using cdbl = __attribute__((address_space(4))) const double;
-        const cd4 *srec = reinterpret_cast<const cd4 *>(reinterpret_cast<uintptr_t>(a.rec + base * 6));
-        struct Ahead {
-            d4 r;   // {w y, w, cos, sin (2 pi delta t')}
-            double cd2;
-            double2 qa, qt;
-        };
-        auto fetch = [&](const int i) {
-            Ahead h;
-            h.qa = tab[i][slot_a];
-            h.qt = tab[i][slot_b];
-            const cd4 *rp = reinterpret_cast<const cd4 *>(reinterpret_cast<const cdbl *>(srec) + i * 6);
-            h.r = rp[0];
-            h.cd2 = reinterpret_cast<const cdbl *>(rp)[4];
-            return h;
-        };
-        auto accumulate = [&](const Ahead &h) {
-            const double2 seed = rot(h.qa, h.qt);
-            const double wy = h.r[0], w = h.r[1], cd = h.r[2], sd = h.r[3], cd2 = h.cd2;
-            double s = seed.x, c = seed.y;
-            double sp = 0.0, cp = 0.0;   // previous step of the recurrence over the grid
+        // (the read-ahead touches one record past the curve - the prologue wrote it - and the padding row of the table)
+        const double *rec = a.rec + base * 6;
+        two_set_pipeline(
+            0, cnt, [&](const int i) { return fetch_sample(tab, rec, i, slot_a, slot_b); },
+            [&](const Ahead &h) {
+                const double wy = h.r[0], w = h.r[1];
+                walk_grid<K>(rot2(h.qa, h.qt), h.r[2], h.r[3], h.cd2, [&](const int k, const double s, const double c) {
+                    // harmonics of this (sample, frequency): Chebyshev recurrence on the unscaled (sin, cos)
+                    const double c2 = c + c;
+                    double sm = s, cm = c, sl = 0.0, cl = 1.0;   // harmonic m and m - 1
 #pragma unroll
-            for (int k = 0; k < K; ++k) {
-                // harmonics of this (sample, frequency): Chebyshev recurrence on the unscaled (sin, cos)
-                const double c2 = c + c;
-                double sm = s, cm = c, sl = 0.0, cl = 1.0;   // harmonic m and m - 1
-#pragma unroll
-                for (int m = 1; m <= 2 * H; ++m) {
-                    Cm[m - 1][k] = __builtin_fma(w, cm, Cm[m - 1][k]);
-                    Sm[m - 1][k] = __builtin_fma(w, sm, Sm[m - 1][k]);
-                    if (m <= H) {
-                        YC[m - 1][k] = __builtin_fma(wy, cm, YC[m - 1][k]);
-                        YS[m - 1][k] = __builtin_fma(wy, sm, YS[m - 1][k]);
+                    for (int m = 1; m <= 2 * H; ++m) {
+                        Cm[m - 1][k] = __builtin_fma(w, cm, Cm[m - 1][k]);
+                        Sm[m - 1][k] = __builtin_fma(w, sm, Sm[m - 1][k]);
+                        if (m <= H) {
+                            YC[m - 1][k] = __builtin_fma(wy, cm, YC[m - 1][k]);
+                            YS[m - 1][k] = __builtin_fma(wy, sm, YS[m - 1][k]);
+                        }
+                        if (m < 2 * H) {
+                            const double cn = __builtin_fma(c2, cm, -cl), sn = __builtin_fma(c2, sm, -sl);
+                            cl = cm;
+                            sl = sm;
+                            cm = cn;
+                            sm = sn;
+                        }
                     }
-                    if (m < 2 * H) {
-                        const double cn = __builtin_fma(c2, cm, -cl), sn = __builtin_fma(c2, sm, -sl);
-                        cl = cm;
-                        sl = sm;
-                        cm = cn;
-                        sm = sn;
-                    }
-                }
-                if (k + 1 < K) {
-                    double sn, cn;
-                    if (k == 0) {
-                        // first grid step: plane rotation by 2 pi delta t'
-                        cn = __builtin_fma(c, cd, -(s * sd));
-                        sn = __builtin_fma(s, cd, c * sd);
-                    } else {
-                        // later steps: x[k+1] = 2 cos(2 pi delta t') x[k] - x[k-1]
-                        cn = __builtin_fma(cd2, c, -cp);
-                        sn = __builtin_fma(cd2, s, -sp);
-                    }
-                    cp = c;
-                    sp = s;
-                    c = cn;
-                    s = sn;
-                }
-            }
-        };
-        Ahead A = fetch(0);
-        int i = 0;
-        for (; i + 1 < cnt; i += 2) {
-            __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): set A has arrived
-            Ahead B = fetch(i + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            accumulate(A);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            A = fetch(i + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            accumulate(B);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (i < cnt) accumulate(A);
+                });
+            });
     }
 
     const double YY = a.scal[0], Wsum = a.scal[1], Werr = a.scal[2], Y1 = a.scal[3];

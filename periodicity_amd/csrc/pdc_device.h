@@ -1,6 +1,7 @@
 // Device-side helpers shared by the kernels of libperiodicity_hip.so (not installed).  Kept apart from
 // pdc_internal.h (host-side runtime declarations) so that the source hashes profiles/*_pmc_summary.json
-// records for a kernel change only when device code does.
+// records for a kernel change only when device code does.  gls_sums.h (the GLS direct-sum skeleton built on these
+// helpers) is hashed there as a file of its own, like every unit that includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -68,7 +68,7 @@ def main(scan_only):
 
     ms = tm.ms(scan, reps=5, warm=2)
     print(f"(a) ragged scan: B={B} N={n_total} ({np.diff(offsets).min()}..{np.diff(offsets).max()}) "
-          f"nf={nf_total} ({nfb.min()}..{nf_max}) pairs={pairs:.3e}: {ms:.2f} ms, {pairs / ms * 1e3:.3e} pair/s "
+          f"nf={nf_total} ({nfb.min()}..{nf_max}) pairs={pairs:.3e}: {ms:.3f} ms, {pairs / ms * 1e3:.3e} pair/s "
           "(prologue + scan + maxima + the 0.2 MB metadata upload)")
     if scan_only:
         return
