@@ -248,6 +248,57 @@ int pdc_bls_scan_dev(int device, void *stream, const double *d_t, const double *
                      int dips_only, int slices,
                      double *d_power, double *d_depth, int32_t *d_start_bin, int32_t *d_box_bins);
 
+/* ---- BLS over curves on their OWN period grids (BLS.batch) -------------------------------------------
+ * Replaces a survey's loop of BLS()(s, e): curve b owns samples [offsets[b], offsets[b+1]) of t, y and dy (dy == NULL:
+ * unit uncertainties for every curve) and the trial periods linspace(start[b], stop[b], P_b),
+ * P_b = p_offsets[b+1] - p_offsets[b], rebuilt on the device with numpy's rule as for pdc_phase_scan_ragged (for
+ * P_b == 1 pass step = stop - start).  n_bins ... dips_only are those of pdc_bls_scan, shared by all curves, with its
+ * limits; there is no `slices`: one workgroup bins and searches one (curve, period).  The rows power, depth,
+ * start_bin, box_bins [p_offsets[B]] come back in period order, X[p_offsets[b] + j], and are BIT-IDENTICAL to
+ * pdc_bls_scan on that curve and those periods at every curve length and every `slices` (the sums are integers).
+ * best_* [B]: index = the first period index of the row's largest power (np.nanargmax), -1 for a row without a
+ * finite power (an empty curve, an empty grid, bad input, no admissible box anywhere); power, depth, start, box =
+ * the rows' values there, NaN / -1 where index is -1.  Any output may be NULL, but not all of them.
+ * Devices, groups and budget as for pdc_phase_scan_ragged: contiguous groups balanced by sum n_b P_b over the
+ * `n_devices` listed slots, per-slot buffers kept until pdc_release, groups that fit PDC_WORK_BUDGET_GB and free
+ * memory, the same bits for any grouping.
+ *
+ * pdc_bls_ragged_peaks: also the [B][k] peak table (k <= 1024) of pdc_gls_ragged_peaks on every curve's power row in
+ * FSeries order (ascending frequency 1/p: index j' = P_b - 1 - j when stop[b] > start[b], j' = j otherwise).  The
+ * rows may all be NULL: they stay in HBM.
+ *
+ * pdc_bls_ragged_work_bytes / pdc_bls_scan_ragged_dev: ONE launch sequence on `device` / `stream`, no grouping:
+ * d_t, d_y, d_dy and every output on the device; offsets ... p_offsets on the HOST (the entry waits for their
+ * upload before it returns, not for the launches).  d_pitched [B][pitch]: the power rows in FSeries order (its pad is
+ * the caller's).  work_bytes >= pdc_bls_ragged_work_bytes(B, offsets[B], p_offsets[B], 0, 0), which covers the
+ * records (24 bytes a sample) and the rows of every NULL output; p_max > 0 and k > 0 add the pitched copy and the
+ * [B][k] table of the peak entry's groups. */
+int pdc_bls_scan_ragged(const double *t, const double *y, const double *dy, const int64_t *offsets, int64_t n_curves,
+                        const double *start, const double *step, const double *stop, const int64_t *p_offsets,
+                        int n_bins, int len_min, int len_max, int min_points, int dips_only,
+                        double *power, double *depth, int32_t *start_bin, int32_t *box_bins,
+                        int64_t *best_index, double *best_power, double *best_depth, int32_t *best_start,
+                        int32_t *best_box, const int *devices, int n_devices);
+int pdc_bls_ragged_peaks(const double *t, const double *y, const double *dy, const int64_t *offsets, int64_t n_curves,
+                         const double *start, const double *step, const double *stop, const int64_t *p_offsets,
+                         int n_bins, int len_min, int len_max, int min_points, int dips_only, int k, int by_prominence,
+                         int64_t *count_out, int64_t *idx_out, double *height_out, double *prominence_out,
+                         int64_t *half_lo_out, int64_t *half_hi_out,
+                         double *power, double *depth, int32_t *start_bin, int32_t *box_bins,
+                         int64_t *best_index, double *best_power, double *best_depth, int32_t *best_start,
+                         int32_t *best_box, const int *devices, int n_devices);
+int64_t pdc_bls_ragged_work_bytes(int64_t n_curves, int64_t n_total, int64_t p_total, int64_t p_max, int k);
+/* TEST HOOK (not for callers): how many groups of curves the last pdc_bls_scan_ragged / pdc_bls_ragged_peaks call of
+ * this process ran, summed over its device slots. */
+int pdc_test_bls_ragged_groups(int64_t *groups);
+int pdc_bls_scan_ragged_dev(int device, void *stream, const double *d_t, const double *d_y, const double *d_dy,
+                            const int64_t *offsets, int64_t n_curves, const double *start, const double *step,
+                            const double *stop, const int64_t *p_offsets,
+                            int n_bins, int len_min, int len_max, int min_points, int dips_only,
+                            double *d_power, double *d_depth, int32_t *d_start_bin, int32_t *d_box_bins,
+                            int64_t *d_best_index, double *d_best_power, double *d_best_depth, int32_t *d_best_start,
+                            int32_t *d_best_box, double *d_pitched, int64_t pitch, void *work, int64_t work_bytes);
+
 /* Device-resident form used by bench.py: inputs already in HBM, no synchronisation.
  * `work` is scratch of at least pdc_gls_work_bytes(n_total, n_curves, nf) bytes on the same
  * device (non-decreasing in n_total and in nf: a buffer sized for the largest call serves all; for a

@@ -50,6 +50,15 @@ PROTOTYPES = {
     "pdc_mhgls_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _D, _D, _L, _L, _I, _I, _I, _VP]),
     "pdc_bls_scan": (_I, [_VP, _VP, _VP, _L, _VP, _L, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _I]),
     "pdc_bls_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _VP, _L, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
+    "pdc_bls_scan_ragged": (_I, [_VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I,
+                                 _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I]),
+    "pdc_bls_ragged_peaks": (_I, [_VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I,
+                                  _VP, _VP, _VP, _VP, _VP, _VP,
+                                  _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I]),
+    "pdc_bls_ragged_work_bytes": (_L, [_L, _L, _L, _L, _I]),
+    "pdc_test_bls_ragged_groups": (_I, [C.POINTER(_L)]),
+    "pdc_bls_scan_ragged_dev": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I,
+                                     _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _L, _VP, _L]),
     "pdc_gls_scan": (_I, [_VP, _VP, _VP, _L, _D, _D, _L, _L, _I, _I, _VP, _I]),
     "pdc_gls_scan_batch": (_I, [_VP, _VP, _VP, _VP, _L, _I, _D, _D, _L, _L, _I, _I,
                                 _VP, _VP, _VP, _I]),
@@ -669,6 +678,53 @@ def phase_scan_ragged(kind, t, x, offsets, start, step, stop, p_offsets, nb, nc,
                                        _ptr(table["indices"]), _ptr(table["heights"]), _ptr(table["prominences"]),
                                        _ptr(table["half_lo"]), _ptr(table["half_hi"]), _ptr(out), _ptr(devs), devs.size))
     return out, table
+
+
+def bls_scan_ragged(t, y, dy, offsets, start, step, stop, p_offsets, n_bins, len_min, len_max, min_points=5,
+                    dips_only=False, k=0, by_prominence=False, want_power=True, device=None, devices=None):
+    """Box least squares over a batch of curves, each on its own period grid ``linspace(start[b], stop[b],
+    p_offsets[b+1] - p_offsets[b])`` (``pdc_bls_scan_ragged``; with ``k > 0`` ``pdc_bls_ragged_peaks``):
+    ``(rows | None, best, peak table dict | None)``.  ``rows``: the dict ``power, depth, start_bin, box_bins``
+    ``[p_offsets[-1]]`` (None without ``want_power``: they stay on the device); ``best``: the dict ``index, power,
+    depth, start_bin, box_bins`` ``[n_curves]`` of every row's first maximum, found on the device."""
+    t, y = _f64(t, "t"), _f64(y, "y")
+    dy = None if dy is None else _f64(dy, "dy")
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    p_offsets = np.ascontiguousarray(p_offsets, dtype=np.int64)
+    start, step, stop = _f64(start, "start"), _f64(step, "step"), _f64(stop, "stop")
+    nb_ = offsets.size - 1
+    if nb_ < 1 or p_offsets.size != nb_ + 1 or any(a.size != nb_ for a in (start, step, stop)):
+        raise ValueError("offsets / p_offsets need n_curves + 1 entries, start / step / stop n_curves")
+    if offsets[-1] != t.size or y.size != t.size or (dy is not None and dy.size != t.size):
+        raise ValueError("Input arrays have incompatible lengths.")
+    total = max(int(p_offsets[-1]), 0)
+    rows = None
+    if want_power:
+        rows = {"power": np.empty(total, dtype=np.float64), "depth": np.empty(total, dtype=np.float64),
+                "start_bin": np.empty(total, dtype=np.int32), "box_bins": np.empty(total, dtype=np.int32)}
+    best = {"index": np.empty(nb_, dtype=np.int64), "power": np.empty(nb_, dtype=np.float64),
+            "depth": np.empty(nb_, dtype=np.float64), "start_bin": np.empty(nb_, dtype=np.int32),
+            "box_bins": np.empty(nb_, dtype=np.int32)}
+    devs = _slots(device, devices)
+    common = (_ptr(t), _ptr(y), _ptr(dy), _ptr(offsets), nb_, _ptr(start), _ptr(step), _ptr(stop), _ptr(p_offsets),
+              int(n_bins), int(len_min), int(len_max), int(min_points), int(bool(dips_only)))
+    outs = tuple(_ptr(rows[name]) if rows else None for name in ("power", "depth", "start_bin", "box_bins")) + \
+        tuple(_ptr(best[name]) for name in ("index", "power", "depth", "start_bin", "box_bins"))
+    if not k:
+        check(lib().pdc_bls_scan_ragged(*common, *outs, _ptr(devs), devs.size))
+        return rows, best, None
+    table = _topk_outputs(nb_, int(k))
+    check(lib().pdc_bls_ragged_peaks(*common, int(k), int(bool(by_prominence)), _ptr(table["count"]),
+                                     _ptr(table["indices"]), _ptr(table["heights"]), _ptr(table["prominences"]),
+                                     _ptr(table["half_lo"]), _ptr(table["half_hi"]), *outs, _ptr(devs), devs.size))
+    return rows, best, table
+
+
+def bls_ragged_groups():
+    """Test hook: groups of curves the last BLS batch call of this process ran."""
+    g = C.c_int64()
+    check(lib().pdc_test_bls_ragged_groups(C.byref(g)))
+    return g.value
 
 
 def stringlength_scan_ragged(t, m, offsets, start, step, stop, p_offsets, k=0, by_prominence=False,

@@ -30,11 +30,13 @@ int release_ragged();
 int release_phase_ragged();
 // ... and those of the ragged-grid StringLength host entries (sl_ragged.inc, in stringlength.hip).
 int release_sl_ragged();
+// ... and those of the ragged-grid BLS host entries (bls_ragged.hip).
+int release_bls_ragged();
 
 // ---- ragged-grid batches: the host side the kinds share (ragged.hip) ---------------------------------------------
 // A ragged batch is a catalogue of light curves that each keep their own grid: curve b owns samples
 // [offsets[b], offsets[b+1]) and rows [rows[b], rows[b+1]) - GLS's frequency bins (gls_ragged.hip) or the phase
-// folds' trial periods (pdm_ragged.hip, sl_ragged.inc).  Each kind keeps its kernels, workspace layout, uploads and launches.
+// folds' trial periods (pdm_ragged.hip, sl_ragged.inc, bls_ragged.hip).  Each kind keeps its kernels, workspace layout, uploads and launches.
 inline int64_t up256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 // The checks every ragged entry shares, with their texts: n_curves, offsets and `rows_name` starting at 0 and never

@@ -356,6 +356,7 @@ int pdc_release(void) {
     release_multi();
     PDC_TRY(release_ragged());
     PDC_TRY(release_phase_ragged());
+    PDC_TRY(release_bls_ragged());
     PDC_TRY(release_sl_ragged());
     PDC_TRY(release_stream_scratch());
     std::lock_guard<std::mutex> lk(g_mutex);

@@ -23,7 +23,7 @@ from .core import FSeries, TSeries
 MAX_CORES = cpu_count()
 
 __all__ = ["StringLength", "PDM", "AOV", "ConditionalEntropy", "GregoryLoredo", "SuperSmoother", "BLS", "PhaseBatch",
-           "StringLengthBatch"]
+           "StringLengthBatch", "BLSBatch"]
 
 
 # ---- host-side grid / scaling rules (O(N) or O(n_periods) numpy, as upstream) -----------------------
@@ -174,6 +174,96 @@ class StringLengthBatch(PhaseBatch):
         start, stop = self._start[rows], self._stop[rows]
         j = np.where(start > stop, count - 1 - bins, bins)
         return 1 / (1 / _linspace_at(start, self._step[rows], stop, count, j))
+
+
+class BLSBatch(PhaseBatch):
+    """What ``BLS.batch`` returns: a :class:`PhaseBatch` (``periods``, ``periodograms`` = one
+    ``FSeries(1 / periods, power)`` per curve or None, ``peaks``) and, per curve and aligned with ``periods[b]``, the
+    lists ``power``, ``depth``, ``start_bin``, ``box_bins``, ``duration``, ``transit_time`` of ``BLS.__call__`` (None
+    without ``want_power``).  ``best`` is always there: a dict of ``[B]`` arrays ``index`` (``np.nanargmax`` of the
+    power row in period order, -1 for a row without a finite power), ``period``, ``power``, ``depth``, ``duration``,
+    ``transit_time`` (NaN where ``index`` is -1), from the maxima found on the device."""
+
+    def __init__(self, start, step, stop, p_offsets, n_bins, rows, best, peaks):
+        super().__init__(start, step, stop, p_offsets, None if rows is None else rows["power"], peaks)
+        n_bins = int(n_bins)
+        self.power = self.depth = self.start_bin = self.box_bins = self.duration = self.transit_time = None
+        if rows is not None:
+            periods = np.concatenate(self.periods) if len(self) else np.empty(0)
+            found = rows["start_bin"] >= 0
+            start_bin = np.where(found, rows["start_bin"], np.nan)
+            box_bins = np.where(found, rows["box_bins"], np.nan)
+            flat = {"power": rows["power"], "depth": rows["depth"], "start_bin": start_bin, "box_bins": box_bins,
+                    "duration": box_bins / n_bins * periods,
+                    "transit_time": ((start_bin + box_bins / 2) / n_bins % 1) * periods}
+            for name, values in flat.items():
+                setattr(self, name, np.split(values, p_offsets[1:-1]))
+        index = np.asarray(best["index"], dtype=np.int64)
+        found = index >= 0
+        count = np.diff(p_offsets)
+        with np.errstate(invalid="ignore"):
+            period = np.where(found, _linspace_at(start, step, stop, count, np.where(found, index, 0)), np.nan)
+        start_bin = np.where(found, best["start_bin"], np.nan)
+        box_bins = np.where(found, best["box_bins"], np.nan)
+        self.best = {"index": np.where(found, index, -1), "period": period,
+                     "power": np.where(found, best["power"], np.nan), "depth": np.where(found, best["depth"], np.nan),
+                     "duration": box_bins / n_bins * period,
+                     "transit_time": ((start_bin + box_bins / 2) / n_bins % 1) * period}
+
+
+def _bls_batch(scan, signals, errs, peaks, by_prominence, want_power):
+    """The batch of :class:`BLS` (``pdc_bls_scan_ragged``): every curve on exactly the grid its own single call would
+    scan (``_pdm_limits``), with that call's weights (``errs``, as ``GLS.batch`` takes them)."""
+    from .spectral import PeakTable
+    len_min, len_max = scan.box_lengths()
+    signals = [s if isinstance(s, TSeries) else _coerce(s) for s in signals]   # (an empty TSeries has no baseline to probe)
+    if not signals:
+        raise ValueError("BLS.batch needs at least one signal")
+    if errs is not None:
+        errs = list(errs)
+        if len(errs) != len(signals):
+            raise ValueError(f"errs has {len(errs)} entries for {len(signals)} signals")
+    peaks = int(peaks)
+    if peaks < 0 or peaks > 1024:
+        raise ValueError("peaks must be 0 .. 1024")
+    values = [np.asarray(s.values, dtype=float) for s in signals]
+    sizes = np.array([v.size for v in values], dtype=np.int64)
+    # (a curve without samples has no grid of its own: its row is empty and its best entries are -1 / NaN)
+    limits = [_pdm_limits(s, scan.p_min, scan.p_max, scan.n_periods, scan.oversample) if s.size else (0.0, 0.0, 0)
+              for s in signals]
+    start = np.array([lim[0] for lim in limits], dtype=np.float64)
+    stop = np.array([lim[1] for lim in limits], dtype=np.float64)
+    count = np.array([lim[2] for lim in limits], dtype=np.int64)
+    if (count < 0).any():
+        b = int(np.argmax(count < 0))
+        raise ValueError(f"curve {b}: number of samples, {count[b]}, must be non-negative")
+    step = _linspace_steps(start, stop, count)
+    if peaks:
+        _check_fseries_order(start, step, stop, count)
+    dy = None
+    if errs is not None and any(e is not None for e in errs):
+        parts = []
+        for v, e in zip(values, errs):
+            e = np.ones(v.size) if e is None else np.asarray(e, dtype=float).ravel()
+            if e.size != v.size:
+                raise ValueError("Input arrays have incompatible lengths.")
+            parts.append(e)
+        dy = np.concatenate(parts)
+    offsets = np.zeros(len(signals) + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum(sizes)
+    p_offsets = np.zeros(len(signals) + 1, dtype=np.int64)
+    p_offsets[1:] = np.cumsum(count)
+    t = np.concatenate([np.asarray(s.time, dtype=float) for s in signals])
+    y = np.concatenate(values)
+    devices = scan.devices if scan.devices else None
+    rows, best, table = _cabi.bls_scan_ragged(t, y, dy, offsets, start, step, stop, p_offsets, int(scan.n_bins), len_min,
+                                              len_max, int(scan.min_points), scan.dips_only, k=peaks,
+                                              by_prominence=by_prominence, want_power=want_power, device=scan.device,
+                                              devices=devices)
+    res = BLSBatch(start, step, stop, p_offsets, scan.n_bins, rows, best, None)
+    if table is not None:
+        res.peaks = PeakTable(None, table, by_prominence, frequency_at=res._frequency_at)
+    return res
 
 
 def _string_batch(scan, signals, peaks, by_prominence, want_power):
@@ -693,6 +783,7 @@ class BLS(object):
         self.dips_only = bool(dips_only)
         self.cores = cores
         self.device = device
+        self.devices = None   # device slots of batch(): an attribute, set after construction (a GPU may repeat)
         self.box_lengths()
 
     def box_lengths(self):
@@ -740,3 +831,26 @@ class BLS(object):
                       ("transit_time", self.transit_time))}
         self.periodogram = FSeries(1 / periods, power)
         return self.periodogram
+
+    def batch(self, signals, errs=None, *, peaks=0, by_prominence=False, want_power=True):
+        """Box searches of many light curves, each on the grid its own data give (``_pdm_periods`` per curve), in one
+        set of launches (``pdc_bls_scan_ragged`` / ``pdc_bls_ragged_peaks``): what a loop of ``BLS(...)(s, e)`` gives,
+        bit for bit, without a launch per curve.  Returns a :class:`BLSBatch`; its ``best`` (one line per curve:
+        period, power, depth, duration, transit time of the highest power) is found on the device.
+
+        errs: None, or a sequence (one entry per signal) of arrays or Nones (ones)
+        peaks: int, keyword-only
+            ``k > 0`` (<= 1024): also the ``k`` highest (``find_peaks``) maxima of every power row, found on the
+            device (``BLSBatch.peaks``).
+        by_prominence: bool, keyword-only
+            Rank them by prominence instead.
+        want_power: bool, keyword-only
+            ``False``: the four per-period rows stay on the device (``periodograms``, ``power`` ... are None); ``best``
+            and the peak table are still returned.
+
+        ``n_bins``, the box lengths, ``min_points`` and ``dips_only`` are the object's, shared by all curves.  With the
+        attribute ``devices`` set (``scan.devices = (0, 1)``; the constructor's parameter list is unchanged) the curves
+        are dealt to those device slots in contiguous groups balanced by ``sum n_b P_b``; else they run on ``device``.
+        A curve without samples has no grid of its own: its rows are empty and its ``best`` entries are -1 / NaN.
+        The object's own attributes (``periods``, ``periodogram`` ...) are left as they were."""
+        return _bls_batch(self, signals, errs, peaks, by_prominence, want_power)
