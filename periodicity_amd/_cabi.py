@@ -564,6 +564,11 @@ def _topk_outputs(nb, k):
             "half_lo": np.empty((nb, k), dtype=np.int64), "half_hi": np.empty((nb, k), dtype=np.int64)}
 
 
+def _table_ptrs(table):
+    """A peak table's six arrays as pointers, in the order every ``pdc_*peaks*`` entry takes them."""
+    return tuple(_ptr(table[name]) for name in ("count", "indices", "heights", "prominences", "half_lo", "half_hi"))
+
+
 def peaks_topk(power, k=1, by_prominence=False, device=None):
     """The ``k`` (<= 1024; beyond 128 in launches of 128 ranks) highest, or most prominent, ``find_peaks`` maxima of each row of ``power`` with
     prominences and half-maximum crossings (``pdc_peaks_topk``); a dict of arrays shaped ``[rows, k]``
@@ -573,8 +578,7 @@ def peaks_topk(power, k=1, by_prominence=False, device=None):
     out = _topk_outputs(rows.shape[0], int(k))
     dev = default_device() if device is None else device
     check(lib().pdc_peaks_topk(_ptr(rows), rows.shape[0], rows.shape[1], int(k), int(bool(by_prominence)),
-                               _ptr(out["count"]), _ptr(out["indices"]), _ptr(out["heights"]),
-                               _ptr(out["prominences"]), _ptr(out["half_lo"]), _ptr(out["half_hi"]), dev))
+                               *_table_ptrs(out), dev))
     return out
 
 
@@ -593,9 +597,7 @@ def gls_batch_peaks(t, y, dy, offsets, f0, delta, nf, k=1, by_prominence=False, 
     dev = default_device() if device is None else device
     check(lib().pdc_gls_batch_peaks(_ptr(t), _ptr(y), _ptr(dy), _ptr(offsets), nb, int(shared_t), f0,
                                     delta, nf, int(bool(fit_mean)), int(bool(psd)), int(k),
-                                    int(bool(by_prominence)), _ptr(out["count"]), _ptr(out["indices"]),
-                                    _ptr(out["heights"]), _ptr(out["prominences"]), _ptr(out["half_lo"]),
-                                    _ptr(out["half_hi"]), dev))
+                                    int(bool(by_prominence)), *_table_ptrs(out), dev))
     return out
 
 
@@ -644,10 +646,25 @@ def gls_ragged_peaks(t, y, dy, offsets, f0, delta, f_offsets, k=1, by_prominence
     devs = _slots(device, devices)
     check(lib().pdc_gls_ragged_peaks(_ptr(t), _ptr(y), _ptr(dy), _ptr(offsets), nb, _ptr(f0), _ptr(delta),
                                      _ptr(f_offsets), int(bool(fit_mean)), int(bool(psd)), int(k),
-                                     int(bool(by_prominence)), _ptr(out["count"]), _ptr(out["indices"]),
-                                     _ptr(out["heights"]), _ptr(out["prominences"]), _ptr(out["half_lo"]),
-                                     _ptr(out["half_hi"]), _ptr(out["power"]), _ptr(devs), devs.size))
+                                     int(bool(by_prominence)), *_table_ptrs(out), _ptr(out["power"]), _ptr(devs),
+                                     devs.size))
     return out
+
+
+def _linspace_inputs(t, v, dy, offsets, start, step, stop, p_offsets, names):
+    """The inputs of a batch whose curves each have a linspace grid, converted and checked: ``(t, v, dy, offsets,
+    start, step, stop, p_offsets, n_curves)``; ``names``: what ``t`` and ``v`` are called in a message."""
+    t, v = _f64(t, names[0]), _f64(v, names[1])
+    dy = None if dy is None else _f64(dy, "dy")
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    p_offsets = np.ascontiguousarray(p_offsets, dtype=np.int64)
+    start, step, stop = _f64(start, "start"), _f64(step, "step"), _f64(stop, "stop")
+    nb = offsets.size - 1
+    if nb < 1 or p_offsets.size != nb + 1 or any(a.size != nb for a in (start, step, stop)):
+        raise ValueError("offsets / p_offsets need n_curves + 1 entries, start / step / stop n_curves")
+    if offsets[-1] != t.size or v.size != t.size or (dy is not None and dy.size != t.size):
+        raise ValueError("Input arrays have incompatible lengths.")
+    return t, v, dy, offsets, start, step, stop, p_offsets, nb
 
 
 def phase_scan_ragged(kind, t, x, offsets, start, step, stop, p_offsets, nb, nc, sigma=None, significant=None,
@@ -655,17 +672,10 @@ def phase_scan_ragged(kind, t, x, offsets, start, step, stop, p_offsets, nb, nc,
     """PDM (kind 0), AoV (1) or conditional entropy (2) over a batch of curves, each on its own period grid
     ``linspace(start[b], stop[b], p_offsets[b+1] - p_offsets[b])`` (``pdc_phase_scan_ragged``; with ``k > 0``
     ``pdc_phase_ragged_peaks``): ``(out [p_offsets[-1]] | None, peak table dict | None)``."""
-    t, x = _f64(t, "t"), _f64(x, "x")
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    p_offsets = np.ascontiguousarray(p_offsets, dtype=np.int64)
-    start, step, stop = _f64(start, "start"), _f64(step, "step"), _f64(stop, "stop")
+    t, x, _, offsets, start, step, stop, p_offsets, nb_ = _linspace_inputs(t, x, None, offsets, start, step, stop,
+                                                                           p_offsets, "tx")
     sigma = None if sigma is None else _f64(sigma, "sigma")
     significant = None if significant is None else _f64(significant, "significant")
-    nb_ = offsets.size - 1
-    if nb_ < 1 or p_offsets.size != nb_ + 1 or any(a.size != nb_ for a in (start, step, stop)):
-        raise ValueError("offsets / p_offsets need n_curves + 1 entries, start / step / stop n_curves")
-    if offsets[-1] != t.size or x.size != t.size:
-        raise ValueError("Input arrays have incompatible lengths.")
     out = np.empty(int(p_offsets[-1]), dtype=np.float64) if want_power else None
     devs = _slots(device, devices)
     common = (int(kind), _ptr(t), _ptr(x), _ptr(offsets), nb_, _ptr(start), _ptr(step), _ptr(stop), _ptr(p_offsets),
@@ -674,9 +684,8 @@ def phase_scan_ragged(kind, t, x, offsets, start, step, stop, p_offsets, nb, nc,
         check(lib().pdc_phase_scan_ragged(*common, _ptr(out), _ptr(devs), devs.size))
         return out, None
     table = _topk_outputs(nb_, int(k))
-    check(lib().pdc_phase_ragged_peaks(*common, int(k), int(bool(by_prominence)), _ptr(table["count"]),
-                                       _ptr(table["indices"]), _ptr(table["heights"]), _ptr(table["prominences"]),
-                                       _ptr(table["half_lo"]), _ptr(table["half_hi"]), _ptr(out), _ptr(devs), devs.size))
+    check(lib().pdc_phase_ragged_peaks(*common, int(k), int(bool(by_prominence)), *_table_ptrs(table), _ptr(out),
+                                       _ptr(devs), devs.size))
     return out, table
 
 
@@ -687,16 +696,8 @@ def bls_scan_ragged(t, y, dy, offsets, start, step, stop, p_offsets, n_bins, len
     ``(rows | None, best, peak table dict | None)``.  ``rows``: the dict ``power, depth, start_bin, box_bins``
     ``[p_offsets[-1]]`` (None without ``want_power``: they stay on the device); ``best``: the dict ``index, power,
     depth, start_bin, box_bins`` ``[n_curves]`` of every row's first maximum, found on the device."""
-    t, y = _f64(t, "t"), _f64(y, "y")
-    dy = None if dy is None else _f64(dy, "dy")
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    p_offsets = np.ascontiguousarray(p_offsets, dtype=np.int64)
-    start, step, stop = _f64(start, "start"), _f64(step, "step"), _f64(stop, "stop")
-    nb_ = offsets.size - 1
-    if nb_ < 1 or p_offsets.size != nb_ + 1 or any(a.size != nb_ for a in (start, step, stop)):
-        raise ValueError("offsets / p_offsets need n_curves + 1 entries, start / step / stop n_curves")
-    if offsets[-1] != t.size or y.size != t.size or (dy is not None and dy.size != t.size):
-        raise ValueError("Input arrays have incompatible lengths.")
+    t, y, dy, offsets, start, step, stop, p_offsets, nb_ = _linspace_inputs(t, y, dy, offsets, start, step, stop,
+                                                                            p_offsets, "ty")
     total = max(int(p_offsets[-1]), 0)
     rows = None
     if want_power:
@@ -714,9 +715,8 @@ def bls_scan_ragged(t, y, dy, offsets, start, step, stop, p_offsets, n_bins, len
         check(lib().pdc_bls_scan_ragged(*common, *outs, _ptr(devs), devs.size))
         return rows, best, None
     table = _topk_outputs(nb_, int(k))
-    check(lib().pdc_bls_ragged_peaks(*common, int(k), int(bool(by_prominence)), _ptr(table["count"]),
-                                     _ptr(table["indices"]), _ptr(table["heights"]), _ptr(table["prominences"]),
-                                     _ptr(table["half_lo"]), _ptr(table["half_hi"]), *outs, _ptr(devs), devs.size))
+    check(lib().pdc_bls_ragged_peaks(*common, int(k), int(bool(by_prominence)), *_table_ptrs(table), *outs, _ptr(devs),
+                                     devs.size))
     return rows, best, table
 
 
@@ -732,15 +732,8 @@ def stringlength_scan_ragged(t, m, offsets, start, step, stop, p_offsets, k=0, b
     """StringLength over a batch of curves, each on its own grid ``1 / linspace(start[b], stop[b], P_b)``
     (``pdc_stringlength_scan_ragged``; with ``k > 0`` ``pdc_stringlength_ragged_peaks``):
     ``(out [p_offsets[-1]] | None, peak table dict | None)``."""
-    t, m = _f64(t, "t"), _f64(m, "m")
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    p_offsets = np.ascontiguousarray(p_offsets, dtype=np.int64)
-    start, step, stop = _f64(start, "start"), _f64(step, "step"), _f64(stop, "stop")
-    nb_ = offsets.size - 1
-    if nb_ < 1 or p_offsets.size != nb_ + 1 or any(a.size != nb_ for a in (start, step, stop)):
-        raise ValueError("offsets / p_offsets need n_curves + 1 entries, start / step / stop n_curves")
-    if offsets[-1] != t.size or m.size != t.size:
-        raise ValueError("Input arrays have incompatible lengths.")
+    t, m, _, offsets, start, step, stop, p_offsets, nb_ = _linspace_inputs(t, m, None, offsets, start, step, stop,
+                                                                           p_offsets, "tm")
     out = np.empty(int(p_offsets[-1]), dtype=np.float64) if want_power else None
     devs = _slots(device, devices)
     common = (_ptr(t), _ptr(m), _ptr(offsets), nb_, _ptr(start), _ptr(step), _ptr(stop), _ptr(p_offsets))
@@ -748,10 +741,8 @@ def stringlength_scan_ragged(t, m, offsets, start, step, stop, p_offsets, k=0, b
         check(lib().pdc_stringlength_scan_ragged(*common, _ptr(out), _ptr(devs), devs.size))
         return out, None
     table = _topk_outputs(nb_, int(k))
-    check(lib().pdc_stringlength_ragged_peaks(*common, int(k), int(bool(by_prominence)), _ptr(table["count"]),
-                                              _ptr(table["indices"]), _ptr(table["heights"]),
-                                              _ptr(table["prominences"]), _ptr(table["half_lo"]),
-                                              _ptr(table["half_hi"]), _ptr(out), _ptr(devs), devs.size))
+    check(lib().pdc_stringlength_ragged_peaks(*common, int(k), int(bool(by_prominence)), *_table_ptrs(table), _ptr(out),
+                                              _ptr(devs), devs.size))
     return out, table
 
 
@@ -762,99 +753,58 @@ def sl_ragged_stats():
     return g.value, mk.value, lc.value
 
 
+def _period_scan(entry, arrays, periods, params, device, devices):
+    """Behind the six single-grid scans: ``arrays`` (``(name, values)`` pairs, all of one length) and ``periods``
+    converted and checked, then ``pdc_<entry>`` on one device, or ``pdc_<entry>_multi`` when ``devices`` lists more than
+    one: one contiguous slab of the period grid per entry."""
+    arrays = [_f64(a, name) for name, a in arrays]
+    periods = _f64(periods, "periods")
+    if any(a.size != arrays[0].size for a in arrays):
+        raise ValueError("Input arrays have incompatible lengths.")
+    out = np.empty(periods.size, dtype=np.float64)
+    args = (*[_ptr(a) for a in arrays], arrays[0].size, _ptr(periods), periods.size, *params, _ptr(out))
+    if devices is not None and len(devices) > 1:
+        devs = np.ascontiguousarray(devices, dtype=np.int32)
+        check(getattr(lib(), f"pdc_{entry}_multi")(*args, _ptr(devs), devs.size))
+        return out
+    device = pick_device(device, devices)
+    check(getattr(lib(), f"pdc_{entry}")(*args, default_device() if device is None else device))
+    return out
+
+
 def pdm_scan(t, x, periods, nb, nc, sigma, device=None, devices=None):
     """theta at every trial period; ``devices`` (a sequence of GPU ordinals) cuts the period grid
     into one contiguous slab per entry (``pdc_pdm_scan_multi``)."""
-    t, x, periods = _f64(t, "t"), _f64(x, "x"), _f64(periods, "periods")
-    if x.size != t.size:
-        raise ValueError("Input arrays have incompatible lengths.")
-    out = np.empty(periods.size, dtype=np.float64)
-    if devices is not None and len(devices) > 1:
-        devs = np.ascontiguousarray(devices, dtype=np.int32)
-        check(lib().pdc_pdm_scan_multi(_ptr(t), _ptr(x), t.size, _ptr(periods), periods.size, int(nb),
-                                       int(nc), float(sigma), _ptr(out), _ptr(devs), devs.size))
-        return out
-    device = pick_device(device, devices)
-    dev = default_device() if device is None else device
-    check(lib().pdc_pdm_scan(_ptr(t), _ptr(x), t.size, _ptr(periods), periods.size, int(nb),
-                             int(nc), float(sigma), _ptr(out), dev))
-    return out
+    return _period_scan("pdm_scan", (("t", t), ("x", x)), periods, (int(nb), int(nc), float(sigma)), device, devices)
 
 
 def aov_scan(t, x, periods, n_bins, device=None, devices=None):
     """Analysis-of-Variance statistic at every trial period (``pdc_aov_scan``; ``devices`` as in
     :func:`pdm_scan`)."""
-    t, x, periods = _f64(t, "t"), _f64(x, "x"), _f64(periods, "periods")
-    if x.size != t.size:
-        raise ValueError("Input arrays have incompatible lengths.")
-    out = np.empty(periods.size, dtype=np.float64)
-    if devices is not None and len(devices) > 1:
-        devs = np.ascontiguousarray(devices, dtype=np.int32)
-        check(lib().pdc_aov_scan_multi(_ptr(t), _ptr(x), t.size, _ptr(periods), periods.size, int(n_bins),
-                                       _ptr(out), _ptr(devs), devs.size))
-        return out
-    device = pick_device(device, devices)
-    dev = default_device() if device is None else device
-    check(lib().pdc_aov_scan(_ptr(t), _ptr(x), t.size, _ptr(periods), periods.size, int(n_bins),
-                             _ptr(out), dev))
-    return out
+    return _period_scan("aov_scan", (("t", t), ("x", x)), periods, (int(n_bins),), device, devices)
 
 
 def cond_entropy_scan(t, mag_bin, periods, n_phase, n_mag, device=None, devices=None):
     """Conditional entropy at every trial period (``pdc_cond_entropy_scan``); ``mag_bin`` holds the
     magnitude bin (0 .. n_mag-1) of every sample; ``devices`` as in :func:`pdm_scan`."""
-    t, mag_bin, periods = _f64(t, "t"), _f64(mag_bin, "mag_bin"), _f64(periods, "periods")
-    if mag_bin.size != t.size:
-        raise ValueError("Input arrays have incompatible lengths.")
+    mag_bin = _f64(mag_bin, "mag_bin")
     if mag_bin.size and not (np.all(mag_bin >= 0) and np.all(mag_bin < n_mag)):
         raise ValueError("magnitude bins must lie in 0 .. n_mag-1")
-    out = np.empty(periods.size, dtype=np.float64)
-    if devices is not None and len(devices) > 1:
-        devs = np.ascontiguousarray(devices, dtype=np.int32)
-        check(lib().pdc_cond_entropy_scan_multi(_ptr(t), _ptr(mag_bin), t.size, _ptr(periods), periods.size,
-                                                int(n_phase), int(n_mag), _ptr(out), _ptr(devs), devs.size))
-        return out
-    device = pick_device(device, devices)
-    dev = default_device() if device is None else device
-    check(lib().pdc_cond_entropy_scan(_ptr(t), _ptr(mag_bin), t.size, _ptr(periods), periods.size,
-                                      int(n_phase), int(n_mag), _ptr(out), dev))
-    return out
+    return _period_scan("cond_entropy_scan", (("t", t), ("mag_bin", mag_bin)), periods, (int(n_phase), int(n_mag)),
+                        device, devices)
 
 
 def gl_scan(t, periods, m, n_offsets, device=None, devices=None):
     """Gregory-Loredo ``ln S_m`` at every trial period for the arrival times ``t`` (``pdc_gl_scan``): ``m``
     phase bins, the bin-offset integral as the mean over ``n_offsets`` shifts; ``devices`` as in
     :func:`pdm_scan`."""
-    t, periods = _f64(t, "t"), _f64(periods, "periods")
-    out = np.empty(periods.size, dtype=np.float64)
-    if devices is not None and len(devices) > 1:
-        devs = np.ascontiguousarray(devices, dtype=np.int32)
-        check(lib().pdc_gl_scan_multi(_ptr(t), t.size, _ptr(periods), periods.size, int(m), int(n_offsets),
-                                      _ptr(out), _ptr(devs), devs.size))
-        return out
-    device = pick_device(device, devices)
-    dev = default_device() if device is None else device
-    check(lib().pdc_gl_scan(_ptr(t), t.size, _ptr(periods), periods.size, int(m), int(n_offsets), _ptr(out), dev))
-    return out
+    return _period_scan("gl_scan", (("t", t),), periods, (int(m), int(n_offsets)), device, devices)
 
 
 def stringlength_scan(t, m, periods, device=None, devices=None):
     """String length at every trial period; ``devices`` as in :func:`pdm_scan`
     (``pdc_stringlength_scan_multi``)."""
-    t, m, periods = _f64(t, "t"), _f64(m, "m"), _f64(periods, "periods")
-    if m.size != t.size:
-        raise ValueError("Input arrays have incompatible lengths.")
-    out = np.empty(periods.size, dtype=np.float64)
-    if devices is not None and len(devices) > 1:
-        devs = np.ascontiguousarray(devices, dtype=np.int32)
-        check(lib().pdc_stringlength_scan_multi(_ptr(t), _ptr(m), t.size, _ptr(periods), periods.size,
-                                                _ptr(out), _ptr(devs), devs.size))
-        return out
-    device = pick_device(device, devices)
-    dev = default_device() if device is None else device
-    check(lib().pdc_stringlength_scan(_ptr(t), _ptr(m), t.size, _ptr(periods), periods.size,
-                                      _ptr(out), dev))
-    return out
+    return _period_scan("stringlength_scan", (("t", t), ("m", m)), periods, (), device, devices)
 
 
 PHASE_KINDS = {"pdm": 0, "aov": 1, "cond_entropy": 2, "stringlength": 3, "gregory_loredo": 4, "supersmoother": 5}
@@ -863,20 +813,7 @@ PHASE_KINDS = {"pdm": 0, "aov": 1, "cond_entropy": 2, "stringlength": 3, "gregor
 def supersmoother_scan(t, y, periods, alpha=0.0, device=None, devices=None):
     """Mean absolute residual of the folded curve about its supersmoother fit at every trial period
     (``pdc_supersmoother_scan``; Friedman 1984 + Reimann 1994, a TODO upstream)."""
-    t, y = _f64(t, "t"), _f64(y, "y")
-    periods = _f64(periods, "periods")
-    if y.size != t.size:
-        raise ValueError("Input arrays have incompatible lengths.")
-    out = np.empty(periods.size, dtype=np.float64)
-    if devices is not None and len(devices) > 1:
-        devs = np.ascontiguousarray(devices, dtype=np.int32)
-        check(lib().pdc_supersmoother_scan_multi(_ptr(t), _ptr(y), t.size, _ptr(periods), periods.size, float(alpha),
-                                                 _ptr(out), _ptr(devs), devs.size))
-        return out
-    device = pick_device(device, devices)
-    dev = default_device() if device is None else device
-    check(lib().pdc_supersmoother_scan(_ptr(t), _ptr(y), t.size, _ptr(periods), periods.size, float(alpha), _ptr(out), dev))
-    return out
+    return _period_scan("supersmoother_scan", (("t", t), ("y", y)), periods, (float(alpha),), device, devices)
 
 
 class PhasePlan:

@@ -29,6 +29,48 @@ def _is_sorted(a):
     return a.size < 2 or bool(np.all(a[1:] >= a[:-1]))
 
 
+# ---- what the batch front ends share (GLS.batch in spectral.py, the five of phase.py) ----------------------------------
+def _batch_request(peaks, want_power=True):
+    """``peaks`` of a ``batch`` call as an int in 0 .. 1024; a call that keeps its rows on the device asks for a table."""
+    peaks = int(peaks)
+    if peaks < 0 or peaks > 1024:
+        raise ValueError("peaks must be 0 .. 1024")
+    if not want_power and peaks == 0:
+        raise ValueError("nothing requested: want_power=False needs peaks > 0")
+    return peaks
+
+
+def _batch_offsets(sizes):
+    """``[0, sizes[0], sizes[0] + sizes[1], ...]``: where each curve's samples (or rows) start in the stacked arrays."""
+    offsets = np.zeros(len(sizes) + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum(sizes)
+    return offsets
+
+
+def _batch_errs(errs, sizes):
+    """``errs`` of a ``batch`` call (None, or one array or None per signal) stacked like the samples, ones where an
+    entry is None; None when no curve has uncertainties of its own."""
+    if errs is None:
+        return None
+    errs = list(errs)
+    if len(errs) != len(sizes):
+        raise ValueError(f"errs has {len(errs)} entries for {len(sizes)} signals")
+    if all(e is None for e in errs):
+        return None
+    parts = []
+    for n, e in zip(sizes, errs):
+        e = np.ones(n) if e is None else np.asarray(e, dtype=float).ravel()
+        if e.size != n:
+            raise ValueError("Input arrays have incompatible lengths.")
+        parts.append(e)
+    return np.concatenate(parts)
+
+
+def _batch_slots(devices):
+    """The device slots of a ``batch`` call: the object's ``devices``, or None (its ``device``) when there are none."""
+    return devices if devices else None
+
+
 class Signal(np.lib.mixins.NDArrayOperatorsMixin):
     """A value array labelled by one monotonically increasing coordinate."""
 

@@ -180,18 +180,20 @@ struct BlsLayout {
     int64_t scal, meta, rec, power, depth, start_bin, box_bins, pitched, total;
 };
 constexpr int kMetaArrays = 7;   // offsets | poff | operiod | order (int64) | start | step | stop, B + 1 each
+enum { M_OFF, M_POFF, M_OPERIOD, M_ORDER, M_START, M_STEP, M_STOP };
 
 BlsLayout bls_layout(int64_t n_curves, int64_t n_total, int64_t p_total, int64_t p_max, int k, bool own_power,
                      bool own_depth, bool own_start, bool own_box) {
     BlsLayout w;
-    w.scal = 0;
-    w.meta = up256(n_curves * 32);
-    w.rec = w.meta + up256(kMetaArrays * (n_curves + 1) * 8);
-    w.power = w.rec + up256((n_total > 0 ? n_total : 1) * (int64_t)sizeof(BlsRec));
-    w.depth = w.power + (own_power ? up256(p_total * 8) : 0);
-    w.start_bin = w.depth + (own_depth ? up256(p_total * 8) : 0);
-    w.box_bins = w.start_bin + (own_start ? up256(p_total * 4) : 0);
-    w.pitched = w.box_bins + (own_box ? up256(p_total * 4) : 0);
+    Carve c;
+    w.scal = c.take(n_curves * 32);
+    w.meta = c.take(kMetaArrays * (n_curves + 1) * 8);
+    w.rec = c.take((n_total > 0 ? n_total : 1) * (int64_t)sizeof(BlsRec));
+    w.power = c.take(own_power ? p_total * 8 : 0);
+    w.depth = c.take(own_depth ? p_total * 8 : 0);
+    w.start_bin = c.take(own_start ? p_total * 4 : 0);
+    w.box_bins = c.take(own_box ? p_total * 4 : 0);
+    w.pitched = c.at;
     w.total = w.pitched + ragged_table_bytes(n_curves, p_max, k);
     return w;
 }
@@ -211,7 +213,7 @@ int validate(const char *what, const int64_t *offsets, int64_t n_curves, const d
 int bls_ragged_dev(int device, hipStream_t st, const double *d_t, const double *d_y, const double *d_dy,
                    const int64_t *offsets, int64_t n_curves, const double *start, const double *step, const double *stop,
                    const int64_t *poff, const BlsParams &q, const BlsOut &out, double *d_pitched, int64_t pitch, void *work,
-                   int64_t work_bytes, std::vector<int64_t> &meta, bool wait_meta) {
+                   int64_t work_bytes, std::vector<int64_t> &host_meta, bool wait_meta) {
     const int64_t n_total = offsets[n_curves], p_total = poff[n_curves];
     const BlsLayout w = bls_layout(n_curves, n_total, p_total, 0, 0, !out.power, !out.depth, !out.start_bin,
                                    !out.box_bins);   // (the pitched copy is the caller's)
@@ -221,37 +223,24 @@ int bls_ragged_dev(int device, hipStream_t st, const double *d_t, const double *
     PDC_TRY(use_device(device));
     char *base = static_cast<char *>(work);
     // metadata: one upload; dispatch order = ragged_order (costliest curve first)
-    const int64_t B1 = n_curves + 1;
-    meta.assign((size_t)(kMetaArrays * B1), 0);
-    int64_t *m_off = meta.data(), *m_poff = m_off + B1, *m_operiod = m_poff + B1, *m_order = m_operiod + B1;
-    double *m_start = reinterpret_cast<double *>(m_order + B1), *m_step = m_start + B1, *m_stop = m_step + B1;
-    for (int64_t b = 0; b < n_curves; ++b) {
-        m_off[b] = offsets[b];
-        m_poff[b] = poff[b];
-        m_start[b] = start[b];
-        m_step[b] = step[b];
-        m_stop[b] = stop[b];
-    }
-    m_off[n_curves] = n_total;
-    m_poff[n_curves] = p_total;
-    const int64_t m = ragged_order(offsets, poff, n_curves, 1, m_order, m_operiod);
-    const int64_t groups = m_operiod[m];   // == p_total
-    int64_t *d_meta = reinterpret_cast<int64_t *>(base + w.meta);
-    PDC_HIP(hipMemcpyAsync(d_meta, meta.data(), (size_t)(kMetaArrays * B1 * 8), hipMemcpyHostToDevice, st));
-    if (wait_meta) PDC_HIP(hipStreamSynchronize(st));   // (`meta` goes when the caller returns)
-    const double *d_dbl = reinterpret_cast<const double *>(d_meta + 4 * B1);
+    RaggedMeta meta(host_meta, kMetaArrays, n_curves, base + w.meta);
+    meta.fill_offsets(offsets, poff);
+    meta.fill_linspace(M_START, start, step, stop);
+    const int64_t m = ragged_order(offsets, poff, n_curves, 1, meta.i64(M_ORDER), meta.i64(M_OPERIOD));
+    const int64_t groups = meta.i64(M_OPERIOD)[m];   // == p_total
+    PDC_TRY(meta.upload(st, wait_meta));
 
     BlsRaggedArgs a = {};
     a.t = d_t;
     a.y = d_y;
     a.dy = d_dy;
-    a.offsets = d_meta;
-    a.poff = d_meta + B1;
-    a.operiod = d_meta + 2 * B1;
-    a.order = d_meta + 3 * B1;
-    a.start = d_dbl;
-    a.step = d_dbl + B1;
-    a.stop = d_dbl + 2 * B1;
+    a.offsets = meta.d_i64(M_OFF);
+    a.poff = meta.d_i64(M_POFF);
+    a.operiod = meta.d_i64(M_OPERIOD);
+    a.order = meta.d_i64(M_ORDER);
+    a.start = meta.d_f64(M_START);
+    a.step = meta.d_f64(M_STEP);
+    a.stop = meta.d_f64(M_STOP);
     a.m = m;
     a.n_bins = q.n_bins;
     a.len_min = q.len_min;
@@ -296,6 +285,13 @@ struct BlsJob : RaggedBatch {
     const double *start, *step, *stop;
     BlsOut out;
 
+    BlsJob(const double *t_, const double *y_, const double *dy_, const int64_t *offsets_, const double *start_,
+           const double *step_, const double *stop_, const int64_t *p_offsets, const BlsParams &q_, const BlsOut &out_)
+        : q(q_), t(t_), y(y_), dy(dy_), start(start_), step(step_), stop(stop_), out(out_) {
+        offsets = offsets_;
+        rows = p_offsets;
+    }
+
     // The slot buffer of the group [c0, c1) whose longest grid has p_max periods: inputs | rows | best | workspace.
     struct Bytes {
         int64_t in_t, in_y, in_dy, power, depth, start_bin, box_bins, best_index, best_power, best_depth, best_start,
@@ -304,82 +300,54 @@ struct BlsJob : RaggedBatch {
     Bytes bytes(int64_t c0, int64_t c1, int64_t p_max) const {
         const int64_t n = offsets[c1] - offsets[c0], np = rows[c1] - rows[c0], B = c1 - c0;
         Bytes g;
-        g.in_t = 0;
-        g.in_y = up256(n * 8);
-        g.in_dy = g.in_y + up256(n * 8);
-        g.power = g.in_dy + (dy ? up256(n * 8) : 0);
-        g.depth = g.power + up256(np * 8);
-        g.start_bin = g.depth + up256(np * 8);
-        g.box_bins = g.start_bin + up256(np * 4);
-        g.best_index = g.box_bins + up256(np * 4);
-        g.best_power = g.best_index + up256(B * 8);
-        g.best_depth = g.best_power + up256(B * 8);
-        g.best_start = g.best_depth + up256(B * 8);
-        g.best_box = g.best_start + up256(B * 4);
-        g.work = g.best_box + up256(B * 4);
+        Carve c;
+        g.in_t = c.take(n * 8);
+        g.in_y = c.take(n * 8);
+        g.in_dy = c.take(dy ? n * 8 : 0);
+        g.power = c.take(np * 8);
+        g.depth = c.take(np * 8);
+        g.start_bin = c.take(np * 4);
+        g.box_bins = c.take(np * 4);
+        g.best_index = c.take(B * 8);
+        g.best_power = c.take(B * 8);
+        g.best_depth = c.take(B * 8);
+        g.best_start = c.take(B * 4);
+        g.best_box = c.take(B * 4);
+        g.work = c.at;
         g.total = g.work + bls_layout(B, n, np, p_max, k, false, false, false, false).total;
         return g;
     }
     int64_t group_bytes(int64_t c0, int64_t c1, int64_t p_max) const override { return bytes(c0, c1, p_max).total; }
 
     int run_group(RaggedSlot &s, int64_t c0, int64_t c1, int64_t p_max, double *pitched) const override {
-        const int64_t B = c1 - c0, s0 = offsets[c0], n = offsets[c1] - s0, pb = rows[c0], np = rows[c1] - pb;
-        const Bytes g = bytes(c0, c1, p_max);
-        char *p = static_cast<char *>(s.buf);
-        hipStream_t st = s.stream;
-        if (n > 0) {
-            PDC_HIP(hipMemcpyAsync(p + g.in_t, t + s0, n * 8, hipMemcpyHostToDevice, st));
-            PDC_HIP(hipMemcpyAsync(p + g.in_y, y + s0, n * 8, hipMemcpyHostToDevice, st));
-            if (dy) PDC_HIP(hipMemcpyAsync(p + g.in_dy, dy + s0, n * 8, hipMemcpyHostToDevice, st));
-        }
-        std::vector<int64_t> off((size_t)B + 1), poff((size_t)B + 1);
-        for (int64_t b = 0; b <= B; ++b) {
-            off[(size_t)b] = offsets[c0 + b] - s0;
-            poff[(size_t)b] = rows[c0 + b] - pb;
-        }
-        BlsOut d = {};
-        d.power = (double *)(p + g.power);
-        d.depth = (double *)(p + g.depth);
-        d.start_bin = (int32_t *)(p + g.start_bin);
-        d.box_bins = (int32_t *)(p + g.box_bins);
-        if (out.best_index) d.best_index = (int64_t *)(p + g.best_index);
-        if (out.best_power) d.best_power = (double *)(p + g.best_power);
-        if (out.best_depth) d.best_depth = (double *)(p + g.best_depth);
-        if (out.best_start) d.best_start = (int32_t *)(p + g.best_start);
-        if (out.best_box) d.best_box = (int32_t *)(p + g.best_box);
-        PDC_TRY(bls_ragged_dev(s.device, st, (const double *)(p + g.in_t), (const double *)(p + g.in_y),
-                               dy ? (const double *)(p + g.in_dy) : nullptr, off.data(), B, start + c0, step + c0, stop + c0,
-                               poff.data(), q, d, pitched, p_max, p + g.work, g.total - g.work, s.meta, false));
-        if (np > 0) {
-            if (out.power) PDC_HIP(hipMemcpyAsync(out.power + pb, d.power, np * 8, hipMemcpyDeviceToHost, st));
-            if (out.depth) PDC_HIP(hipMemcpyAsync(out.depth + pb, d.depth, np * 8, hipMemcpyDeviceToHost, st));
-            if (out.start_bin) PDC_HIP(hipMemcpyAsync(out.start_bin + pb, d.start_bin, np * 4, hipMemcpyDeviceToHost, st));
-            if (out.box_bins) PDC_HIP(hipMemcpyAsync(out.box_bins + pb, d.box_bins, np * 4, hipMemcpyDeviceToHost, st));
-        }
-        if (out.best_index) PDC_HIP(hipMemcpyAsync(out.best_index + c0, d.best_index, B * 8, hipMemcpyDeviceToHost, st));
-        if (out.best_power) PDC_HIP(hipMemcpyAsync(out.best_power + c0, d.best_power, B * 8, hipMemcpyDeviceToHost, st));
-        if (out.best_depth) PDC_HIP(hipMemcpyAsync(out.best_depth + c0, d.best_depth, B * 8, hipMemcpyDeviceToHost, st));
-        if (out.best_start) PDC_HIP(hipMemcpyAsync(out.best_start + c0, d.best_start, B * 4, hipMemcpyDeviceToHost, st));
-        if (out.best_box) PDC_HIP(hipMemcpyAsync(out.best_box + c0, d.best_box, B * 4, hipMemcpyDeviceToHost, st));
-        return PDC_OK;
+        const RaggedGroup g(*this, s, c0, c1);
+        const Bytes at = bytes(c0, c1, p_max);
+        PDC_TRY(g.upload(at.in_t, t));
+        PDC_TRY(g.upload(at.in_y, y));
+        PDC_TRY(g.upload(at.in_dy, dy));
+        const BlsOut d = {g.at<double>(at.power),
+                          g.at<double>(at.depth),
+                          g.at<int32_t>(at.start_bin),
+                          g.at<int32_t>(at.box_bins),
+                          g.at_if<int64_t>(out.best_index, at.best_index),
+                          g.at_if<double>(out.best_power, at.best_power),
+                          g.at_if<double>(out.best_depth, at.best_depth),
+                          g.at_if<int32_t>(out.best_start, at.best_start),
+                          g.at_if<int32_t>(out.best_box, at.best_box)};
+        PDC_TRY(bls_ragged_dev(s.device, g.st, g.at<double>(at.in_t), g.at<double>(at.in_y), g.at_if<double>(dy, at.in_dy),
+                               g.off.data(), g.B, start + c0, step + c0, stop + c0, g.roff.data(), q, d, pitched, p_max,
+                               g.buf + at.work, at.total - at.work, s.meta, false));
+        PDC_TRY(g.rows_back(out.power, at.power));
+        PDC_TRY(g.rows_back(out.depth, at.depth));
+        PDC_TRY(g.rows_back(out.start_bin, at.start_bin));
+        PDC_TRY(g.rows_back(out.box_bins, at.box_bins));
+        PDC_TRY(g.curves_back(out.best_index, at.best_index));
+        PDC_TRY(g.curves_back(out.best_power, at.best_power));
+        PDC_TRY(g.curves_back(out.best_depth, at.best_depth));
+        PDC_TRY(g.curves_back(out.best_start, at.best_start));
+        return g.curves_back(out.best_box, at.best_box);
     }
 };
-
-BlsJob make_job(const double *t, const double *y, const double *dy, const int64_t *offsets, const double *start,
-                const double *step, const double *stop, const int64_t *p_offsets, const BlsParams &q, const BlsOut &out) {
-    BlsJob j = {};
-    j.q = q;
-    j.t = t;
-    j.y = y;
-    j.dy = dy;
-    j.offsets = offsets;
-    j.rows = p_offsets;
-    j.start = start;
-    j.step = step;
-    j.stop = stop;
-    j.out = out;
-    return j;
-}
 
 int bls_host(const char *what, const BlsJob &j, int64_t n_curves, const int *devices, int n_devices) {
     PDC_REQUIRE(j.offsets[n_curves] == 0 || (j.t && j.y), "%s: t and y must not be NULL", what);
@@ -417,10 +385,7 @@ int pdc_bls_scan_ragged_dev(int device, void *stream, const double *d_t, const d
     const BlsOut out = {d_power, d_depth, d_start_bin, d_box_bins, d_best_index, d_best_power, d_best_depth, d_best_start,
                         d_best_box};
     PDC_REQUIRE(out.any() || d_pitched, "bls_ragged_dev: no output requested");
-    if (d_pitched)
-        for (int64_t b = 0; b < n_curves; ++b)
-            PDC_REQUIRE(p_offsets[b + 1] - p_offsets[b] <= pitch, "bls_ragged_dev: curve %lld has more periods than the pitch",
-                        (long long)b);
+    if (d_pitched) PDC_TRY(ragged_check_pitch("bls_ragged_dev", p_offsets, n_curves, pitch, "periods"));
     std::vector<int64_t> meta;
     return bls_ragged_dev(device, (hipStream_t)stream, d_t, d_y, d_dy, offsets, n_curves, start, step, stop, p_offsets, q,
                           out, d_pitched, pitch, work, work_bytes, meta, true);
@@ -435,7 +400,7 @@ int pdc_bls_scan_ragged(const double *t, const double *y, const double *dy, cons
     PDC_TRY(validate("bls_ragged", offsets, n_curves, start, step, stop, p_offsets, q));
     const BlsOut out = {power, depth, start_bin, box_bins, best_index, best_power, best_depth, best_start, best_box};
     PDC_REQUIRE(out.any(), "bls_ragged: no output requested");
-    const BlsJob j = make_job(t, y, dy, offsets, start, step, stop, p_offsets, q, out);
+    const BlsJob j(t, y, dy, offsets, start, step, stop, p_offsets, q, out);
     return bls_host("bls_ragged", j, n_curves, devices, n_devices);
 }
 
@@ -448,19 +413,10 @@ int pdc_bls_ragged_peaks(const double *t, const double *y, const double *dy, con
                          int32_t *best_start, int32_t *best_box, const int *devices, int n_devices) {
     const BlsParams q = {n_bins, len_min, len_max, min_points, dips_only ? 1 : 0, 0};
     PDC_TRY(validate("bls_ragged_peaks", offsets, n_curves, start, step, stop, p_offsets, q));
-    PDC_REQUIRE(k >= 1 && k <= 1024, "bls_ragged_peaks: k must be 1..1024 (got %d)", k);
     const BlsOut out = {power, depth, start_bin, box_bins, best_index, best_power, best_depth, best_start, best_box};
-    PDC_REQUIRE(count_out || idx_out || height_out || prominence_out || half_lo_out || half_hi_out || out.any(),
-                "bls_ragged_peaks: no output requested");
-    BlsJob j = make_job(t, y, dy, offsets, start, step, stop, p_offsets, q, out);
-    j.k = k;
-    j.by_prominence = by_prominence ? 1 : 0;
-    j.count = count_out;
-    j.idx = idx_out;
-    j.height = height_out;
-    j.prom = prominence_out;
-    j.lo = half_lo_out;
-    j.hi = half_hi_out;
+    BlsJob j(t, y, dy, offsets, start, step, stop, p_offsets, q, out);
+    PDC_TRY(j.want_table("bls_ragged_peaks", k, by_prominence, count_out, idx_out, height_out, prominence_out, half_lo_out,
+                         half_hi_out, out.any()));
     return bls_host("bls_ragged_peaks", j, n_curves, devices, n_devices);
 }
 

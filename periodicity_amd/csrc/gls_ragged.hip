@@ -30,6 +30,7 @@
 #include "gls_epilogue.h"
 #include "gls_sums.h"
 
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -218,16 +219,18 @@ struct RaggedLayout {
     int64_t rec, scal, meta, blk_max, blk_arg, pitched, total;
 };
 constexpr int kMetaArrays = 7;   // offsets | foff | ctile | otile | order (int64) | f0 | delta (double), B + 1 each
+enum { M_OFF, M_FOFF, M_CTILE, M_OTILE, M_ORDER, M_F0, M_DELTA };
 
 RaggedLayout ragged_layout(int64_t n_total, int64_t n_curves, int64_t nf_total, int64_t nf_max, int k) {
     const int64_t tiles_max = nf_total / kRTile + n_curves;   // >= sum of ceil(nf_b / 1024)
     RaggedLayout w;
-    w.rec = 0;
-    w.scal = up256((n_total + 2) * 48);
-    w.meta = w.scal + up256(n_curves * 32);
-    w.blk_max = w.meta + up256(kMetaArrays * (n_curves + 1) * 8);
-    w.blk_arg = w.blk_max + up256(tiles_max * 8);
-    w.pitched = w.blk_arg + up256(tiles_max * 8);
+    Carve c;
+    w.rec = c.take((n_total + 2) * 48);
+    w.scal = c.take(n_curves * 32);
+    w.meta = c.take(kMetaArrays * (n_curves + 1) * 8);
+    w.blk_max = c.take(tiles_max * 8);
+    w.blk_arg = c.take(tiles_max * 8);
+    w.pitched = c.at;
     w.total = w.pitched + ragged_table_bytes(n_curves, nf_max, k);
     return w;
 }
@@ -251,7 +254,7 @@ int validate(const char *what, const int64_t *offsets, int64_t n_curves, const d
 int ragged_dev(int device, hipStream_t st, const double *d_t, const double *d_y, const double *d_dy,
                const int64_t *offsets, int64_t n_curves, const double *f0, const double *delta, const int64_t *foff,
                int fit_mean, int psd, double *d_power, double *d_pitched, int64_t pitch, double *d_amax,
-               int64_t *d_argmax, void *work, int64_t work_bytes, std::vector<int64_t> &meta, bool wait_meta) {
+               int64_t *d_argmax, void *work, int64_t work_bytes, std::vector<int64_t> &host_meta, bool wait_meta) {
     const int64_t n_total = offsets[n_curves], nf_total = foff[n_curves];
     const RaggedLayout w = ragged_layout(n_total, n_curves, nf_total, 0, 0);   // (the pitched copy is the caller's)
     PDC_REQUIRE(work && work_bytes >= w.total, "gls_ragged: workspace too small (%lld < %lld bytes)",
@@ -260,35 +263,22 @@ int ragged_dev(int device, hipStream_t st, const double *d_t, const double *d_y,
     PDC_TRY(use_device(device));
     char *base = static_cast<char *>(work);
     // metadata: one upload; dispatch order = ragged_order (costliest curve first)
-    const int64_t B1 = n_curves + 1;
-    meta.assign((size_t)(kMetaArrays * B1), 0);
-    int64_t *m_off = meta.data(), *m_foff = m_off + B1, *m_ctile = m_foff + B1, *m_otile = m_ctile + B1,
-            *m_order = m_otile + B1;
-    double *m_f0 = reinterpret_cast<double *>(m_order + B1), *m_delta = m_f0 + B1;
-    for (int64_t b = 0; b < n_curves; ++b) {
-        m_off[b] = offsets[b];
-        m_foff[b] = foff[b];
-        m_f0[b] = f0[b];
-        m_delta[b] = delta[b];
-        m_ctile[b + 1] = m_ctile[b] + tiles_of(foff[b + 1] - foff[b]);
-    }
-    m_off[n_curves] = n_total;
-    m_foff[n_curves] = nf_total;
-    const int64_t m = ragged_order(offsets, foff, n_curves, kRTile, m_order, m_otile);
+    RaggedMeta meta(host_meta, kMetaArrays, n_curves, base + w.meta);
+    meta.fill_offsets(offsets, foff);
+    std::copy(f0, f0 + n_curves, meta.f64(M_F0));
+    std::copy(delta, delta + n_curves, meta.f64(M_DELTA));
+    int64_t *m_ctile = meta.i64(M_CTILE);
+    for (int64_t b = 0; b < n_curves; ++b) m_ctile[b + 1] = m_ctile[b] + tiles_of(foff[b + 1] - foff[b]);
+    const int64_t m = ragged_order(offsets, foff, n_curves, kRTile, meta.i64(M_ORDER), meta.i64(M_OTILE));
     const int64_t tiles = m_ctile[n_curves];
-    int64_t *d_meta = reinterpret_cast<int64_t *>(base + w.meta);
-    PDC_HIP(hipMemcpyAsync(d_meta, meta.data(), (size_t)(kMetaArrays * B1 * 8), hipMemcpyHostToDevice, st));
-    if (wait_meta) PDC_HIP(hipStreamSynchronize(st));   // (`meta` goes when the caller returns)
-    const int64_t *d_off = d_meta, *d_foff = d_off + B1, *d_ctile = d_foff + B1, *d_otile = d_ctile + B1,
-                  *d_order = d_otile + B1;
-    const double *d_f0 = reinterpret_cast<const double *>(d_order + B1), *d_delta = d_f0 + B1;
+    PDC_TRY(meta.upload(st, wait_meta));
 
     RaggedPrepArgs p;
     p.t = d_t;
     p.y = d_y;
     p.dy = d_dy;
-    p.offsets = d_off;
-    p.delta = d_delta;
+    p.offsets = meta.d_i64(M_OFF);
+    p.delta = meta.d_f64(M_DELTA);
     p.fit_mean = fit_mean;
     p.rec = reinterpret_cast<double *>(base + w.rec);
     p.scal = reinterpret_cast<double *>(base + w.scal);
@@ -299,13 +289,13 @@ int ragged_dev(int device, hipStream_t st, const double *d_t, const double *d_y,
         RaggedArgs a;
         a.rec = p.rec;
         a.scal = p.scal;
-        a.offsets = d_off;
-        a.foff = d_foff;
-        a.f0 = d_f0;
-        a.delta = d_delta;
-        a.ctile = d_ctile;
-        a.otile = d_otile;
-        a.order = d_order;
+        a.offsets = p.offsets;
+        a.foff = meta.d_i64(M_FOFF);
+        a.f0 = meta.d_f64(M_F0);
+        a.delta = p.delta;
+        a.ctile = meta.d_i64(M_CTILE);
+        a.otile = meta.d_i64(M_OTILE);
+        a.order = meta.d_i64(M_ORDER);
         a.m = m;
         a.tiles = tiles;
         a.psd = psd;
@@ -321,7 +311,7 @@ int ragged_dev(int device, hipStream_t st, const double *d_t, const double *d_y,
     if (peaks) {
         hipLaunchKernelGGL(gls_ragged_peak_kernel, dim3((unsigned)n_curves), dim3(64), 0, st,
                            reinterpret_cast<const double *>(base + w.blk_max),
-                           reinterpret_cast<const int64_t *>(base + w.blk_arg), d_ctile, d_amax, d_argmax);
+                           reinterpret_cast<const int64_t *>(base + w.blk_arg), meta.d_i64(M_CTILE), d_amax, d_argmax);
         PDC_HIP(hipGetLastError());
     }
     return PDC_OK;
@@ -335,8 +325,15 @@ struct RaggedJob : RaggedBatch {
     const double *t, *y, *dy;
     const double *f0, *delta;
     int fit_mean, psd;
-    double *power, *amax;
-    int64_t *argmax;
+    double *power, *amax = nullptr;
+    int64_t *argmax = nullptr;
+
+    RaggedJob(const double *t_, const double *y_, const double *dy_, const int64_t *offsets_, const double *f0_,
+              const double *delta_, const int64_t *f_offsets, int fit_mean_, int psd_, double *power_out)
+        : t(t_), y(y_), dy(dy_), f0(f0_), delta(delta_), fit_mean(fit_mean_ ? 1 : 0), psd(psd_ ? 1 : 0), power(power_out) {
+        offsets = offsets_;
+        rows = f_offsets;
+    }
 
     // The slot buffer of the group [c0, c1) whose longest grid has nf_max bins: inputs | power | amax | argmax | workspace.
     struct Bytes {
@@ -345,42 +342,32 @@ struct RaggedJob : RaggedBatch {
     Bytes bytes(int64_t c0, int64_t c1, int64_t nf_max) const {
         const int64_t n = offsets[c1] - offsets[c0], nf = rows[c1] - rows[c0], B = c1 - c0;
         Bytes g;
-        g.in_t = 0;
-        g.in_y = up256(n * 8);
-        g.in_dy = g.in_y + up256(n * 8);
-        g.pow = g.in_dy + (dy ? up256(n * 8) : 0);
-        g.amax = g.pow + (power ? up256(nf * 8) : 0);
-        g.arg = g.amax + (amax ? up256(B * 8) : 0);
-        g.work = g.arg + (argmax ? up256(B * 8) : 0);
+        Carve c;
+        g.in_t = c.take(n * 8);
+        g.in_y = c.take(n * 8);
+        g.in_dy = c.take(dy ? n * 8 : 0);
+        g.pow = c.take(power ? nf * 8 : 0);
+        g.amax = c.take(amax ? B * 8 : 0);
+        g.arg = c.take(argmax ? B * 8 : 0);
+        g.work = c.at;
         g.total = g.work + ragged_layout(n, B, nf, nf_max, k).total;
         return g;
     }
     int64_t group_bytes(int64_t c0, int64_t c1, int64_t nf_max) const override { return bytes(c0, c1, nf_max).total; }
 
     int run_group(RaggedSlot &s, int64_t c0, int64_t c1, int64_t nf_max, double *pitched) const override {
-        const int64_t B = c1 - c0, s0 = offsets[c0], n = offsets[c1] - s0, fb = rows[c0], nf = rows[c1] - fb;
-        const Bytes g = bytes(c0, c1, nf_max);
-        char *p = static_cast<char *>(s.buf);
-        hipStream_t st = s.stream;
-        if (n > 0) {
-            PDC_HIP(hipMemcpyAsync(p + g.in_t, t + s0, n * 8, hipMemcpyHostToDevice, st));
-            PDC_HIP(hipMemcpyAsync(p + g.in_y, y + s0, n * 8, hipMemcpyHostToDevice, st));
-            if (dy) PDC_HIP(hipMemcpyAsync(p + g.in_dy, dy + s0, n * 8, hipMemcpyHostToDevice, st));
-        }
-        std::vector<int64_t> off((size_t)B + 1), foff((size_t)B + 1);
-        for (int64_t b = 0; b <= B; ++b) {
-            off[(size_t)b] = offsets[c0 + b] - s0;
-            foff[(size_t)b] = rows[c0 + b] - fb;
-        }
-        PDC_TRY(ragged_dev(s.device, st, (const double *)(p + g.in_t), (const double *)(p + g.in_y),
-                           dy ? (const double *)(p + g.in_dy) : nullptr, off.data(), B, f0 + c0, delta + c0, foff.data(),
-                           fit_mean, psd, power ? (double *)(p + g.pow) : nullptr, pitched, nf_max,
-                           amax ? (double *)(p + g.amax) : nullptr, argmax ? (int64_t *)(p + g.arg) : nullptr,
-                           p + g.work, g.total - g.work, s.meta, false));
-        if (power && nf > 0) PDC_HIP(hipMemcpyAsync(power + fb, p + g.pow, nf * 8, hipMemcpyDeviceToHost, st));
-        if (amax) PDC_HIP(hipMemcpyAsync(amax + c0, p + g.amax, B * 8, hipMemcpyDeviceToHost, st));
-        if (argmax) PDC_HIP(hipMemcpyAsync(argmax + c0, p + g.arg, B * 8, hipMemcpyDeviceToHost, st));
-        return PDC_OK;
+        const RaggedGroup g(*this, s, c0, c1);
+        const Bytes at = bytes(c0, c1, nf_max);
+        PDC_TRY(g.upload(at.in_t, t));
+        PDC_TRY(g.upload(at.in_y, y));
+        PDC_TRY(g.upload(at.in_dy, dy));
+        PDC_TRY(ragged_dev(s.device, g.st, g.at<double>(at.in_t), g.at<double>(at.in_y), g.at_if<double>(dy, at.in_dy),
+                           g.off.data(), g.B, f0 + c0, delta + c0, g.roff.data(), fit_mean, psd,
+                           g.at_if<double>(power, at.pow), pitched, nf_max, g.at_if<double>(amax, at.amax),
+                           g.at_if<int64_t>(argmax, at.arg), g.buf + at.work, at.total - at.work, s.meta, false));
+        PDC_TRY(g.rows_back(power, at.pow));
+        PDC_TRY(g.curves_back(amax, at.amax));
+        return g.curves_back(argmax, at.arg);
     }
 };
 
@@ -407,10 +394,7 @@ int pdc_gls_scan_ragged_dev(int device, void *stream, const double *d_t, const d
                             int64_t pitch, double *d_amax, int64_t *d_argmax, void *work, int64_t work_bytes) {
     PDC_TRY(validate("gls_ragged_dev", offsets, n_curves, f0, delta, f_offsets));
     PDC_REQUIRE(d_power || d_pitched || d_amax || d_argmax, "gls_ragged_dev: no output requested");
-    if (d_pitched)
-        for (int64_t b = 0; b < n_curves; ++b)
-            PDC_REQUIRE(f_offsets[b + 1] - f_offsets[b] <= pitch, "gls_ragged_dev: curve %lld has more bins than the pitch",
-                        (long long)b);
+    if (d_pitched) PDC_TRY(ragged_check_pitch("gls_ragged_dev", f_offsets, n_curves, pitch, "bins"));
     std::vector<int64_t> meta;
     return ragged_dev(device, (hipStream_t)stream, d_t, d_y, d_dy, offsets, n_curves, f0, delta, f_offsets, fit_mean, psd,
                       d_power, d_pitched, pitch, d_amax, d_argmax, work, work_bytes, meta, true);
@@ -421,17 +405,7 @@ int pdc_gls_scan_ragged(const double *t, const double *y, const double *dy, cons
                         double *power_out, double *amax_out, int64_t *argmax_out, const int *devices, int n_devices) {
     PDC_TRY(validate("gls_ragged", offsets, n_curves, f0, delta, f_offsets));
     PDC_REQUIRE(power_out || amax_out || argmax_out, "gls_ragged: no output requested");
-    RaggedJob j = {};
-    j.t = t;
-    j.y = y;
-    j.dy = dy;
-    j.offsets = offsets;
-    j.rows = f_offsets;
-    j.f0 = f0;
-    j.delta = delta;
-    j.fit_mean = fit_mean ? 1 : 0;
-    j.psd = psd ? 1 : 0;
-    j.power = power_out;
+    RaggedJob j(t, y, dy, offsets, f0, delta, f_offsets, fit_mean, psd, power_out);
     j.amax = amax_out;
     j.argmax = argmax_out;
     return ragged_host("gls_ragged", j, n_curves, devices, n_devices);
@@ -443,28 +417,9 @@ int pdc_gls_ragged_peaks(const double *t, const double *y, const double *dy, con
                          double *prominence_out, int64_t *half_lo_out, int64_t *half_hi_out, double *power_out,
                          const int *devices, int n_devices) {
     PDC_TRY(validate("gls_ragged_peaks", offsets, n_curves, f0, delta, f_offsets));
-    PDC_REQUIRE(k >= 1 && k <= 1024, "gls_ragged_peaks: k must be 1..1024 (got %d)", k);
-    PDC_REQUIRE(count_out || idx_out || height_out || prominence_out || half_lo_out || half_hi_out || power_out,
-                "gls_ragged_peaks: no output requested");
-    RaggedJob j = {};
-    j.t = t;
-    j.y = y;
-    j.dy = dy;
-    j.offsets = offsets;
-    j.rows = f_offsets;
-    j.f0 = f0;
-    j.delta = delta;
-    j.fit_mean = fit_mean ? 1 : 0;
-    j.psd = psd ? 1 : 0;
-    j.k = k;
-    j.by_prominence = by_prominence ? 1 : 0;
-    j.power = power_out;
-    j.count = count_out;
-    j.idx = idx_out;
-    j.height = height_out;
-    j.prom = prominence_out;
-    j.lo = half_lo_out;
-    j.hi = half_hi_out;
+    RaggedJob j(t, y, dy, offsets, f0, delta, f_offsets, fit_mean, psd, power_out);
+    PDC_TRY(j.want_table("gls_ragged_peaks", k, by_prominence, count_out, idx_out, height_out, prominence_out, half_lo_out,
+                         half_hi_out, power_out != nullptr));
     return ragged_host("gls_ragged_peaks", j, n_curves, devices, n_devices);
 }
 

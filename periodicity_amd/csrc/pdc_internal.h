@@ -36,13 +36,27 @@ int release_bls_ragged();
 // ---- ragged-grid batches: the host side the kinds share (ragged.hip) ---------------------------------------------
 // A ragged batch is a catalogue of light curves that each keep their own grid: curve b owns samples
 // [offsets[b], offsets[b+1]) and rows [rows[b], rows[b+1]) - GLS's frequency bins (gls_ragged.hip) or the phase
-// folds' trial periods (pdm_ragged.hip, sl_ragged.inc, bls_ragged.hip).  Each kind keeps its kernels, workspace layout, uploads and launches.
+// folds' trial periods (pdm_ragged.hip, sl_ragged.inc, bls_ragged.hip).  Each kind keeps its kernels, its workspace
+// layout and its launches; the frame around them - slots, groups, a group's uploads and copies back, the metadata
+// upload, the peak-table arguments, the pitch check - is here, once.
 inline int64_t up256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+
+struct Carve {   // byte offsets of the parts of a buffer, in order: each part starts on a multiple of 256
+    int64_t at = 0;
+    int64_t take(int64_t bytes) {   // the part's offset; the next one starts up256(bytes) later
+        const int64_t here = at;
+        at += up256(bytes);
+        return here;
+    }
+};
 
 // The checks every ragged entry shares, with their texts: n_curves, offsets and `rows_name` starting at 0 and never
 // decreasing, fewer than 2^31 tiles of `tile` rows (`too_large` ends that message); curve(b) adds the kind's own.
 int ragged_validate(const char *what, const int64_t *offsets, const int64_t *rows, const char *rows_name,
                     int64_t n_curves, int64_t tile, const char *too_large, const std::function<int(int64_t)> &curve);
+
+// A `_dev` entry's pitched copy: no curve has more rows (`unit`: "bins" or "periods") than the pitch.
+int ragged_check_pitch(const char *what, const int64_t *rows, int64_t n_curves, int64_t pitch, const char *unit);
 
 // Dispatch order of a ragged scan: order[0, m) = the curves with at least one row, most samples first (ties in curve
 // order), otile[0, m] = their prefix of tiles of `tile` rows; returns m.
@@ -71,11 +85,16 @@ struct RaggedSlots {   // one kind's slots, kept between host calls for the same
 
 // One host call of a kind: where its peak table goes (caller's host arrays, any may be NULL) and its two group hooks.
 struct RaggedBatch {
-    const int64_t *offsets, *rows;   // [B + 1]
-    int k, by_prominence;            // k > 0: a [B][k] peak table of the rows (pdc_peaks_topk_dev)
-    int64_t *count, *idx, *lo, *hi;
-    double *height, *prom;
+    const int64_t *offsets = nullptr, *rows = nullptr;   // [B + 1]
+    int k = 0, by_prominence = 0;                        // k > 0: a [B][k] peak table of the rows (pdc_peaks_topk_dev)
+    int64_t *count = nullptr, *idx = nullptr, *lo = nullptr, *hi = nullptr;
+    double *height = nullptr, *prom = nullptr;
+    bool negate_heights = false;   // the pitched copy holds -statistic (dips): ragged_run turns `height` back
     int64_t rows_of(int64_t b) const { return rows[b + 1] - rows[b]; }
+    // The table arguments of a `*_ragged_peaks` entry, in the ABI's order, after the kind's validate: k in 1 .. 1024,
+    // at least one output (`other_output`: the entry has one besides the table), then the fields above.
+    int want_table(const char *what, int k, int by_prominence, int64_t *count_out, int64_t *idx_out, double *height_out,
+                   double *prominence_out, int64_t *half_lo_out, int64_t *half_hi_out, bool other_output);
     // Slot-buffer bytes of the group [c0, c1) whose longest grid has row_max rows (0 without a table); the buffer
     // ends with the ragged_table_bytes(c1 - c0, row_max, k) of the peak table.
     virtual int64_t group_bytes(int64_t c0, int64_t c1, int64_t row_max) const = 0;
@@ -84,9 +103,46 @@ struct RaggedBatch {
     virtual int run_group(RaggedSlot &s, int64_t c0, int64_t c1, int64_t row_max, double *pitched) const = 0;
 };
 
+// The group [c0, c1) of a batch on its slot, as a run_group sees it: B curves, n samples from s0, nr rows from r0, the
+// batch's offsets and rows rebased to the group (what a kind's `*_dev` function takes), and the copies between the
+// caller's host arrays and byte offsets of the slot buffer, enqueued on the slot's stream.
+struct RaggedGroup {
+    RaggedGroup(const RaggedBatch &batch, const RaggedSlot &slot, int64_t c0, int64_t c1);
+    int64_t B, c0, s0, n, r0, nr;
+    std::vector<int64_t> off, roff;   // [B + 1]
+    char *buf;
+    hipStream_t st;
+    template <typename T>
+    T *at(int64_t byte) const { return reinterpret_cast<T *>(buf + byte); }
+    template <typename T>
+    T *at_if(const void *wanted, int64_t byte) const { return wanted ? at<T>(byte) : nullptr; }
+    int upload(int64_t byte, const double *host) const;   // the group's n samples of a [n_total] array (NULL: none)
+    template <typename T>
+    int rows_back(T *host, int64_t byte) const { return back(host ? host + r0 : nullptr, byte, nr * (int64_t)sizeof(T)); }
+    template <typename T>
+    int curves_back(T *host, int64_t byte) const { return back(host ? host + c0 : nullptr, byte, B * (int64_t)sizeof(T)); }
+    int back(void *host, int64_t byte, int64_t bytes) const;   // (NULL or nothing to copy: no call)
+};
+
+// A group's metadata: `arrays` columns of B + 1 entries each, int64 or double, filled in the slot's host vector,
+// uploaded in one copy to `d_meta`; the same object gives the columns' device addresses for the kernel arguments.
+struct RaggedMeta {
+    RaggedMeta(std::vector<int64_t> &host, int arrays, int64_t n_curves, void *d_meta);   // (all zeros)
+    std::vector<int64_t> &host;
+    int64_t B1, *dev;
+    int64_t *i64(int column) { return host.data() + column * B1; }
+    double *f64(int column) { return reinterpret_cast<double *>(i64(column)); }
+    const int64_t *d_i64(int column) const { return dev + column * B1; }
+    const double *d_f64(int column) const { return reinterpret_cast<const double *>(d_i64(column)); }
+    void fill_offsets(const int64_t *offsets, const int64_t *rows);   // columns 0 and 1, [B + 1]
+    // columns column .. column + 2 [B]: the linspace description of every curve's grid
+    void fill_linspace(int column, const double *start, const double *step, const double *stop);
+    int upload(hipStream_t st, bool wait);   // wait: the host vector goes when the caller returns
+};
+
 // A host call: curves dealt to device slots in contiguous shares balanced by sum n_b rows_b + n_b + rows_b (a device
 // may repeat), each share cut into contiguous groups that fit the slot's budget, one thread per slot; a slot's error
-// is the call's.
+// is the call's.  With batch.negate_heights the table's heights change sign once every group has run.
 int ragged_run(const char *what, RaggedSlots &slots, const RaggedBatch &batch, int64_t n_curves, const int *devices,
                int n_devices);
 

@@ -219,13 +219,15 @@ struct PhaseLayout {
     int64_t stat, meta, raw, pitched, total;
 };
 constexpr int kMetaArrays = 9;   // offsets | poff | otile | order (int64) | start | step | stop | sigma | signif, B + 1 each
+enum { M_OFF, M_POFF, M_OTILE, M_ORDER, M_START, M_STEP, M_STOP, M_SIGMA, M_SIGNIF };
 
 PhaseLayout phase_layout(int64_t n_curves, int64_t p_total, int64_t p_max, int k) {
     PhaseLayout w;
-    w.stat = 0;
-    w.meta = up256(n_curves * 24);
-    w.raw = w.meta + up256(kMetaArrays * (n_curves + 1) * 8);
-    w.pitched = w.raw + up256(p_total * 8);
+    Carve c;
+    w.stat = c.take(n_curves * 24);
+    w.meta = c.take(kMetaArrays * (n_curves + 1) * 8);
+    w.raw = c.take(p_total * 8);
+    w.pitched = c.at;
     w.total = w.pitched + ragged_table_bytes(n_curves, p_max, k);
     return w;
 }
@@ -267,7 +269,7 @@ int launch_scan(Kernel kernel, int block, const Shape &s, int64_t tiles, hipStre
 int phase_ragged_dev(int kind, int device, hipStream_t st, const double *d_t, const double *d_x, const int64_t *offsets,
                      int64_t n_curves, const double *start, const double *step, const double *stop, const int64_t *poff,
                      const double *sigma, const double *signif, int nb, int nc, double *d_out, double *d_pitched,
-                     int64_t pitch, void *work, int64_t work_bytes, std::vector<int64_t> &meta, bool wait_meta) {
+                     int64_t pitch, void *work, int64_t work_bytes, std::vector<int64_t> &host_meta, bool wait_meta) {
     const int64_t n_total = offsets[n_curves], p_total = poff[n_curves];
     const PhaseLayout w = phase_layout(n_curves, p_total, 0, 0);   // (the pitched copy is the caller's)
     PDC_REQUIRE(work && work_bytes >= w.total, "phase_ragged: workspace too small (%lld < %lld bytes)",
@@ -277,41 +279,29 @@ int phase_ragged_dev(int kind, int device, hipStream_t st, const double *d_t, co
     PDC_TRY(use_device(device));
     char *base = static_cast<char *>(work);
     // metadata: one upload; dispatch order = ragged_order (costliest curve first)
-    const int64_t B1 = n_curves + 1;
-    meta.assign((size_t)(kMetaArrays * B1), 0);
-    int64_t *m_off = meta.data(), *m_poff = m_off + B1, *m_otile = m_poff + B1, *m_order = m_otile + B1;
-    double *m_start = reinterpret_cast<double *>(m_order + B1), *m_step = m_start + B1, *m_stop = m_step + B1,
-           *m_sigma = m_stop + B1, *m_signif = m_sigma + B1;
+    RaggedMeta meta(host_meta, kMetaArrays, n_curves, base + w.meta);
+    meta.fill_offsets(offsets, poff);
+    meta.fill_linspace(M_START, start, step, stop);
     for (int64_t b = 0; b < n_curves; ++b) {
-        m_off[b] = offsets[b];
-        m_poff[b] = poff[b];
-        m_start[b] = start[b];
-        m_step[b] = step[b];
-        m_stop[b] = stop[b];
-        m_sigma[b] = sigma ? sigma[b] : 1.0;
-        m_signif[b] = signif ? signif[b] : 0.0;
+        meta.f64(M_SIGMA)[b] = sigma ? sigma[b] : 1.0;
+        meta.f64(M_SIGNIF)[b] = signif ? signif[b] : 0.0;
     }
-    m_off[n_curves] = n_total;
-    m_poff[n_curves] = p_total;
-    const int64_t m = ragged_order(offsets, poff, n_curves, kPTile, m_order, m_otile);
-    const int64_t tiles = m_otile[m];
-    int64_t *d_meta = reinterpret_cast<int64_t *>(base + w.meta);
-    PDC_HIP(hipMemcpyAsync(d_meta, meta.data(), (size_t)(kMetaArrays * B1 * 8), hipMemcpyHostToDevice, st));
-    if (wait_meta) PDC_HIP(hipStreamSynchronize(st));   // (`meta` goes when the caller returns)
-    const double *d_dbl = reinterpret_cast<const double *>(d_meta + 4 * B1);
+    const int64_t m = ragged_order(offsets, poff, n_curves, kPTile, meta.i64(M_ORDER), meta.i64(M_OTILE));
+    const int64_t tiles = meta.i64(M_OTILE)[m];
+    PDC_TRY(meta.upload(st, wait_meta));
 
     RaggedPhaseArgs a = {};
     a.t = d_t;
     a.x = d_x;
-    a.offsets = d_meta;
-    a.poff = d_meta + B1;
-    a.otile = d_meta + 2 * B1;
-    a.order = d_meta + 3 * B1;
-    a.start = d_dbl;
-    a.step = d_dbl + B1;
-    a.stop = d_dbl + 2 * B1;
-    a.sigma = d_dbl + 3 * B1;
-    a.signif = signif ? d_dbl + 4 * B1 : nullptr;
+    a.offsets = meta.d_i64(M_OFF);
+    a.poff = meta.d_i64(M_POFF);
+    a.otile = meta.d_i64(M_OTILE);
+    a.order = meta.d_i64(M_ORDER);
+    a.start = meta.d_f64(M_START);
+    a.step = meta.d_f64(M_STEP);
+    a.stop = meta.d_f64(M_STOP);
+    a.sigma = meta.d_f64(M_SIGMA);
+    a.signif = signif ? meta.d_f64(M_SIGNIF) : nullptr;
     a.m = m;
     a.tiles = tiles;
     a.nb = nb;
@@ -362,6 +352,16 @@ struct PhaseJob : RaggedBatch {
     const double *start, *step, *stop, *sigma, *signif;
     double *out;
 
+    PhaseJob(int kind_, const double *t_, const double *x_, const int64_t *offsets_, const double *start_,
+             const double *step_, const double *stop_, const int64_t *p_offsets, const double *sigma_,
+             const double *significant, int nb_, int nc_, double *out_)
+        : kind(kind_), nb(nb_), nc(kind_ == 1 ? 1 : nc_), t(t_), x(x_), start(start_), step(step_), stop(stop_),
+          sigma(kind_ == 0 ? sigma_ : nullptr), signif(significant), out(out_) {
+        offsets = offsets_;
+        rows = p_offsets;
+        negate_heights = is_dip(kind_);
+    }
+
     // The slot buffer of the group [c0, c1) whose longest grid has p_max periods: inputs | out | workspace.
     struct Bytes {
         int64_t in_t, in_x, out, work, total;
@@ -369,35 +369,26 @@ struct PhaseJob : RaggedBatch {
     Bytes bytes(int64_t c0, int64_t c1, int64_t p_max) const {
         const int64_t n = offsets[c1] - offsets[c0], np = rows[c1] - rows[c0], B = c1 - c0;
         Bytes g;
-        g.in_t = 0;
-        g.in_x = up256(n * 8);
-        g.out = g.in_x + up256(n * 8);
-        g.work = g.out + (out ? up256(np * 8) : 0);
+        Carve c;
+        g.in_t = c.take(n * 8);
+        g.in_x = c.take(n * 8);
+        g.out = c.take(out ? np * 8 : 0);
+        g.work = c.at;
         g.total = g.work + phase_layout(B, np, p_max, k).total;
         return g;
     }
     int64_t group_bytes(int64_t c0, int64_t c1, int64_t p_max) const override { return bytes(c0, c1, p_max).total; }
 
     int run_group(RaggedSlot &s, int64_t c0, int64_t c1, int64_t p_max, double *pitched) const override {
-        const int64_t B = c1 - c0, s0 = offsets[c0], n = offsets[c1] - s0, pb = rows[c0], np = rows[c1] - pb;
-        const Bytes g = bytes(c0, c1, p_max);
-        char *p = static_cast<char *>(s.buf);
-        hipStream_t st = s.stream;
-        if (n > 0) {
-            PDC_HIP(hipMemcpyAsync(p + g.in_t, t + s0, n * 8, hipMemcpyHostToDevice, st));
-            PDC_HIP(hipMemcpyAsync(p + g.in_x, x + s0, n * 8, hipMemcpyHostToDevice, st));
-        }
-        std::vector<int64_t> off((size_t)B + 1), poff((size_t)B + 1);
-        for (int64_t b = 0; b <= B; ++b) {
-            off[(size_t)b] = offsets[c0 + b] - s0;
-            poff[(size_t)b] = rows[c0 + b] - pb;
-        }
-        PDC_TRY(phase_ragged_dev(kind, s.device, st, (const double *)(p + g.in_t), (const double *)(p + g.in_x),
-                                 off.data(), B, start + c0, step + c0, stop + c0, poff.data(), sigma ? sigma + c0 : nullptr,
-                                 signif ? signif + c0 : nullptr, nb, nc, out ? (double *)(p + g.out) : nullptr,
-                                 pitched, p_max, p + g.work, g.total - g.work, s.meta, false));
-        if (out && np > 0) PDC_HIP(hipMemcpyAsync(out + pb, p + g.out, np * 8, hipMemcpyDeviceToHost, st));
-        return PDC_OK;
+        const RaggedGroup g(*this, s, c0, c1);
+        const Bytes at = bytes(c0, c1, p_max);
+        PDC_TRY(g.upload(at.in_t, t));
+        PDC_TRY(g.upload(at.in_x, x));
+        PDC_TRY(phase_ragged_dev(kind, s.device, g.st, g.at<double>(at.in_t), g.at<double>(at.in_x), g.off.data(), g.B,
+                                 start + c0, step + c0, stop + c0, g.roff.data(), sigma ? sigma + c0 : nullptr,
+                                 signif ? signif + c0 : nullptr, nb, nc, g.at_if<double>(out, at.out), pitched, p_max,
+                                 g.buf + at.work, at.total - at.work, s.meta, false));
+        return g.rows_back(out, at.out);
     }
 };
 
@@ -409,29 +400,7 @@ int phase_host(const char *what, const PhaseJob &j, int64_t n_curves, const int 
                 PDC_REQUIRE(j.x[i] >= 0.0 && j.x[i] < (double)j.nc,
                             "%s: curve %lld: mag_bin[%lld] = %g is not a bin index in 0 .. %d", what, (long long)b,
                             (long long)(i - j.offsets[b]), j.x[i], j.nc - 1);
-    PDC_TRY(ragged_run(what, g_slots, j, n_curves, devices, n_devices));
-    if (j.k > 0 && j.height && is_dip(j.kind))   // the table ranked -stat: heights back to the statistic's own values
-        for (int64_t i = 0; i < n_curves * j.k; ++i) j.height[i] = -j.height[i];
-    return PDC_OK;
-}
-
-PhaseJob make_job(int kind, const double *t, const double *x, const int64_t *offsets, const double *start,
-                  const double *step, const double *stop, const int64_t *p_offsets, const double *sigma,
-                  const double *significant, int nb, int nc) {
-    PhaseJob j = {};
-    j.kind = kind;
-    j.nb = nb;
-    j.nc = kind == 1 ? 1 : nc;
-    j.t = t;
-    j.x = x;
-    j.offsets = offsets;
-    j.rows = p_offsets;
-    j.start = start;
-    j.step = step;
-    j.stop = stop;
-    j.sigma = kind == 0 ? sigma : nullptr;
-    j.signif = significant;
-    return j;
+    return ragged_run(what, g_slots, j, n_curves, devices, n_devices);
 }
 
 }  // namespace
@@ -460,10 +429,7 @@ int pdc_phase_scan_ragged_dev(int kind, int device, void *stream, const double *
                               void *work, int64_t work_bytes) {
     PDC_TRY(validate("phase_ragged_dev", kind, offsets, n_curves, start, step, stop, p_offsets, sigma, significant, nb, nc));
     PDC_REQUIRE(d_out || d_pitched, "phase_ragged_dev: no output requested");
-    if (d_pitched)
-        for (int64_t b = 0; b < n_curves; ++b)
-            PDC_REQUIRE(p_offsets[b + 1] - p_offsets[b] <= pitch, "phase_ragged_dev: curve %lld has more periods than the pitch",
-                        (long long)b);
+    if (d_pitched) PDC_TRY(ragged_check_pitch("phase_ragged_dev", p_offsets, n_curves, pitch, "periods"));
     std::vector<int64_t> meta;
     return phase_ragged_dev(kind, device, (hipStream_t)stream, d_t, d_x, offsets, n_curves, start, step, stop, p_offsets,
                             kind == 0 ? sigma : nullptr, significant, nb, nc, d_out, d_pitched, pitch, work, work_bytes,
@@ -476,8 +442,7 @@ int pdc_phase_scan_ragged(int kind, const double *t, const double *x, const int6
                           const int *devices, int n_devices) {
     PDC_TRY(validate("phase_ragged", kind, offsets, n_curves, start, step, stop, p_offsets, sigma, significant, nb, nc));
     PDC_REQUIRE(out, "phase_ragged: no output requested");
-    PhaseJob j = make_job(kind, t, x, offsets, start, step, stop, p_offsets, sigma, significant, nb, nc);
-    j.out = out;
+    const PhaseJob j(kind, t, x, offsets, start, step, stop, p_offsets, sigma, significant, nb, nc, out);
     return phase_host(kind_name(kind), j, n_curves, devices, n_devices);
 }
 
@@ -488,19 +453,9 @@ int pdc_phase_ragged_peaks(int kind, const double *t, const double *x, const int
                            int64_t *half_lo_out, int64_t *half_hi_out, double *out, const int *devices, int n_devices) {
     PDC_TRY(validate("phase_ragged_peaks", kind, offsets, n_curves, start, step, stop, p_offsets, sigma, significant, nb,
                      nc));
-    PDC_REQUIRE(k >= 1 && k <= 1024, "phase_ragged_peaks: k must be 1..1024 (got %d)", k);
-    PDC_REQUIRE(count_out || idx_out || height_out || prominence_out || half_lo_out || half_hi_out || out,
-                "phase_ragged_peaks: no output requested");
-    PhaseJob j = make_job(kind, t, x, offsets, start, step, stop, p_offsets, sigma, significant, nb, nc);
-    j.k = k;
-    j.by_prominence = by_prominence ? 1 : 0;
-    j.out = out;
-    j.count = count_out;
-    j.idx = idx_out;
-    j.height = height_out;
-    j.prom = prominence_out;
-    j.lo = half_lo_out;
-    j.hi = half_hi_out;
+    PhaseJob j(kind, t, x, offsets, start, step, stop, p_offsets, sigma, significant, nb, nc, out);
+    PDC_TRY(j.want_table("phase_ragged_peaks", k, by_prominence, count_out, idx_out, height_out, prominence_out,
+                         half_lo_out, half_hi_out, out != nullptr));
     return phase_host(kind_name(kind), j, n_curves, devices, n_devices);
 }
 

@@ -1,6 +1,7 @@
-// The host side that the ragged-grid batches share (gls_ragged.hip, pdm_ragged.hip; declared in pdc_internal.h): the
-// checks of offsets and tiles, the costliest-first dispatch order, the device slots with their shares, budgets, groups
-// and threads, and each group's peak table: pdc_peaks_topk_dev on a pitched copy of the rows whose pad is NaN (why
+// The host side that the ragged-grid batches share (gls_ragged.hip, pdm_ragged.hip, sl_ragged.inc, bls_ragged.hip;
+// declared in pdc_internal.h): the checks of offsets, tiles and pitch, the costliest-first dispatch order, the device
+// slots with their shares, budgets, groups and threads, a group's view of the batch with its uploads and copies back,
+// its metadata block, the peak-table arguments and each group's peak table: pdc_peaks_topk_dev on a pitched copy of the rows whose pad is NaN (why
 // that keeps scipy's answers, and the one half-maximum artefact run_group removes: periodicity_hip.h).
 #include "pdc_internal.h"
 
@@ -116,6 +117,70 @@ int ragged_validate(const char *what, const int64_t *offsets, const int64_t *row
     return PDC_OK;
 }
 
+int ragged_check_pitch(const char *what, const int64_t *rows, int64_t n_curves, int64_t pitch, const char *unit) {
+    for (int64_t b = 0; b < n_curves; ++b)
+        PDC_REQUIRE(rows[b + 1] - rows[b] <= pitch, "%s: curve %lld has more %s than the pitch", what, (long long)b, unit);
+    return PDC_OK;
+}
+
+int RaggedBatch::want_table(const char *what, int k_, int by_prominence_, int64_t *count_out, int64_t *idx_out,
+                            double *height_out, double *prominence_out, int64_t *half_lo_out, int64_t *half_hi_out,
+                            bool other_output) {
+    PDC_REQUIRE(k_ >= 1 && k_ <= 1024, "%s: k must be 1..1024 (got %d)", what, k_);
+    PDC_REQUIRE(count_out || idx_out || height_out || prominence_out || half_lo_out || half_hi_out || other_output,
+                "%s: no output requested", what);
+    k = k_;
+    by_prominence = by_prominence_ ? 1 : 0;
+    count = count_out;
+    idx = idx_out;
+    height = height_out;
+    prom = prominence_out;
+    lo = half_lo_out;
+    hi = half_hi_out;
+    return PDC_OK;
+}
+
+RaggedGroup::RaggedGroup(const RaggedBatch &j, const RaggedSlot &s, int64_t c0_, int64_t c1)
+    : B(c1 - c0_), c0(c0_), s0(j.offsets[c0_]), n(j.offsets[c1] - s0), r0(j.rows[c0_]), nr(j.rows[c1] - r0),
+      off((size_t)B + 1), roff((size_t)B + 1), buf(static_cast<char *>(s.buf)), st(s.stream) {
+    for (int64_t b = 0; b <= B; ++b) {
+        off[(size_t)b] = j.offsets[c0 + b] - s0;
+        roff[(size_t)b] = j.rows[c0 + b] - r0;
+    }
+}
+
+int RaggedGroup::upload(int64_t byte, const double *host) const {
+    if (host && n > 0) PDC_HIP(hipMemcpyAsync(buf + byte, host + s0, (size_t)(n * 8), hipMemcpyHostToDevice, st));
+    return PDC_OK;
+}
+
+int RaggedGroup::back(void *host, int64_t byte, int64_t bytes) const {
+    if (host && bytes > 0) PDC_HIP(hipMemcpyAsync(host, buf + byte, (size_t)bytes, hipMemcpyDeviceToHost, st));
+    return PDC_OK;
+}
+
+RaggedMeta::RaggedMeta(std::vector<int64_t> &host_, int arrays, int64_t n_curves, void *d_meta)
+    : host(host_), B1(n_curves + 1), dev(static_cast<int64_t *>(d_meta)) {
+    host.assign((size_t)(arrays * B1), 0);
+}
+
+void RaggedMeta::fill_offsets(const int64_t *offsets, const int64_t *rows) {
+    std::copy(offsets, offsets + B1, i64(0));
+    std::copy(rows, rows + B1, i64(1));
+}
+
+void RaggedMeta::fill_linspace(int column, const double *start, const double *step, const double *stop) {
+    std::copy(start, start + B1 - 1, f64(column));
+    std::copy(step, step + B1 - 1, f64(column + 1));
+    std::copy(stop, stop + B1 - 1, f64(column + 2));
+}
+
+int RaggedMeta::upload(hipStream_t st, bool wait) {
+    PDC_HIP(hipMemcpyAsync(dev, host.data(), host.size() * 8, hipMemcpyHostToDevice, st));
+    if (wait) PDC_HIP(hipStreamSynchronize(st));
+    return PDC_OK;
+}
+
 int64_t ragged_order(const int64_t *offsets, const int64_t *rows, int64_t n_curves, int64_t tile, int64_t *order,
                      int64_t *otile) {
     int64_t m = 0;
@@ -220,6 +285,8 @@ int ragged_run(const char *what, RaggedSlots &r, const RaggedBatch &j, int64_t n
             set_error("%s", why[(size_t)i].c_str());
             return rc[(size_t)i];
         }
+    if (j.negate_heights && j.k > 0 && j.height)   // the table ranked -statistic: heights back to the statistic itself
+        for (int64_t i = 0; i < n_curves * j.k; ++i) j.height[i] = -j.height[i];
     return PDC_OK;
 }
 

@@ -35,7 +35,8 @@ namespace {
 
 namespace slr {
 
-constexpr int kMeta = 14;          // int64 arrays of B + 1 in the metadata upload (slr_group_dev)
+constexpr int kMeta = 14;          // arrays of B + 1 in the metadata upload (slr_group_dev), in this order:
+enum { M_OFF, M_POFF, M_ROUTE, M_ORDER, M_OPRE = M_ORDER + 4, M_START = M_OPRE + 4, M_STEP, M_STOP };   // order, opre: [4]
 constexpr int kPrepBlock = 256;
 constexpr int kRangeGrid = 1024;   // duo workgroups at most (4 x 256 CUs): the range scratch is laid out for them
 constexpr int64_t kMarkGrid = 32;  // workgroups of the marked-period fallback (its scratch is laid out for them)
@@ -284,19 +285,21 @@ struct SlRaggedLayout {
 // nr_pad: range slots of the longest duo curve (0: none); fallback: the largest slr_fallback_bytes of the group
 SlRaggedLayout slr_layout(int64_t B, int64_t n_total, int64_t p_total, int64_t nr_pad, int64_t fallback) {
     SlRaggedLayout w;
-    w.meta = 0;
-    w.rec = w.meta + up256(slr::kMeta * (B + 1) * 8);
-    w.flags = w.rec + up256(n_total * 16);
-    w.bad = w.flags + up256(B * 4);
-    w.periods = w.bad + up256(B * 8);
-    w.skip = w.periods + up256(p_total * 8);
-    w.todo = w.skip + up256(p_total);
-    w.list = w.todo + up256(p_total);
-    w.count = w.list + up256(p_total * 4);   // count | ticket | (256 on) marked [B]
-    w.ell = w.count + 256 + up256(B * 4);
-    w.range = w.ell + up256(p_total * 8);
-    w.fallback = w.range + up256((int64_t)slr::kRangeGrid * nr_pad * (32 + 4 + 8));
-    w.total = w.fallback + up256(fallback);
+    Carve c;
+    w.meta = c.take(slr::kMeta * (B + 1) * 8);
+    w.rec = c.take(n_total * 16);
+    w.flags = c.take(B * 4);
+    w.bad = c.take(B * 8);
+    w.periods = c.take(p_total * 8);
+    w.skip = c.take(p_total);
+    w.todo = c.take(p_total);
+    w.list = c.take(p_total * 4);
+    w.count = c.take(256);   // count | ticket | (256 on) marked [B]
+    c.take(B * 4);
+    w.ell = c.take(p_total * 8);
+    w.range = c.take((int64_t)slr::kRangeGrid * nr_pad * (32 + 4 + 8));
+    w.fallback = c.take(fallback);
+    w.total = c.at;
     return w;
 }
 
@@ -320,7 +323,7 @@ SlrStats g_slr_stats;
 int slr_group_dev(int device, hipStream_t st, const double *d_t, const double *d_m, const int64_t *offsets,
                   int64_t B, const double *start, const double *step, const double *stop, const int64_t *poff,
                   const int *hints, double *d_out, double *d_pitched, int64_t pitch, void *work, int64_t work_bytes,
-                  std::vector<int64_t> &meta, bool wait_meta) {
+                  std::vector<int64_t> &host_meta, bool wait_meta) {
     const int64_t n_total = offsets[B], p_total = poff[B];
     std::vector<int> route((size_t)B);
     int64_t n_duo = 0, fb = 0;
@@ -337,48 +340,34 @@ int slr_group_dev(int device, hipStream_t st, const double *d_t, const double *d
     PDC_TRY(use_device(device));
     if (p_total == 0) return PDC_OK;
     char *base = static_cast<char *>(work);
-    // metadata: offsets | poff | route | order[4] | opre[4] | start | step | stop, B + 1 each
-    const int64_t B1 = B + 1;
-    meta.assign((size_t)(slr::kMeta * B1), 0);
-    int64_t *m_off = meta.data(), *m_poff = m_off + B1, *m_route = m_poff + B1, *m_order = m_route + B1,
-            *m_opre = m_order + 4 * B1;
-    double *m_dbl = reinterpret_cast<double *>(m_opre + 4 * B1);
-    for (int64_t b = 0; b <= B; ++b) {
-        m_off[b] = offsets[b];
-        m_poff[b] = poff[b];
-    }
+    // metadata: one upload; every duo instance's dispatch order = ragged_order (costliest curve first)
+    RaggedMeta meta(host_meta, slr::kMeta, B, base + w.meta);
+    meta.fill_offsets(offsets, poff);
+    meta.fill_linspace(slr::M_START, start, step, stop);
+    std::copy(route.begin(), route.end(), meta.i64(slr::M_ROUTE));
     int64_t mc[4], items[4];
     int n_max[4] = {0, 0, 0, 0};
-    std::vector<int64_t> rows((size_t)B1);
+    std::vector<int64_t> rows((size_t)B + 1);
     for (int c = 0; c < 4; ++c) {   // each instance's curves, most samples first, and their period prefix
         rows[0] = 0;
         for (int64_t b = 0; b < B; ++b) {
             rows[(size_t)b + 1] = rows[(size_t)b] + (route[(size_t)b] == c ? poff[b + 1] - poff[b] : 0);
             if (route[(size_t)b] == c) n_max[c] = std::max(n_max[c], (int)(offsets[b + 1] - offsets[b]));
         }
-        mc[c] = ragged_order(offsets, rows.data(), B, 1, m_order + c * B1, m_opre + c * B1);
-        items[c] = m_opre[c * B1 + mc[c]];
+        mc[c] = ragged_order(offsets, rows.data(), B, 1, meta.i64(slr::M_ORDER + c), meta.i64(slr::M_OPRE + c));
+        items[c] = meta.i64(slr::M_OPRE + c)[mc[c]];
     }
-    for (int64_t b = 0; b < B; ++b) {
-        m_route[b] = route[(size_t)b];
-        m_dbl[b] = start[b];
-        m_dbl[B1 + b] = step[b];
-        m_dbl[2 * B1 + b] = stop[b];
-    }
-    int64_t *d_meta = reinterpret_cast<int64_t *>(base + w.meta);
-    PDC_HIP(hipMemcpyAsync(d_meta, meta.data(), (size_t)(slr::kMeta * B1 * 8), hipMemcpyHostToDevice, st));
-    if (wait_meta) PDC_HIP(hipStreamSynchronize(st));   // (`meta` goes when the caller returns)
-    const double *d_dbl = reinterpret_cast<const double *>(d_meta + 11 * B1);
+    PDC_TRY(meta.upload(st, wait_meta));
 
     slr::Args a = {};
     a.t = d_t;
     a.m = d_m;
-    a.offsets = d_meta;
-    a.poff = d_meta + B1;
-    a.route = d_meta + 2 * B1;
-    a.start = d_dbl;
-    a.step = d_dbl + B1;
-    a.stop = d_dbl + 2 * B1;
+    a.offsets = meta.d_i64(slr::M_OFF);
+    a.poff = meta.d_i64(slr::M_POFF);
+    a.route = meta.d_i64(slr::M_ROUTE);
+    a.start = meta.d_f64(slr::M_START);
+    a.step = meta.d_f64(slr::M_STEP);
+    a.stop = meta.d_f64(slr::M_STOP);
     a.n_curves = B;
     a.p_total = p_total;
     a.periods = ptr<double>(base, w.periods);
@@ -424,8 +413,8 @@ int slr_group_dev(int device, hipStream_t st, const double *d_t, const double *d
         const int cus = cu_count(device);
         for (int c = 0; c < 4; ++c) {
             if (items[c] == 0) continue;
-            d.order = d_meta + (3 + c) * B1;
-            d.opre = d_meta + (7 + c) * B1;
+            d.order = meta.d_i64(slr::M_ORDER + c);
+            d.opre = meta.d_i64(slr::M_OPRE + c);
             d.mc = mc[c];
             int64_t grid = (c == 0 ? 4 : 2) * (int64_t)cus;
             grid = std::min(grid, std::min(items[c], (int64_t)slr::kRangeGrid));
@@ -497,44 +486,42 @@ struct SlJob : RaggedBatch {
     const double *t, *m, *start, *step, *stop;
     double *out;
     std::vector<int> hints;            // per curve (long curves: host_hints, as pdc_stringlength_scan computes them)
-    const RangeMax *fb_max, *nr_max;   // per-curve fallback bytes, range slots of the duo curves
+    const RangeMax *fb_max = nullptr, *nr_max = nullptr;   // per-curve fallback bytes, range slots of the duo curves
+
+    SlJob(const double *t_, const double *m_, const int64_t *offsets_, const double *start_, const double *step_,
+          const double *stop_, const int64_t *p_offsets, double *out_)
+        : t(t_), m(m_), start(start_), step(step_), stop(stop_), out(out_) {
+        offsets = offsets_;
+        rows = p_offsets;
+        negate_heights = true;   // (a string length is minimal at the period)
+    }
 
     struct Bytes {
-        int64_t in_t, in_m, out, work, total;
+        int64_t in_t, in_m, out, work, table, total;
     };
     Bytes bytes(int64_t c0, int64_t c1, int64_t p_max) const {
         const int64_t n = offsets[c1] - offsets[c0], np = rows[c1] - rows[c0], B = c1 - c0;
         Bytes g;
-        g.in_t = 0;
-        g.in_m = up256(n * 8);
-        g.out = g.in_m + up256(n * 8);
-        g.work = g.out + (out ? up256(np * 8) : 0);
-        g.total = g.work + slr_layout(B, n, np, (*nr_max)(c0, c1), (*fb_max)(c0, c1)).total +
-                  ragged_table_bytes(B, p_max, k);
+        Carve c;
+        g.in_t = c.take(n * 8);
+        g.in_m = c.take(n * 8);
+        g.out = c.take(out ? np * 8 : 0);
+        g.work = c.at;
+        g.table = g.work + slr_layout(B, n, np, (*nr_max)(c0, c1), (*fb_max)(c0, c1)).total;
+        g.total = g.table + ragged_table_bytes(B, p_max, k);
         return g;
     }
     int64_t group_bytes(int64_t c0, int64_t c1, int64_t p_max) const override { return bytes(c0, c1, p_max).total; }
 
     int run_group(RaggedSlot &s, int64_t c0, int64_t c1, int64_t p_max, double *pitched) const override {
-        const int64_t B = c1 - c0, s0 = offsets[c0], n = offsets[c1] - s0, pb = rows[c0], np = rows[c1] - pb;
-        const Bytes g = bytes(c0, c1, p_max);
-        char *p = static_cast<char *>(s.buf);
-        hipStream_t st = s.stream;
-        if (n > 0) {
-            PDC_HIP(hipMemcpyAsync(p + g.in_t, t + s0, n * 8, hipMemcpyHostToDevice, st));
-            PDC_HIP(hipMemcpyAsync(p + g.in_m, m + s0, n * 8, hipMemcpyHostToDevice, st));
-        }
-        std::vector<int64_t> off((size_t)B + 1), poff((size_t)B + 1);
-        for (int64_t b = 0; b <= B; ++b) {
-            off[(size_t)b] = offsets[c0 + b] - s0;
-            poff[(size_t)b] = rows[c0 + b] - pb;
-        }
-        PDC_TRY(slr_group_dev(s.device, st, (const double *)(p + g.in_t), (const double *)(p + g.in_m), off.data(), B,
-                              start + c0, step + c0, stop + c0, poff.data(), hints.data() + c0,
-                              out ? (double *)(p + g.out) : nullptr, pitched, p_max, p + g.work,
-                              g.total - g.work - ragged_table_bytes(B, p_max, k), s.meta, false));
-        if (out && np > 0) PDC_HIP(hipMemcpyAsync(out + pb, p + g.out, np * 8, hipMemcpyDeviceToHost, st));
-        return PDC_OK;
+        const RaggedGroup g(*this, s, c0, c1);
+        const Bytes at = bytes(c0, c1, p_max);
+        PDC_TRY(g.upload(at.in_t, t));
+        PDC_TRY(g.upload(at.in_m, m));
+        PDC_TRY(slr_group_dev(s.device, g.st, g.at<double>(at.in_t), g.at<double>(at.in_m), g.off.data(), g.B, start + c0,
+                              step + c0, stop + c0, g.roff.data(), hints.data() + c0, g.at_if<double>(out, at.out),
+                              pitched, p_max, g.buf + at.work, at.table - at.work, s.meta, false));
+        return g.rows_back(out, at.out);
     }
 };
 
@@ -577,29 +564,7 @@ int slr_host(SlJob &j, int64_t n_curves, const int *devices, int n_devices) {
     j.nr_max = &nr_max;
     g_slr_stats.marked = 0;
     g_slr_stats.long_curves = 0;
-    PDC_TRY(ragged_run("stringlength_ragged", g_slr_slots, j, n_curves, devices, n_devices));
-    if (j.k > 0 && j.height)   // the table ranked -length: heights back to the lengths themselves
-        for (int64_t i = 0; i < n_curves * j.k; ++i) j.height[i] = -j.height[i];
-    return PDC_OK;
-}
-
-SlJob slr_job(const double *t, const double *m, const int64_t *offsets, const double *start, const double *step,
-              const double *stop, const int64_t *p_offsets) {
-    SlJob j;
-    j.offsets = offsets;
-    j.rows = p_offsets;
-    j.k = 0;
-    j.by_prominence = 0;
-    j.count = j.idx = j.lo = j.hi = nullptr;
-    j.height = j.prom = nullptr;
-    j.t = t;
-    j.m = m;
-    j.start = start;
-    j.step = step;
-    j.stop = stop;
-    j.out = nullptr;
-    j.fb_max = j.nr_max = nullptr;
-    return j;
+    return ragged_run("stringlength_ragged", g_slr_slots, j, n_curves, devices, n_devices);
 }
 
 }  // namespace
@@ -638,10 +603,7 @@ int pdc_stringlength_scan_ragged_dev(int device, void *stream, const double *d_t
                                      int64_t pitch, void *work, int64_t work_bytes) {
     PDC_TRY(slr_validate("stringlength_ragged_dev", offsets, n_curves, start, step, stop, p_offsets));
     PDC_REQUIRE(d_out || d_pitched, "stringlength_ragged_dev: no output requested");
-    if (d_pitched)
-        for (int64_t b = 0; b < n_curves; ++b)
-            PDC_REQUIRE(p_offsets[b + 1] - p_offsets[b] <= pitch,
-                        "stringlength_ragged_dev: curve %lld has more periods than the pitch", (long long)b);
+    if (d_pitched) PDC_TRY(ragged_check_pitch("stringlength_ragged_dev", p_offsets, n_curves, pitch, "periods"));
     std::vector<int64_t> meta;
     return slr_group_dev(device, (hipStream_t)stream, d_t, d_m, offsets, n_curves, start, step, stop, p_offsets,
                          nullptr, d_out, d_pitched, pitch, work, work_bytes, meta, true);
@@ -652,8 +614,7 @@ int pdc_stringlength_scan_ragged(const double *t, const double *m, const int64_t
                                  const int64_t *p_offsets, double *out, const int *devices, int n_devices) {
     PDC_TRY(slr_validate("stringlength_ragged", offsets, n_curves, start, step, stop, p_offsets));
     PDC_REQUIRE(out, "stringlength_ragged: no output requested");
-    SlJob j = slr_job(t, m, offsets, start, step, stop, p_offsets);
-    j.out = out;
+    SlJob j(t, m, offsets, start, step, stop, p_offsets, out);
     return slr_host(j, n_curves, devices, n_devices);
 }
 
@@ -663,19 +624,9 @@ int pdc_stringlength_ragged_peaks(const double *t, const double *m, const int64_
                                   int64_t *idx_out, double *height_out, double *prominence_out, int64_t *half_lo_out,
                                   int64_t *half_hi_out, double *out, const int *devices, int n_devices) {
     PDC_TRY(slr_validate("stringlength_ragged_peaks", offsets, n_curves, start, step, stop, p_offsets));
-    PDC_REQUIRE(k >= 1 && k <= 1024, "stringlength_ragged_peaks: k must be 1..1024 (got %d)", k);
-    PDC_REQUIRE(count_out || idx_out || height_out || prominence_out || half_lo_out || half_hi_out || out,
-                "stringlength_ragged_peaks: no output requested");
-    SlJob j = slr_job(t, m, offsets, start, step, stop, p_offsets);
-    j.k = k;
-    j.by_prominence = by_prominence ? 1 : 0;
-    j.out = out;
-    j.count = count_out;
-    j.idx = idx_out;
-    j.height = height_out;
-    j.prom = prominence_out;
-    j.lo = half_lo_out;
-    j.hi = half_hi_out;
+    SlJob j(t, m, offsets, start, step, stop, p_offsets, out);
+    PDC_TRY(j.want_table("stringlength_ragged_peaks", k, by_prominence, count_out, idx_out, height_out, prominence_out,
+                         half_lo_out, half_hi_out, out != nullptr));
     return slr_host(j, n_curves, devices, n_devices);
 }
 

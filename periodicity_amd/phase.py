@@ -18,7 +18,7 @@ from multiprocessing import cpu_count
 import numpy as np
 
 from . import _cabi
-from .core import FSeries, TSeries
+from .core import FSeries, TSeries, _batch_errs, _batch_offsets, _batch_request, _batch_slots
 
 MAX_CORES = cpu_count()
 
@@ -126,9 +126,15 @@ class PhaseBatch(object):
             count = np.diff(self._p_offsets)
             rows = np.repeat(np.arange(count.size), count)
             j = np.arange(self._p_offsets[-1], dtype=np.int64) - np.repeat(self._p_offsets[:-1], count)
-            flat = _linspace_at(self._start[rows], self._step[rows], self._stop[rows], count[rows], j)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                flat = self._period_of(_linspace_at(self._start[rows], self._step[rows], self._stop[rows], count[rows], j))
             self._periods = np.split(flat, self._p_offsets[1:-1])
         return self._periods
+
+    @staticmethod
+    def _period_of(grid):
+        """The trial periods of the linspace values ``grid``: themselves (a subclass's grids may be reciprocal)."""
+        return grid
 
     def _frequency_at(self, rows, bins):
         """Frequency of bin ``bins`` of ``periodograms[rows]``: ascending frequency, so the period index reversed on
@@ -156,16 +162,9 @@ class StringLengthBatch(PhaseBatch):
     (``_string_periods``): ``periods[b] = 1 / linspace(start[b], stop[b], P_b)``, and whose peak table's frequencies
     are ``FSeries(1 / periods).frequency``, i.e. ``1 / (1 / f)``."""
 
-    @property
-    def periods(self):
-        if self._periods is None:
-            count = np.diff(self._p_offsets)
-            rows = np.repeat(np.arange(count.size), count)
-            j = np.arange(self._p_offsets[-1], dtype=np.int64) - np.repeat(self._p_offsets[:-1], count)
-            with np.errstate(divide="ignore", invalid="ignore"):
-                flat = 1 / _linspace_at(self._start[rows], self._step[rows], self._stop[rows], count[rows], j)
-            self._periods = np.split(flat, self._p_offsets[1:-1])
-        return self._periods
+    @staticmethod
+    def _period_of(grid):
+        return 1 / grid
 
     def _frequency_at(self, rows, bins):
         """Frequency of bin ``bins`` of ``periodograms[rows]``: ascending frequency, so the index reversed on a
@@ -211,25 +210,11 @@ class BLSBatch(PhaseBatch):
                      "transit_time": ((start_bin + box_bins / 2) / n_bins % 1) * period}
 
 
-def _bls_batch(scan, signals, errs, peaks, by_prominence, want_power):
-    """The batch of :class:`BLS` (``pdc_bls_scan_ragged``): every curve on exactly the grid its own single call would
-    scan (``_pdm_limits``), with that call's weights (``errs``, as ``GLS.batch`` takes them)."""
-    from .spectral import PeakTable
-    len_min, len_max = scan.box_lengths()
-    signals = [s if isinstance(s, TSeries) else _coerce(s) for s in signals]   # (an empty TSeries has no baseline to probe)
-    if not signals:
-        raise ValueError("BLS.batch needs at least one signal")
-    if errs is not None:
-        errs = list(errs)
-        if len(errs) != len(signals):
-            raise ValueError(f"errs has {len(errs)} entries for {len(signals)} signals")
-    peaks = int(peaks)
-    if peaks < 0 or peaks > 1024:
-        raise ValueError("peaks must be 0 .. 1024")
-    values = [np.asarray(s.values, dtype=float) for s in signals]
-    sizes = np.array([v.size for v in values], dtype=np.int64)
-    # (a curve without samples has no grid of its own: its row is empty and its best entries are -1 / NaN)
-    limits = [_pdm_limits(s, scan.p_min, scan.p_max, scan.n_periods, scan.oversample) if s.size else (0.0, 0.0, 0)
+def _period_grids(scan, signals, peaks, empty=None):
+    """Per curve, the linspace description of the grid ``_pdm_periods`` gives it from ``scan``'s parameters: ``start,
+    step, stop, p_offsets``, checked for a peak table when ``peaks``.  ``empty``: the limits of a curve without samples
+    (None: it has none, ``_pdm_limits`` raises)."""
+    limits = [_pdm_limits(s, scan.p_min, scan.p_max, scan.n_periods, scan.oversample) if empty is None or s.size else empty
               for s in signals]
     start = np.array([lim[0] for lim in limits], dtype=np.float64)
     stop = np.array([lim[1] for lim in limits], dtype=np.float64)
@@ -240,41 +225,42 @@ def _bls_batch(scan, signals, errs, peaks, by_prominence, want_power):
     step = _linspace_steps(start, stop, count)
     if peaks:
         _check_fseries_order(start, step, stop, count)
-    dy = None
-    if errs is not None and any(e is not None for e in errs):
-        parts = []
-        for v, e in zip(values, errs):
-            e = np.ones(v.size) if e is None else np.asarray(e, dtype=float).ravel()
-            if e.size != v.size:
-                raise ValueError("Input arrays have incompatible lengths.")
-            parts.append(e)
-        dy = np.concatenate(parts)
-    offsets = np.zeros(len(signals) + 1, dtype=np.int64)
-    offsets[1:] = np.cumsum(sizes)
-    p_offsets = np.zeros(len(signals) + 1, dtype=np.int64)
-    p_offsets[1:] = np.cumsum(count)
-    t = np.concatenate([np.asarray(s.time, dtype=float) for s in signals])
-    y = np.concatenate(values)
-    devices = scan.devices if scan.devices else None
-    rows, best, table = _cabi.bls_scan_ragged(t, y, dy, offsets, start, step, stop, p_offsets, int(scan.n_bins), len_min,
-                                              len_max, int(scan.min_points), scan.dips_only, k=peaks,
-                                              by_prominence=by_prominence, want_power=want_power, device=scan.device,
-                                              devices=devices)
-    res = BLSBatch(start, step, stop, p_offsets, scan.n_bins, rows, best, None)
+    return start, step, stop, _batch_offsets(count)
+
+
+def _with_peaks(res, table, by_prominence):
+    """``res`` with the binding's peak table, if there is one, as its ``peaks``."""
+    from .spectral import PeakTable
     if table is not None:
         res.peaks = PeakTable(None, table, by_prominence, frequency_at=res._frequency_at)
     return res
 
 
+def _bls_batch(scan, signals, errs, peaks, by_prominence, want_power):
+    """The batch of :class:`BLS` (``pdc_bls_scan_ragged``): every curve on exactly the grid its own single call would
+    scan (``_pdm_limits``), with that call's weights (``errs``, as ``GLS.batch`` takes them)."""
+    len_min, len_max = scan.box_lengths()
+    signals = [s if isinstance(s, TSeries) else _coerce(s) for s in signals]   # (an empty TSeries has no baseline to probe)
+    if not signals:
+        raise ValueError("BLS.batch needs at least one signal")
+    peaks = _batch_request(peaks)   # (want_power=False alone is a request: ``best`` is always produced)
+    values = [np.asarray(s.values, dtype=float) for s in signals]
+    sizes = [v.size for v in values]
+    dy = _batch_errs(errs, sizes)
+    # (a curve without samples has no grid of its own: its row is empty and its best entries are -1 / NaN)
+    start, step, stop, p_offsets = _period_grids(scan, signals, peaks, empty=(0.0, 0.0, 0))
+    t = np.concatenate([np.asarray(s.time, dtype=float) for s in signals])
+    rows, best, table = _cabi.bls_scan_ragged(t, np.concatenate(values), dy, _batch_offsets(sizes), start, step, stop,
+                                              p_offsets, int(scan.n_bins), len_min, len_max, int(scan.min_points),
+                                              scan.dips_only, k=peaks, by_prominence=by_prominence, want_power=want_power,
+                                              device=scan.device, devices=_batch_slots(scan.devices))
+    return _with_peaks(BLSBatch(start, step, stop, p_offsets, scan.n_bins, rows, best, None), table, by_prominence)
+
+
 def _string_batch(scan, signals, peaks, by_prominence, want_power):
     """The batch of :class:`StringLength` (``pdc_stringlength_scan_ragged``): every curve scaled as the single call
     scales it (``_quarter_scaled``) and scanned on exactly the grid ``_string_periods`` gives it."""
-    from .spectral import PeakTable
-    peaks = int(peaks)
-    if peaks < 0 or peaks > 1024:
-        raise ValueError("peaks must be 0 .. 1024")
-    if not want_power and peaks == 0:
-        raise ValueError("nothing requested: want_power=False needs peaks > 0")
+    peaks = _batch_request(peaks, want_power)
     coerced = []
     for b, s in enumerate(signals):
         try:
@@ -292,8 +278,7 @@ def _string_batch(scan, signals, peaks, by_prominence, want_power):
     if (sizes == 0).any():
         b = int(np.argmax(sizes == 0))
         raise ValueError(f"curve {b} has no samples: StringLength cannot scale an empty curve")
-    offsets = np.zeros(len(signals) + 1, dtype=np.int64)
-    offsets[1:] = np.cumsum(sizes)
+    offsets = _batch_offsets(sizes)
     x = np.concatenate(values)
     # _quarter_scaled for every curve at once: np.nanmax / np.nanmin are np.fmax / np.fmin reductions
     top = np.repeat(np.fmax.reduceat(x, offsets[:-1]), sizes)
@@ -310,14 +295,10 @@ def _string_batch(scan, signals, peaks, by_prominence, want_power):
             raise ValueError(f"curve {b}: a peak table needs a frequency step dphi / baseline that is finite and "
                              f"positive (got {stop[b]!r})")
     p_offsets = np.arange(len(signals) + 1, dtype=np.int64) * count
-    devices = scan.devices if scan.devices else None
     out, table = _cabi.stringlength_scan_ragged(t, m, offsets, start, step, stop, p_offsets, k=peaks,
                                                 by_prominence=by_prominence, want_power=want_power,
-                                                device=scan.device, devices=devices)
-    res = StringLengthBatch(start, step, stop, p_offsets, out, None)
-    if table is not None:
-        res.peaks = PeakTable(None, table, by_prominence, frequency_at=res._frequency_at)
-    return res
+                                                device=scan.device, devices=_batch_slots(scan.devices))
+    return _with_peaks(StringLengthBatch(start, step, stop, p_offsets, out, None), table, by_prominence)
 
 
 _KINDS = {"pdm": 0, "aov": 1, "ce": 2}
@@ -328,13 +309,8 @@ def _phase_batch(scan, kind, signals, nb, nc, peaks, by_prominence, want_power, 
     """The batch of :class:`PDM` / :class:`AOV` / :class:`ConditionalEntropy` (``pdc_phase_scan_ragged``): every
     curve on exactly the grid its own single call would scan, with that call's host-side inputs (``sigma``, the
     magnitude bins, the sub-harmonic threshold) computed the same way, per curve, and uploaded."""
-    from .spectral import PeakTable
     code = _KINDS[kind]
-    peaks = int(peaks)
-    if peaks < 0 or peaks > 1024:
-        raise ValueError("peaks must be 0 .. 1024")
-    if not want_power and peaks == 0:
-        raise ValueError("nothing requested: want_power=False needs peaks > 0")
+    peaks = _batch_request(peaks, want_power)
     signals = [_coerce(s) for s in signals]
     if not signals:
         raise ValueError(f"{type(scan).__name__}.batch needs at least one signal")
@@ -344,26 +320,15 @@ def _phase_batch(scan, kind, signals, nb, nc, peaks, by_prominence, want_power, 
         b = int(np.argmax(sizes > _CELL_SAMPLES))
         raise ValueError(f"curve {b} has {sizes[b]} samples: ConditionalEntropy.batch bins a whole curve in one "
                          f"workgroup of 16-bit cells, at most {_CELL_SAMPLES} samples")
-    limits = [_pdm_limits(s, scan.p_min, scan.p_max, scan.n_periods, scan.oversample) for s in signals]
-    start = np.array([lim[0] for lim in limits], dtype=np.float64)
-    stop = np.array([lim[1] for lim in limits], dtype=np.float64)
-    count = np.array([lim[2] for lim in limits], dtype=np.int64)
-    if (count < 0).any():
-        b = int(np.argmax(count < 0))
-        raise ValueError(f"curve {b}: number of samples, {count[b]}, must be non-negative")
+    start, step, stop, p_offsets = _period_grids(scan, signals, peaks)
     significant = None
     if subharmonic:
+        count = np.diff(p_offsets)
         if (count < 2).any():
             b = int(np.argmax(count < 2))
             raise ValueError(f"curve {b}: sub-harmonic averaging needs at least two trial periods (got {count[b]})")
         significant = np.array([1.0 - 11.0 / s.size ** 0.8 for s in signals], dtype=np.float64)
-    step = _linspace_steps(start, stop, count)
-    if peaks:
-        _check_fseries_order(start, step, stop, count)
-    offsets = np.zeros(len(signals) + 1, dtype=np.int64)
-    offsets[1:] = np.cumsum(sizes)
-    p_offsets = np.zeros(len(signals) + 1, dtype=np.int64)
-    p_offsets[1:] = np.cumsum(count)
+    offsets = _batch_offsets(sizes)
     t = np.concatenate([np.asarray(s.time, dtype=float) for s in signals])
     x = np.concatenate(values)
     sigma = None
@@ -380,19 +345,15 @@ def _phase_batch(scan, kind, signals, nb, nc, peaks, by_prominence, want_power, 
         if not ok.all():
             b = int(np.searchsorted(offsets, np.argmin(ok), side="right") - 1)
             raise ValueError(f"curve {b}: magnitude bins must lie in 0 .. n_mag-1 (a constant curve, or NaN values)")
-    devices = scan.devices if scan.devices else None
     out, table = _cabi.phase_scan_ragged(code, t, x, offsets, start, step, stop, p_offsets, nb, nc, sigma=sigma,
                                          significant=significant, k=peaks, by_prominence=by_prominence,
-                                         want_power=want_power, device=scan.device, devices=devices)
-    res = PhaseBatch(start, step, stop, p_offsets, out, None)
-    if table is not None:
-        res.peaks = PeakTable(None, table, by_prominence, frequency_at=res._frequency_at)
-    return res
+                                         want_power=want_power, device=scan.device, devices=_batch_slots(scan.devices))
+    return _with_peaks(PhaseBatch(start, step, stop, p_offsets, out, None), table, by_prominence)
 
 
-_BATCH_DOC = """Periodograms of many light curves, each on the grid its own data give (``_pdm_periods`` per curve), in
-        one set of launches (``pdc_phase_scan_ragged`` / ``pdc_phase_ragged_peaks``): what a loop of ``{cls}(...)(s)``
-        followed by ``{find}()`` gives, without a launch per curve.  Returns a :class:`PhaseBatch`.
+_BATCH_DOC = """Periodograms of many light curves, each on the grid its own data give (``{grid}`` per curve), in
+        one set of launches (``{entry}_scan_ragged`` / ``{entry}_ragged_peaks``): what a loop of ``{cls}(...)(s)``
+        followed by ``{find}()`` gives, without a launch per curve.  Returns a :class:`{result}`.
 
         peaks: int, keyword-only
             ``k > 0`` (<= 1024): also the ``k`` {what} of every periodogram, found on the device
@@ -404,6 +365,8 @@ _BATCH_DOC = """Periodograms of many light curves, each on the grid its own data
 
         With ``devices=(...)`` the curves are dealt to those device slots in contiguous groups balanced by
         ``sum n_b P_b``.  The object's own attributes (``periods``, ``periodogram`` ...) are left as they were."""
+_PHASE_DOC = dict(grid="_pdm_periods", entry="pdc_phase", result="PhaseBatch")
+_DIPS, _PEAKS = "deepest (``find_dips``) minima", "highest (``find_peaks``) maxima"
 
 
 def _average_with_double_period(thetas, periods, n_samples, shortest, longest):
@@ -470,12 +433,8 @@ class StringLength(object):
     def batch(self, signals, *, peaks=0, by_prominence=False, want_power=True):
         return _string_batch(self, signals, peaks, by_prominence, want_power)
 
-    batch.__doc__ = _BATCH_DOC.format(cls="StringLength", find="find_dips",
-                                      what="deepest (``find_dips``) minima").replace(
-        "``_pdm_periods`` per curve", "``_string_periods`` per curve").replace(
-        "``pdc_phase_scan_ragged`` / ``pdc_phase_ragged_peaks``",
-        "``pdc_stringlength_scan_ragged`` / ``pdc_stringlength_ragged_peaks``").replace(
-        ":class:`PhaseBatch`", ":class:`StringLengthBatch`")
+    batch.__doc__ = _BATCH_DOC.format(cls="StringLength", find="find_dips", what=_DIPS, grid="_string_periods",
+                                      entry="pdc_stringlength", result="StringLengthBatch")
 
 
 class PDM(object):
@@ -541,7 +500,7 @@ class PDM(object):
         return _phase_batch(self, "pdm", signals, self.nb, self.nc, peaks, by_prominence, want_power,
                             subharmonic=self.do_subharmonic)
 
-    batch.__doc__ = _BATCH_DOC.format(cls="PDM", find="find_dips", what="deepest (``find_dips``) minima")
+    batch.__doc__ = _BATCH_DOC.format(cls="PDM", find="find_dips", what=_DIPS, **_PHASE_DOC)
 
 
 class AOV(object):
@@ -586,7 +545,7 @@ class AOV(object):
     def batch(self, signals, *, peaks=0, by_prominence=False, want_power=True):
         return _phase_batch(self, "aov", signals, self.n_bins, 1, peaks, by_prominence, want_power)
 
-    batch.__doc__ = _BATCH_DOC.format(cls="AOV", find="find_peaks", what="highest (``find_peaks``) maxima")
+    batch.__doc__ = _BATCH_DOC.format(cls="AOV", find="find_peaks", what=_PEAKS, **_PHASE_DOC)
 
 
 class SuperSmoother(object):
@@ -675,8 +634,7 @@ class ConditionalEntropy(object):
     def batch(self, signals, *, peaks=0, by_prominence=False, want_power=True):
         return _phase_batch(self, "ce", signals, self.n_phase, self.n_mag, peaks, by_prominence, want_power)
 
-    batch.__doc__ = _BATCH_DOC.format(cls="ConditionalEntropy", find="find_dips",
-                                      what="deepest (``find_dips``) minima")
+    batch.__doc__ = _BATCH_DOC.format(cls="ConditionalEntropy", find="find_dips", what=_DIPS, **_PHASE_DOC)
 
 
 class GregoryLoredo(object):

@@ -17,7 +17,7 @@ import copy as _copy
 import numpy as np
 
 from . import _cabi
-from .core import FSeries, TSeries
+from .core import FSeries, TSeries, _batch_errs, _batch_offsets, _batch_request, _batch_slots
 
 __all__ = ["GLS", "LombScargle", "BGLST", "MultiHarmonicGLS", "GLSBatch", "PeakTable"]
 
@@ -120,8 +120,7 @@ class GLS(object):
         kernel rebuilds it from (``start + j*step`` per curve).  A grid of fewer than two bins has no step of its
         own; any positive step rebuilds it, and 1 is used."""
         grids = [self._grid(s) for s in signals]
-        f_offsets = np.zeros(len(grids) + 1, dtype=np.int64)
-        f_offsets[1:] = np.cumsum([g.size for g in grids])
+        f_offsets = _batch_offsets([g.size for g in grids])
         f0 = np.array([g[0] if g.size else 0.0 for g in grids], dtype=np.float64)
         delta = np.array([g[1] - g[0] if g.size > 1 else 1.0 for g in grids], dtype=np.float64)
         return grids, f0, delta, f_offsets
@@ -152,30 +151,14 @@ class GLS(object):
         signals = [_as_tseries(s) for s in signals]
         if not signals:
             raise ValueError("GLS.batch needs at least one signal")
-        if errs is not None:
-            errs = list(errs)
-            if len(errs) != len(signals):
-                raise ValueError(f"errs has {len(errs)} entries for {len(signals)} signals")
-        peaks = int(peaks)
-        if peaks < 0 or peaks > 1024:
-            raise ValueError("peaks must be 0 .. 1024")
-        if not want_power and peaks == 0:
-            raise ValueError("nothing requested: want_power=False needs peaks > 0")
+        peaks = _batch_request(peaks, want_power)
+        sizes = [len(s) for s in signals]
+        dy = _batch_errs(errs, sizes)
         grids, f0, delta, f_offsets = self._ragged_grids(signals)
         t = np.concatenate([np.asarray(s.time, dtype=float) for s in signals])
         y = np.concatenate([np.asarray(s.values, dtype=float) for s in signals])
-        offsets = np.zeros(len(signals) + 1, dtype=np.int64)
-        offsets[1:] = np.cumsum([len(s) for s in signals])
-        dy = None
-        if errs is not None and any(e is not None for e in errs):
-            parts = []
-            for s, e in zip(signals, errs):
-                e = np.ones(len(s)) if e is None else np.asarray(e, dtype=float).ravel()
-                if e.size != len(s):
-                    raise ValueError("Input arrays have incompatible lengths.")
-                parts.append(e)
-            dy = np.concatenate(parts)
-        devices = self.devices if self.devices else None
+        offsets = _batch_offsets(sizes)
+        devices = _batch_slots(self.devices)
         if peaks:
             out = _cabi.gls_ragged_peaks(t, y, dy, offsets, f0, delta, f_offsets, k=peaks, by_prominence=by_prominence,
                                          fit_mean=fit_mean, psd=self.psd, want_power=want_power, device=self.device,
