@@ -209,11 +209,8 @@ int pdc_bls_scan_dev(int device, void *stream, const double *d_t, const double *
     PDC_TRY(bls_route("bls", n, n_periods, q, work_budget(), &s, &bytes));
     hipStream_t st = (hipStream_t)stream;
     void *work = nullptr;
-    PDC_TRY(stream_scratch(device, st, bytes, &work));
     ScratchPin pin;
-    pin.device = device;
-    pin.stream = st;
-    pin.held = true;
+    PDC_TRY(pin.take(device, st, bytes, &work));
     return bls_enqueue(st, d_t, d_y, d_dy, n, d_periods, n_periods, q, s, d_power, d_depth, d_start_bin, d_box_bins, work);
 }
 
@@ -225,38 +222,32 @@ int pdc_bls_scan(const double *t, const double *y, const double *dy, int64_t n, 
     PDC_REQUIRE((t && y) || n == 0, "bls: NULL argument");
     PDC_REQUIRE((periods && power) || n_periods == 0, "bls: NULL argument");
     if (n_periods == 0) return PDC_OK;
-    PDC_TRY(use_device(device));
-    DeviceLock lock(device);
+    HostCall hc(device);
+    PDC_TRY(hc.status);
     int s = 1;
     int64_t bytes = 0;
     PDC_TRY(bls_route("bls", n, n_periods, q, host_work_budget(device), &s, &bytes));
+    // (an empty curve still gets its blocks, and nothing to copy: t, y may be NULL then)
     const int64_t nn = n > 0 ? n : 1, ints = up256(n_periods * 4);
-    void *d_t, *d_y, *d_dy = nullptr, *d_per, *d_power, *d_depth, *d_int, *d_work;
-    PDC_TRY(cached(device, SLOT_IN0, nn * 8, &d_t));
-    PDC_TRY(cached(device, SLOT_IN1, nn * 8, &d_y));
-    if (dy) PDC_TRY(cached(device, SLOT_IN2, nn * 8, &d_dy));
-    PDC_TRY(cached(device, SLOT_IN3, n_periods * 8, &d_per));
-    PDC_TRY(cached(device, SLOT_OUT0, n_periods * 8, &d_power));
-    PDC_TRY(cached(device, SLOT_OUT1, n_periods * 8, &d_depth));
-    PDC_TRY(cached(device, SLOT_OUT2, 2 * ints, &d_int));
-    PDC_TRY(cached(device, SLOT_WORK, bytes, &d_work));
-    int32_t *d_start = static_cast<int32_t *>(d_int), *d_box = reinterpret_cast<int32_t *>(static_cast<char *>(d_int) + ints);
-    hipStream_t st = nullptr;
-    PDC_TRY(host_stream(device, &st));
+    double *d_t = hc.out<double>(SLOT_IN0, nn * 8), *d_y = hc.out<double>(SLOT_IN1, nn * 8);
+    double *d_dy = dy ? hc.out<double>(SLOT_IN2, nn * 8) : nullptr;
     if (n > 0) {
-        PDC_HIP(hipMemcpyAsync(d_t, t, n * 8, hipMemcpyHostToDevice, st));
-        PDC_HIP(hipMemcpyAsync(d_y, y, n * 8, hipMemcpyHostToDevice, st));
-        if (dy) PDC_HIP(hipMemcpyAsync(d_dy, dy, n * 8, hipMemcpyHostToDevice, st));
+        hc.put(d_t, t, n * 8);
+        hc.put(d_y, y, n * 8);
+        hc.put(d_dy, dy, n * 8);
     }
-    PDC_HIP(hipMemcpyAsync(d_per, periods, n_periods * 8, hipMemcpyHostToDevice, st));
-    PDC_TRY(bls_enqueue(st, (double *)d_t, (double *)d_y, (double *)d_dy, n, (double *)d_per, n_periods, q, s,
-                        (double *)d_power, (double *)d_depth, d_start, d_box, d_work));
-    PDC_HIP(hipMemcpyAsync(power, d_power, n_periods * 8, hipMemcpyDeviceToHost, st));
-    if (depth) PDC_HIP(hipMemcpyAsync(depth, d_depth, n_periods * 8, hipMemcpyDeviceToHost, st));
-    if (start_bin) PDC_HIP(hipMemcpyAsync(start_bin, d_start, n_periods * 4, hipMemcpyDeviceToHost, st));
-    if (box_bins) PDC_HIP(hipMemcpyAsync(box_bins, d_box, n_periods * 4, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipStreamSynchronize(st));
-    return PDC_OK;
+    double *d_per = hc.in(SLOT_IN3, periods, n_periods * 8);
+    double *d_power = hc.out<double>(SLOT_OUT0, n_periods * 8), *d_depth = hc.out<double>(SLOT_OUT1, n_periods * 8);
+    char *d_int = hc.out<char>(SLOT_OUT2, 2 * ints);   // start_bin | box_bins
+    void *d_work = hc.reserve(SLOT_WORK, bytes);
+    PDC_TRY(hc.status);
+    int32_t *d_start = reinterpret_cast<int32_t *>(d_int), *d_box = reinterpret_cast<int32_t *>(d_int + ints);
+    PDC_TRY(bls_enqueue(hc.stream(), d_t, d_y, d_dy, n, d_per, n_periods, q, s, d_power, d_depth, d_start, d_box, d_work));
+    hc.back(power, d_power, n_periods * 8);
+    hc.back(depth, d_depth, n_periods * 8);
+    hc.back(start_bin, d_start, n_periods * 4);
+    hc.back(box_bins, d_box, n_periods * 4);
+    return hc.finish();
 }
 
 }  // extern "C"

@@ -1750,42 +1750,23 @@ int pdc_gls_scan_batch(const double *t, const double *y, const double *dy, const
     PDC_REQUIRE(t && y && offsets, "gls: t, y and offsets must not be NULL");
     PDC_REQUIRE(n_curves >= 1 && nf >= 0 && j_begin >= 0, "gls: negative size");
     PDC_REQUIRE(power_out || amax_out || argmax_out, "gls: no output requested");
-    for (int64_t b = 0; b < n_curves; ++b) {
-        PDC_REQUIRE(offsets[b + 1] >= offsets[b], "gls: offsets must be non-decreasing");
-        PDC_REQUIRE(!shared_t || offsets[b + 1] - offsets[b] == offsets[1] - offsets[0],
-                    "gls: with a shared time axis every curve must have the same length");
-    }
-    PDC_REQUIRE(offsets[0] == 0, "gls: offsets[0] must be 0");
-    PDC_TRY(use_device(device));
-    DeviceLock lock(device);
-    const int64_t n_total = offsets[n_curves];
-    const int64_t n_t = shared_t ? offsets[1] : n_total;
-    const int64_t wb = pdc_gls_work_bytes(n_total, n_curves, nf);
-    void *d_t, *d_y, *d_dy = nullptr, *d_off, *d_pow = nullptr, *d_amax = nullptr, *d_arg = nullptr,
-                     *d_work;
-    PDC_TRY(cached(device, SLOT_IN0, n_t * 8, &d_t));
-    PDC_TRY(cached(device, SLOT_IN1, n_total * 8, &d_y));
-    if (dy) PDC_TRY(cached(device, SLOT_IN2, n_total * 8, &d_dy));
-    PDC_TRY(cached(device, SLOT_IN3, (n_curves + 1) * 8, &d_off));
-    if (power_out) PDC_TRY(cached(device, SLOT_OUT0, n_curves * nf * 8, &d_pow));
-    if (amax_out) PDC_TRY(cached(device, SLOT_OUT1, n_curves * 8, &d_amax));
-    if (argmax_out) PDC_TRY(cached(device, SLOT_OUT2, n_curves * 8, &d_arg));
-    PDC_TRY(cached(device, SLOT_WORK, wb, &d_work));
-    hipStream_t st = nullptr;
-    PDC_TRY(host_stream(device, &st));
-    PDC_HIP(hipMemcpyAsync(d_t, t, n_t * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_y, y, n_total * 8, hipMemcpyHostToDevice, st));
-    if (dy) PDC_HIP(hipMemcpyAsync(d_dy, dy, n_total * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_off, offsets, (n_curves + 1) * 8, hipMemcpyHostToDevice, st));
-    PDC_TRY(scan_dev(device, st, (double *)d_t, (double *)d_y, (double *)d_dy, (int64_t *)d_off,
-                     n_total, n_curves, shared_t, f0, delta, j_begin, nf,
-                     fit_mean ? MODE_FIT_MEAN : MODE_NO_MEAN, psd, (double *)d_pow, nullptr, nullptr,
-                     (double *)d_amax, (int64_t *)d_arg, d_work, wb));
-    if (power_out) PDC_HIP(hipMemcpyAsync(power_out, d_pow, n_curves * nf * 8, hipMemcpyDeviceToHost, st));
-    if (amax_out) PDC_HIP(hipMemcpyAsync(amax_out, d_amax, n_curves * 8, hipMemcpyDeviceToHost, st));
-    if (argmax_out) PDC_HIP(hipMemcpyAsync(argmax_out, d_arg, n_curves * 8, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipStreamSynchronize(st));
-    return PDC_OK;
+    GlsBatchIn in;
+    PDC_TRY(in.check("gls", offsets, n_curves, shared_t));
+    HostCall hc(device);
+    const int64_t wb = pdc_gls_work_bytes(in.n_total, n_curves, nf);
+    in.upload(hc, t, y, dy, offsets, n_curves);
+    double *d_pow = power_out ? hc.out<double>(SLOT_OUT0, n_curves * nf * 8) : nullptr;
+    double *d_amax = amax_out ? hc.out<double>(SLOT_OUT1, n_curves * 8) : nullptr;
+    int64_t *d_arg = argmax_out ? hc.out<int64_t>(SLOT_OUT2, n_curves * 8) : nullptr;
+    void *d_work = hc.reserve(SLOT_WORK, wb);
+    PDC_TRY(hc.status);
+    PDC_TRY(scan_dev(device, hc.stream(), in.d_t, in.d_y, in.d_dy, in.d_off, in.n_total, n_curves, shared_t, f0, delta,
+                     j_begin, nf, fit_mean ? MODE_FIT_MEAN : MODE_NO_MEAN, psd, d_pow, nullptr, nullptr, d_amax, d_arg,
+                     d_work, wb));
+    hc.back(power_out, d_pow, n_curves * nf * 8);
+    hc.back(amax_out, d_amax, n_curves * 8);
+    hc.back(argmax_out, d_arg, n_curves * 8);
+    return hc.finish();
 }
 
 int pdc_gls_scan(const double *t, const double *y, const double *dy, int64_t n, double f0,
@@ -1821,51 +1802,33 @@ int pdc_bglst_scan(const double *t, const double *y, const double *dy, int64_t n
                    int64_t nf, const double *scalars, double *loglik_out, int device) {
     PDC_REQUIRE(t && y && scalars && (loglik_out || nf == 0), "bglst: NULL argument");
     PDC_REQUIRE(n >= 0 && nf >= 0 && j_begin >= 0, "bglst: negative size");
-    PDC_TRY(use_device(device));
-    DeviceLock lock(device);
+    HostCall hc(device);
     const int64_t wb = pdc_gls_work_bytes(n, 1, nf);
-    void *d_t, *d_y, *d_dy = nullptr, *d_out, *d_work;
-    PDC_TRY(cached(device, SLOT_IN0, n * 8, &d_t));
-    PDC_TRY(cached(device, SLOT_IN1, n * 8, &d_y));
-    if (dy) PDC_TRY(cached(device, SLOT_IN2, n * 8, &d_dy));
-    PDC_TRY(cached(device, SLOT_OUT0, nf * 8, &d_out));
-    PDC_TRY(cached(device, SLOT_WORK, wb, &d_work));
-    hipStream_t st = nullptr;
-    PDC_TRY(host_stream(device, &st));
-    PDC_HIP(hipMemcpyAsync(d_t, t, n * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_y, y, n * 8, hipMemcpyHostToDevice, st));
-    if (dy) PDC_HIP(hipMemcpyAsync(d_dy, dy, n * 8, hipMemcpyHostToDevice, st));
-    PDC_TRY(pdc_bglst_scan_dev(device, st, (double *)d_t, (double *)d_y, (double *)d_dy, n, f0, delta, j_begin, nf, scalars,
-                               (double *)d_out, d_work, wb));
-    PDC_HIP(hipMemcpyAsync(loglik_out, d_out, nf * 8, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipStreamSynchronize(st));
-    return PDC_OK;
+    double *d_t = hc.in(SLOT_IN0, t, n * 8), *d_y = hc.in(SLOT_IN1, y, n * 8), *d_dy = hc.in(SLOT_IN2, dy, n * 8);
+    double *d_out = hc.out<double>(SLOT_OUT0, nf * 8);
+    void *d_work = hc.reserve(SLOT_WORK, wb);
+    PDC_TRY(hc.status);
+    // (n < 4 is refused in there, after the uploads: the HostCall waits for them before this entry returns)
+    PDC_TRY(pdc_bglst_scan_dev(device, hc.stream(), d_t, d_y, d_dy, n, f0, delta, j_begin, nf, scalars, d_out, d_work, wb));
+    hc.back(loglik_out, d_out, nf * 8);
+    return hc.finish();
 }
 
 int pdc_trig_sums(const double *t, const double *w, int64_t n, double f0, double delta, int64_t nf,
                   double *S_out, double *C_out, int device) {
     PDC_REQUIRE(t && w && S_out && C_out, "trig_sums: NULL argument");
     PDC_REQUIRE(n >= 0 && nf >= 0, "trig_sums: negative size");
-    PDC_TRY(use_device(device));
-    DeviceLock lock(device);
+    HostCall hc(device);
     const int64_t wb = pdc_gls_work_bytes(n, 1, nf);
-    void *d_t, *d_w, *d_s, *d_c, *d_work;
-    PDC_TRY(cached(device, SLOT_IN0, n * 8, &d_t));
-    PDC_TRY(cached(device, SLOT_IN1, n * 8, &d_w));
-    PDC_TRY(cached(device, SLOT_OUT0, nf * 8, &d_s));
-    PDC_TRY(cached(device, SLOT_OUT1, nf * 8, &d_c));
-    PDC_TRY(cached(device, SLOT_WORK, wb, &d_work));
-    hipStream_t st = nullptr;
-    PDC_TRY(host_stream(device, &st));
-    PDC_HIP(hipMemcpyAsync(d_t, t, n * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_w, w, n * 8, hipMemcpyHostToDevice, st));
-    PDC_TRY(scan_dev(device, st, (double *)d_t, (double *)d_w, nullptr, nullptr, n, 1, 0, f0, delta,
-                     0, nf, MODE_RAW, 0, nullptr, (double *)d_s, (double *)d_c, nullptr, nullptr,
-                     d_work, wb));
-    PDC_HIP(hipMemcpyAsync(S_out, d_s, nf * 8, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipMemcpyAsync(C_out, d_c, nf * 8, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipStreamSynchronize(st));
-    return PDC_OK;
+    double *d_t = hc.in(SLOT_IN0, t, n * 8), *d_w = hc.in(SLOT_IN1, w, n * 8);
+    double *d_s = hc.out<double>(SLOT_OUT0, nf * 8), *d_c = hc.out<double>(SLOT_OUT1, nf * 8);
+    void *d_work = hc.reserve(SLOT_WORK, wb);
+    PDC_TRY(hc.status);
+    PDC_TRY(scan_dev(device, hc.stream(), d_t, d_w, nullptr, nullptr, n, 1, 0, f0, delta, 0, nf, MODE_RAW, 0, nullptr, d_s,
+                     d_c, nullptr, nullptr, d_work, wb));
+    hc.back(S_out, d_s, nf * 8);
+    hc.back(C_out, d_c, nf * 8);
+    return hc.finish();
 }
 
 }  // extern "C"

@@ -1048,25 +1048,15 @@ int pdc_gls_scan_fft(const double *t, const double *y, const double *dy, int64_t
                      double df, int64_t nf, int fit_mean, int psd, double *power_out, int device) {
     PDC_REQUIRE(t && y && (power_out || nf == 0), "gls_fft: NULL argument");
     PDC_REQUIRE(n >= 0 && nf >= 0, "gls_fft: negative size");
-    PDC_TRY(use_device(device));
-    DeviceLock lock(device);
+    HostCall hc(device);
     const int64_t wb = pdc_gls_fft_work_bytes(n, nf);
-    void *d_t, *d_y, *d_dy = nullptr, *d_pow, *d_work;
-    PDC_TRY(cached(device, SLOT_IN0, n * 8, &d_t));
-    PDC_TRY(cached(device, SLOT_IN1, n * 8, &d_y));
-    if (dy) PDC_TRY(cached(device, SLOT_IN2, n * 8, &d_dy));
-    PDC_TRY(cached(device, SLOT_OUT0, nf * 8, &d_pow));
-    PDC_TRY(cached(device, SLOT_WORK, wb, &d_work));
-    hipStream_t st = nullptr;
-    PDC_TRY(host_stream(device, &st));
-    PDC_HIP(hipMemcpyAsync(d_t, t, n * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_y, y, n * 8, hipMemcpyHostToDevice, st));
-    if (dy) PDC_HIP(hipMemcpyAsync(d_dy, dy, n * 8, hipMemcpyHostToDevice, st));
-    PDC_TRY(pdc_gls_scan_fft_dev(device, st, (double *)d_t, (double *)d_y, (double *)d_dy, n, fmin, df,
-                                 nf, fit_mean, psd, (double *)d_pow, d_work, wb));
-    PDC_HIP(hipMemcpyAsync(power_out, d_pow, nf * 8, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipStreamSynchronize(st));
-    return PDC_OK;
+    double *d_t = hc.in(SLOT_IN0, t, n * 8), *d_y = hc.in(SLOT_IN1, y, n * 8), *d_dy = hc.in(SLOT_IN2, dy, n * 8);
+    double *d_pow = hc.out<double>(SLOT_OUT0, nf * 8);
+    void *d_work = hc.reserve(SLOT_WORK, wb);
+    PDC_TRY(hc.status);
+    PDC_TRY(pdc_gls_scan_fft_dev(device, hc.stream(), d_t, d_y, d_dy, n, fmin, df, nf, fit_mean, psd, d_pow, d_work, wb));
+    hc.back(power_out, d_pow, nf * 8);
+    return hc.finish();
 }
 
 
@@ -1082,20 +1072,13 @@ int fft_batch_host(const double *t, const double *y, const double *dy, const int
     PDC_REQUIRE(t && y && offsets, "gls_fft_batch: t, y and offsets must not be NULL");
     PDC_REQUIRE(n_curves >= 1 && nf >= 0, "gls_fft_batch: bad size");
     PDC_REQUIRE(power_out || amax_out || argmax_out, "gls_fft_batch: no output requested");
+    // (first here, last in check(): a call wrong in both ways keeps the text it has always got)
     PDC_REQUIRE(offsets[0] == 0, "gls_fft_batch: offsets[0] must be 0");
-    int64_t n_max = 0;
-    for (int64_t b = 0; b < n_curves; ++b) {
-        const int64_t nb = offsets[b + 1] - offsets[b];
-        PDC_REQUIRE(nb >= 0, "gls_fft_batch: offsets must be non-decreasing");
-        PDC_REQUIRE(!shared_t || nb == offsets[1] - offsets[0],
-                    "gls_fft_batch: with a shared time axis every curve must have the same length");
-        n_max = nb > n_max ? nb : n_max;
-    }
+    GlsBatchIn in;
+    PDC_TRY(in.check("gls_fft_batch", offsets, n_curves, shared_t));
     if (nf == 0) return PDC_OK;
-    PDC_TRY(use_device(device));
-    DeviceLock lock(device);
-    const int64_t n_total = offsets[n_curves];
-    const int64_t n_t = shared_t ? offsets[1] : n_total;
+    HostCall hc(device);
+    const int64_t n_total = in.n_total, n_max = in.n_max;
     const int64_t nfft = fft_length(nf);
     const int ngrid = fit_mean ? 3 : 2;
     // curves per pass: grids + ping-pong scratch + power within ~8 GiB, and gridDim.y <= 65535
@@ -1110,31 +1093,19 @@ int fft_batch_host(const double *t, const double *y, const double *dy, const int
     const int64_t o_scratch = o_grid + up(chunk * ngrid * nfft * 16);
     const int64_t o_pow = o_scratch + up(chunk * ngrid * nfft * 16);
     const int64_t wb = o_pow + up(chunk * nf * 8);
-    void *d_t, *d_y, *d_dy = nullptr, *d_off, *d_amax = nullptr, *d_arg = nullptr, *d_work;
-    const int64_t n_y = picks ? n_t : n_total;   // values / errors on the device: one curve, or all of them
-    void *d_picks = nullptr;
-    PDC_TRY(cached(device, SLOT_IN0, n_t * 8, &d_t));
-    PDC_TRY(cached(device, SLOT_IN1, n_y * 8, &d_y));
-    if (dy) PDC_TRY(cached(device, SLOT_IN2, n_y * 8, &d_dy));
-    PDC_TRY(cached(device, SLOT_IN3, (n_curves + 1) * 8, &d_off));
-    if (picks) PDC_TRY(cached(device, SLOT_OUT0, n_total * 4, &d_picks));
-    if (amax_out) PDC_TRY(cached(device, SLOT_OUT1, n_curves * 8, &d_amax));
-    if (argmax_out) PDC_TRY(cached(device, SLOT_OUT2, n_curves * 8, &d_arg));
-    PDC_TRY(cached(device, SLOT_WORK, wb, &d_work));
-    hipStream_t st = nullptr;
-    PDC_TRY(host_stream(device, &st));
-    PDC_HIP(hipMemcpyAsync(d_t, t, n_t * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_y, y, n_y * 8, hipMemcpyHostToDevice, st));
-    if (dy) PDC_HIP(hipMemcpyAsync(d_dy, dy, n_y * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_off, offsets, (n_curves + 1) * 8, hipMemcpyHostToDevice, st));
-    if (picks) PDC_HIP(hipMemcpyAsync(d_picks, picks, n_total * 4, hipMemcpyHostToDevice, st));
-    char *base = static_cast<char *>(d_work);
+    in.upload(hc, t, y, dy, offsets, n_curves, picks != nullptr);   // (bootstrap: one curve of values / errors on the device)
+    const int32_t *d_picks = hc.in(SLOT_OUT0, picks, n_total * 4);
+    double *d_amax = amax_out ? hc.out<double>(SLOT_OUT1, n_curves * 8) : nullptr;
+    int64_t *d_arg = argmax_out ? hc.out<int64_t>(SLOT_OUT2, n_curves * 8) : nullptr;
+    char *base = hc.out<char>(SLOT_WORK, wb);
+    PDC_TRY(hc.status);
+    hipStream_t st = hc.stream();
     FftBatchArgs a;
-    a.picks = static_cast<const int32_t *>(d_picks);
-    a.t = (double *)d_t;
-    a.y = (double *)d_y;
-    a.dy = (double *)d_dy;
-    a.offsets = (int64_t *)d_off;
+    a.picks = d_picks;
+    a.t = in.d_t;
+    a.y = in.d_y;
+    a.dy = in.d_dy;
+    a.offsets = in.d_off;
     a.shared_t = shared_t;
     a.fit_mean = fit_mean;
     a.psd = psd;
@@ -1173,18 +1144,14 @@ int fft_batch_host(const double *t, const double *y, const double *dy, const int
         PDC_HIP(hipGetLastError());
         if (amax_out || argmax_out) {
             hipLaunchKernelGGL(row_nanmax_kernel, dim3((unsigned)bc), dim3(kBlock), 0, st, c.power, nf,
-                               d_amax ? (double *)d_amax + c0 : nullptr,
-                               d_arg ? (int64_t *)d_arg + c0 : nullptr);
+                               d_amax ? d_amax + c0 : nullptr, d_arg ? d_arg + c0 : nullptr);
             PDC_HIP(hipGetLastError());
         }
-        if (power_out)
-            PDC_HIP(hipMemcpyAsync(power_out + c0 * nf, c.power, (size_t)(bc * nf * 8),
-                                   hipMemcpyDeviceToHost, st));
+        hc.back(power_out ? power_out + c0 * nf : nullptr, c.power, bc * nf * 8);
     }
-    if (amax_out) PDC_HIP(hipMemcpyAsync(amax_out, d_amax, n_curves * 8, hipMemcpyDeviceToHost, st));
-    if (argmax_out) PDC_HIP(hipMemcpyAsync(argmax_out, d_arg, n_curves * 8, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipStreamSynchronize(st));
-    return PDC_OK;
+    hc.back(amax_out, d_amax, n_curves * 8);
+    hc.back(argmax_out, d_arg, n_curves * 8);
+    return hc.finish();
 }
 }  // namespace
 
@@ -1211,8 +1178,7 @@ int pdc_trig_sums_fft(const double *t, const double *h, int64_t n, double df, in
                       double fmin, double *S_out, double *C_out, int device) {
     PDC_REQUIRE(t && h && S_out && C_out, "trig_sums_fft: NULL argument");
     PDC_REQUIRE(n >= 1 && nf >= 1, "trig_sums_fft: need at least one sample and one frequency");
-    PDC_TRY(use_device(device));
-    DeviceLock lock(device);
+    HostCall hc(device);
     const int64_t nfft = fft_length(nf);
     double tmin = t[0], tmax = t[0];
     bool sorted = t[0] == t[0];
@@ -1222,23 +1188,17 @@ int pdc_trig_sums_fft(const double *t, const double *h, int64_t n, double df, in
         sorted = sorted && t[i] >= t[i - 1];
     }
     const double scal_host[8] = {0.0, 0.0, tmin, tmax, sorted ? 1.0 : 0.0, 0.0, 0.0, 0.0};
-    void *d_t, *d_h, *d_s, *d_c, *d_work;
-    PDC_TRY(cached(device, SLOT_IN0, n * 8, &d_t));
-    PDC_TRY(cached(device, SLOT_IN1, n * 8, &d_h));
-    PDC_TRY(cached(device, SLOT_OUT0, nf * 8, &d_s));
-    PDC_TRY(cached(device, SLOT_OUT1, nf * 8, &d_c));
-    PDC_TRY(cached(device, SLOT_WORK, nfft * 32 + 512, &d_work));
-    hipStream_t st = nullptr;
-    PDC_TRY(host_stream(device, &st));
+    double *d_t = hc.in(SLOT_IN0, t, n * 8), *d_h = hc.in(SLOT_IN1, h, n * 8);
+    double *d_s = hc.out<double>(SLOT_OUT0, nf * 8), *d_c = hc.out<double>(SLOT_OUT1, nf * 8);
+    char *d_work = hc.out<char>(SLOT_WORK, nfft * 32 + 512);
+    PDC_TRY(hc.status);
     cplx *grid = reinterpret_cast<cplx *>(d_work), *scratch = grid + nfft;
-    PDC_HIP(hipMemcpyAsync(d_t, t, n * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_h, h, n * 8, hipMemcpyHostToDevice, st));
-    double *scal = reinterpret_cast<double *>(static_cast<char *>(d_work) + nfft * 32);
-    PDC_HIP(hipMemcpyAsync(scal, scal_host, sizeof(scal_host), hipMemcpyHostToDevice, st));
-    launch_deposit(st, DepositArgs{(double *)d_t, (double *)d_h, (double *)d_h, nullptr, n, 0, 1, 0, 1, scal + 2, 0, nfft, df,
-                                   fmin, reinterpret_cast<double *>(grid)}, 1);
-    SpreadArgs s{(double *)d_t, (double *)d_h, scal, tmin, n, nfft, df, fmin,
-                 reinterpret_cast<double *>(grid)};
+    double *scal = reinterpret_cast<double *>(d_work + nfft * 32);
+    hc.put(scal, scal_host, sizeof(scal_host));
+    hipStream_t st = hc.stream();
+    launch_deposit(st, DepositArgs{d_t, d_h, d_h, nullptr, n, 0, 1, 0, 1, scal + 2, 0, nfft, df, fmin,
+                                   reinterpret_cast<double *>(grid)}, 1);
+    SpreadArgs s{d_t, d_h, scal, tmin, n, nfft, df, fmin, reinterpret_cast<double *>(grid)};
     hipLaunchKernelGGL(glsfft_spread_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock),
                        0, st, s);
     PDC_HIP(hipGetLastError());
@@ -1250,17 +1210,16 @@ int pdc_trig_sums_fft(const double *t, const double *h, int64_t n, double df, in
     e.nf = nf;
     e.df = df;
     e.fmin = fmin;
-    e.raw_s = (double *)d_s;
-    e.raw_c = (double *)d_c;
+    e.raw_s = d_s;
+    e.raw_c = d_c;
     e.tmin_value = tmin;
     e.raw = 1;
     hipLaunchKernelGGL(glsfft_epilogue_kernel, dim3((unsigned)((nf + kBlock - 1) / kBlock)),
                        dim3(kBlock), 0, st, e);
     PDC_HIP(hipGetLastError());
-    PDC_HIP(hipMemcpyAsync(S_out, d_s, nf * 8, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipMemcpyAsync(C_out, d_c, nf * 8, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipStreamSynchronize(st));
-    return PDC_OK;
+    hc.back(S_out, d_s, nf * 8);
+    hc.back(C_out, d_c, nf * 8);
+    return hc.finish();
 }
 
 }  // extern "C"

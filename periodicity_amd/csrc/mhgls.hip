@@ -306,11 +306,8 @@ int pdc_mhgls_scan_dev(int device, void *stream, const double *d_t, const double
     PDC_TRY(use_device(device));
     hipStream_t st = (hipStream_t)stream;
     void *work = nullptr;
-    PDC_TRY(stream_scratch(device, st, mh_work_bytes(n), &work));
     ScratchPin pin;
-    pin.device = device;
-    pin.stream = st;
-    pin.held = true;
+    PDC_TRY(pin.take(device, st, mh_work_bytes(n), &work));
     return mh_enqueue(st, d_t, d_y, d_dy, n, f0, delta, j_begin, nf, nterms, fit_mean, psd, d_power, work);
 }
 
@@ -319,24 +316,14 @@ int pdc_mhgls_scan(const double *t, const double *y, const double *dy, int64_t n
     PDC_REQUIRE(t && y && (power_out || nf == 0), "mhgls: NULL argument");
     PDC_TRY(mh_validate("mhgls", n, delta, j_begin, nf, nterms, fit_mean));
     if (nf == 0) return PDC_OK;
-    PDC_TRY(use_device(device));
-    DeviceLock lock(device);
-    void *d_t, *d_y, *d_dy = nullptr, *d_out, *d_work;
-    PDC_TRY(cached(device, SLOT_IN0, n * 8, &d_t));
-    PDC_TRY(cached(device, SLOT_IN1, n * 8, &d_y));
-    if (dy) PDC_TRY(cached(device, SLOT_IN2, n * 8, &d_dy));
-    PDC_TRY(cached(device, SLOT_OUT0, nf * 8, &d_out));
-    PDC_TRY(cached(device, SLOT_WORK, mh_work_bytes(n), &d_work));
-    hipStream_t st = nullptr;
-    PDC_TRY(host_stream(device, &st));
-    PDC_HIP(hipMemcpyAsync(d_t, t, n * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_y, y, n * 8, hipMemcpyHostToDevice, st));
-    if (dy) PDC_HIP(hipMemcpyAsync(d_dy, dy, n * 8, hipMemcpyHostToDevice, st));
-    PDC_TRY(mh_enqueue(st, (double *)d_t, (double *)d_y, (double *)d_dy, n, f0, delta, j_begin, nf, nterms, fit_mean, psd,
-                       (double *)d_out, d_work));
-    PDC_HIP(hipMemcpyAsync(power_out, d_out, nf * 8, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipStreamSynchronize(st));
-    return PDC_OK;
+    HostCall hc(device);
+    double *d_t = hc.in(SLOT_IN0, t, n * 8), *d_y = hc.in(SLOT_IN1, y, n * 8), *d_dy = hc.in(SLOT_IN2, dy, n * 8);
+    double *d_out = hc.out<double>(SLOT_OUT0, nf * 8);
+    void *d_work = hc.reserve(SLOT_WORK, mh_work_bytes(n));
+    PDC_TRY(hc.status);
+    PDC_TRY(mh_enqueue(hc.stream(), d_t, d_y, d_dy, n, f0, delta, j_begin, nf, nterms, fit_mean, psd, d_out, d_work));
+    hc.back(power_out, d_out, nf * 8);
+    return hc.finish();
 }
 
 }  // extern "C"

@@ -164,7 +164,7 @@ int pinned_alloc(void **hptr, int64_t bytes);
 // from then on the stream itself is busy until they have run.  Entry points that take an
 // explicit workspace (pdc_phase_scan_dev, pdc_gls_scan_dev, pdc_stringlength_scan_dev) never come here.
 // RULE: no nested pin on one (device, stream) - a caller that takes stream_scratch() twice before stream_scratch_done()
-// waits for itself.  Every `_dev` entry takes the block once, enqueues, unpins (ScratchPin).
+// waits for itself.  Every `_dev` entry takes the block once, enqueues, unpins (ScratchPin::take).
 int host_stream(int device, hipStream_t *st);   // the device's stream for host entry points (caller holds DeviceLock); destroyed by pdc_release()
 int stream_scratch(int device, hipStream_t stream, int64_t bytes, void **dptr);
 void stream_scratch_done(int device, hipStream_t stream);
@@ -173,6 +173,15 @@ struct ScratchPin {   // unpins on scope exit (also on the error returns of PDC_
     int device = -1;
     hipStream_t stream = nullptr;
     bool held = false;
+    ScratchPin() = default;
+    ScratchPin(const ScratchPin &) = delete;
+    int take(int device_, hipStream_t stream_, int64_t bytes, void **dptr) {   // stream_scratch(), and the pin is this guard's
+        const int status = stream_scratch(device_, stream_, bytes, dptr);
+        device = device_;
+        stream = stream_;
+        held = status == PDC_OK;
+        return status;
+    }
     ~ScratchPin() {
         if (held) stream_scratch_done(device, stream);
     }
@@ -250,6 +259,64 @@ struct DeviceLock {
     int device;
 };
 
+// ---- single-call host entries: the frame they share (runtime.hip) -------------------------------------------------
+// A host entry (numpy in, numpy out) checks its arguments, then opens a HostCall: use_device (it builds the device
+// table), the DeviceLock, the device's host stream, in that order.  Inputs go up through in(), outputs and SLOT_WORK are
+// reserved, the entry enqueues its own `_dev` call or launches on stream(), outputs come back through back(), finish()
+// waits.  Slots, sizes, checks and launches stay the entry's; nothing here knows a kind.
+// The status is STICKY: after the first failure (of the opening, a cached() block, a copy) every later call does
+// nothing and returns NULL, and the error text stays the first one's - so an entry checks `status` once, before it
+// enqueues.  An entry that returns before finish() with work enqueued (a late PDC_REQUIRE in a `_dev` call, a failed
+// launch) leaves copies from and into the caller's arrays in the stream: the destructor waits for them, status
+// ignored, before the lock goes.
+struct HostCall {
+    explicit HostCall(int device);
+    ~HostCall();
+    HostCall(const HostCall &) = delete;
+    int status;
+    const int device;
+    hipStream_t stream() {   // for the entry's own enqueues: from here on the destructor has something to wait for
+        busy = true;
+        return st;
+    }
+    void *reserve(Slot slot, int64_t bytes);                  // the slot's cached() block, nothing copied
+    void put(void *dev, const void *host, int64_t bytes);     // H2D into a reserved block (NULL host: no call)
+    void back(void *host, const void *dev, int64_t bytes);    // D2H (NULL host: no call)
+    int finish();                                             // the one hipStreamSynchronize; the call's status
+    template <typename T>
+    T *out(Slot slot, int64_t bytes) { return static_cast<T *>(reserve(slot, bytes)); }
+    template <typename T>
+    T *in(Slot slot, const T *host, int64_t bytes) {          // block + H2D copy (NULL host: NULL, no call)
+        T *dev = host ? out<T>(slot, bytes) : nullptr;
+        put(dev, host, bytes);
+        return dev;
+    }
+
+private:
+    DeviceLock lock;   // (taken after use_device, released after the destructor's wait)
+    hipStream_t st = nullptr;
+    bool busy = false;
+};
+
+// The inputs every GLS batch entry takes: check() before any device - offsets never decrease, under shared_t every curve
+// is as long as the first, offsets[0] == 0, each with `what` in front, in that order - and it fills the sizes; upload()
+// on the open call: t [n_t] in SLOT_IN0, y and dy (NULL: none) in SLOT_IN1 / SLOT_IN2 - n_total values, or the one
+// curve's n_t that a bootstrap resamples by index (one_curve) -, offsets [n_curves + 1] in SLOT_IN3.
+struct GlsBatchIn {
+    int64_t n_total = 0, n_t = 0, n_max = 0;   // samples of y, of t (one curve's when shared), of the longest curve
+    double *d_t = nullptr, *d_y = nullptr, *d_dy = nullptr;
+    int64_t *d_off = nullptr;
+    int check(const char *what, const int64_t *offsets, int64_t n_curves, int shared_t);
+    void upload(HostCall &hc, const double *t, const double *y, const double *dy, const int64_t *offsets, int64_t n_curves,
+                bool one_curve = false) {
+        const int64_t n_y = one_curve ? n_t : n_total;
+        d_t = hc.in(SLOT_IN0, t, n_t * 8);
+        d_y = hc.in(SLOT_IN1, y, n_y * 8);
+        d_dy = hc.in(SLOT_IN2, dy, n_y * 8);
+        d_off = hc.in(SLOT_IN3, offsets, (n_curves + 1) * 8);
+    }
+};
+
 }  // namespace pdc
 
 #define PDC_HIP(call)                                                                     \
@@ -275,5 +342,19 @@ struct DeviceLock {
             return PDC_ERR_INVALID;     \
         }                               \
     } while (0)
+
+inline int pdc::GlsBatchIn::check(const char *what, const int64_t *offsets, int64_t n_curves, int shared_t) {
+    for (int64_t b = 0; b < n_curves; ++b) {
+        const int64_t nb = offsets[b + 1] - offsets[b];
+        PDC_REQUIRE(nb >= 0, "%s: offsets must be non-decreasing", what);
+        PDC_REQUIRE(!shared_t || nb == offsets[1] - offsets[0],
+                    "%s: with a shared time axis every curve must have the same length", what);
+        n_max = nb > n_max ? nb : n_max;
+    }
+    PDC_REQUIRE(offsets[0] == 0, "%s: offsets[0] must be 0", what);
+    n_total = offsets[n_curves];
+    n_t = shared_t ? offsets[1] : n_total;
+    return PDC_OK;
+}
 
 #include "pdc_device.h"

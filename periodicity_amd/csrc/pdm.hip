@@ -424,10 +424,7 @@ int pdc::phase_stat_dev(int kind, int device, hipStream_t st, const double *d_t,
             PDC_REQUIRE(work_bytes >= sh.bytes, "phase scan: workspace too small (%lld < %lld bytes)",
                         (long long)work_bytes, (long long)sh.bytes);
         } else {   // cached per (device, stream): see pdc_internal.h on why not hipMallocAsync
-            PDC_TRY(stream_scratch(device, st, sh.bytes, &spv));
-            pin.device = device;
-            pin.stream = st;
-            pin.held = true;
+            PDC_TRY(pin.take(device, st, sh.bytes, &spv));
         }
         char *const sp = static_cast<char *>(spv);
         // PDC_PDM_POISON=1 fills the scratch with a NaN pattern first (debugging aid: every word the kernels
@@ -538,26 +535,16 @@ int phase_stat_host(int kind, const double *t, const double *x, int64_t n, const
         for (int64_t i = 0; i < n; ++i)
             PDC_REQUIRE(x[i] >= 0.0 && x[i] < (double)nc,
                         "cond_entropy: mag_bin[%lld] = %g is not a bin index in 0 .. %d", (long long)i, x[i], nc - 1);
-    PDC_TRY(use_device(device));
-    DeviceLock lock(device);
-    void *d_t, *d_x, *d_p, *d_th, *d_work;
-    const int64_t wb = phase_stat_work_bytes(kind, n, n_periods, nb < 1 ? 1 : nb, nc < 1 ? 1 : nc);
-    PDC_TRY(cached(device, SLOT_WORK, wb > 0 ? wb : 0, &d_work));
-    PDC_TRY(cached(device, SLOT_IN0, n * 8, &d_t));
-    d_x = nullptr;   // (Gregory-Loredo bins arrival times only: no values, no buffer, no statistics pass over them)
-    if (x) PDC_TRY(cached(device, SLOT_IN1, n * 8, &d_x));
-    PDC_TRY(cached(device, SLOT_IN2, n_periods * 8, &d_p));
-    PDC_TRY(cached(device, SLOT_OUT0, n_periods * 8, &d_th));
-    hipStream_t st = nullptr;
-    PDC_TRY(host_stream(device, &st));
-    PDC_HIP(hipMemcpyAsync(d_t, t, n * 8, hipMemcpyHostToDevice, st));
-    if (x) PDC_HIP(hipMemcpyAsync(d_x, x, n * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_p, periods, n_periods * 8, hipMemcpyHostToDevice, st));
-    PDC_TRY(phase_stat_dev(kind, device, st, (double *)d_t, (double *)d_x, n, (double *)d_p, n_periods, nb, nc,
-                           sigma, (double *)d_th, d_work, wb > 0 ? wb : 0));
-    PDC_HIP(hipMemcpyAsync(out, d_th, n_periods * 8, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipStreamSynchronize(st));
-    return PDC_OK;
+    HostCall hc(device);
+    const int64_t need = phase_stat_work_bytes(kind, n, n_periods, nb < 1 ? 1 : nb, nc < 1 ? 1 : nc), wb = need > 0 ? need : 0;
+    void *d_work = hc.reserve(SLOT_WORK, wb);
+    // (Gregory-Loredo bins arrival times only: no values, no buffer, no statistics pass over them)
+    double *d_t = hc.in(SLOT_IN0, t, n * 8), *d_x = hc.in(SLOT_IN1, x, n * 8), *d_p = hc.in(SLOT_IN2, periods, n_periods * 8);
+    double *d_th = hc.out<double>(SLOT_OUT0, n_periods * 8);
+    PDC_TRY(hc.status);
+    PDC_TRY(phase_stat_dev(kind, device, hc.stream(), d_t, d_x, n, d_p, n_periods, nb, nc, sigma, d_th, d_work, wb));
+    hc.back(out, d_th, n_periods * 8);
+    return hc.finish();
 }
 
 }  // namespace

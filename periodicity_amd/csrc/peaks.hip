@@ -954,11 +954,8 @@ int pdc_highest_peak_dev(int device, void *stream, const double *d_power, int64_
     segs = segs < nf / 16384 ? segs : nf / 16384;
     if (segs > 1) {
         void *sp = nullptr;
-        PDC_TRY(stream_scratch(device, st, n_curves * segs * 16, &sp));
         ScratchPin pin;
-        pin.device = device;
-        pin.stream = st;
-        pin.held = true;
+        PDC_TRY(pin.take(device, st, n_curves * segs * 16, &sp));
         double *part_v = static_cast<double *>(sp);
         long long *part_i = reinterpret_cast<long long *>(part_v + n_curves * segs);
         hipLaunchKernelGGL(highest_peak_kernel, dim3((unsigned)(n_curves * segs)), dim3(kBlock), 0, st, d_power, nf, (int)segs,
@@ -978,20 +975,15 @@ int pdc_highest_peak(const double *power, int64_t n_curves, int64_t nf, int64_t 
     PDC_REQUIRE(idx_out || val_out, "highest_peak: no output requested");
     PDC_REQUIRE(n_curves >= 0 && nf >= 0, "highest_peak: negative size");
     if (n_curves == 0) return PDC_OK;
-    PDC_TRY(use_device(device));
-    DeviceLock lock(device);
-    void *d_p, *d_i, *d_v;
-    PDC_TRY(cached(device, SLOT_OUT0, n_curves * nf * 8, &d_p));
-    PDC_TRY(cached(device, SLOT_OUT1, n_curves * 8, &d_i));
-    PDC_TRY(cached(device, SLOT_OUT2, n_curves * 8, &d_v));
-    hipStream_t st = nullptr;
-    PDC_TRY(host_stream(device, &st));
-    PDC_HIP(hipMemcpyAsync(d_p, power, n_curves * nf * 8, hipMemcpyHostToDevice, st));
-    PDC_TRY(pdc_highest_peak_dev(device, st, (double *)d_p, n_curves, nf, (int64_t *)d_i, (double *)d_v));
-    if (idx_out) PDC_HIP(hipMemcpyAsync(idx_out, d_i, n_curves * 8, hipMemcpyDeviceToHost, st));
-    if (val_out) PDC_HIP(hipMemcpyAsync(val_out, d_v, n_curves * 8, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipStreamSynchronize(st));
-    return PDC_OK;
+    HostCall hc(device);
+    double *d_p = hc.in(SLOT_OUT0, power, n_curves * nf * 8);
+    int64_t *d_i = hc.out<int64_t>(SLOT_OUT1, n_curves * 8);
+    double *d_v = hc.out<double>(SLOT_OUT2, n_curves * 8);
+    PDC_TRY(hc.status);
+    PDC_TRY(pdc_highest_peak_dev(device, hc.stream(), d_p, n_curves, nf, d_i, d_v));
+    hc.back(idx_out, d_i, n_curves * 8);
+    hc.back(val_out, d_v, n_curves * 8);
+    return hc.finish();
 }
 
 namespace {
@@ -1058,26 +1050,24 @@ int pdc_peaks_topk_dev(int device, void *stream, const double *d_power, int64_t 
 
 namespace {
 
-// device slots of the k-wide outputs + D2H; shared by the two host entry points
-int topk_outputs(int device, hipStream_t st, const double *d_pow, int64_t n_curves, int64_t nf, int k,
-                 int by_prominence, int64_t *count, int64_t *idx, double *height, double *prom,
-                 int64_t *half_lo, int64_t *half_hi) {
+// device slots of the k-wide outputs + D2H + the wait; shared by the two host entry points
+int topk_outputs(HostCall &hc, const double *d_pow, int64_t n_curves, int64_t nf, int k, int by_prominence, int64_t *count,
+                 int64_t *idx, double *height, double *prom, int64_t *half_lo, int64_t *half_hi) {
     const int64_t nk = n_curves * k;
     // one cached block: count | idx | lo | hi | height | prom
-    void *blockp;
-    PDC_TRY(cached(device, SLOT_OUT1, (n_curves + 5 * nk) * 8, &blockp));
-    int64_t *d_count = (int64_t *)blockp, *d_idx = d_count + n_curves, *d_lo = d_idx + nk, *d_hi = d_lo + nk;
+    int64_t *d_count = hc.out<int64_t>(SLOT_OUT1, (n_curves + 5 * nk) * 8);
+    PDC_TRY(hc.status);
+    int64_t *d_idx = d_count + n_curves, *d_lo = d_idx + nk, *d_hi = d_lo + nk;
     double *d_h = (double *)(d_hi + nk), *d_p = d_h + nk;
-    PDC_TRY(pdc_peaks_topk_dev(device, st, d_pow, n_curves, nf, k, by_prominence, d_count, d_idx, d_h, d_p,
+    PDC_TRY(pdc_peaks_topk_dev(hc.device, hc.stream(), d_pow, n_curves, nf, k, by_prominence, d_count, d_idx, d_h, d_p,
                                (half_lo || half_hi) ? d_lo : nullptr, (half_lo || half_hi) ? d_hi : nullptr));
-    if (count) PDC_HIP(hipMemcpyAsync(count, d_count, n_curves * 8, hipMemcpyDeviceToHost, st));
-    if (idx) PDC_HIP(hipMemcpyAsync(idx, d_idx, nk * 8, hipMemcpyDeviceToHost, st));
-    if (height) PDC_HIP(hipMemcpyAsync(height, d_h, nk * 8, hipMemcpyDeviceToHost, st));
-    if (prom) PDC_HIP(hipMemcpyAsync(prom, d_p, nk * 8, hipMemcpyDeviceToHost, st));
-    if (half_lo) PDC_HIP(hipMemcpyAsync(half_lo, d_lo, nk * 8, hipMemcpyDeviceToHost, st));
-    if (half_hi) PDC_HIP(hipMemcpyAsync(half_hi, d_hi, nk * 8, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipStreamSynchronize(st));
-    return PDC_OK;
+    hc.back(count, d_count, n_curves * 8);
+    hc.back(idx, d_idx, nk * 8);
+    hc.back(height, d_h, nk * 8);
+    hc.back(prom, d_p, nk * 8);
+    hc.back(half_lo, d_lo, nk * 8);
+    hc.back(half_hi, d_hi, nk * 8);
+    return hc.finish();
 }
 
 }  // namespace
@@ -1091,15 +1081,10 @@ int pdc_peaks_topk(const double *power, int64_t n_curves, int64_t nf, int k, int
     PDC_REQUIRE(count_out || idx_out || height_out || prominence_out || half_lo_out || half_hi_out,
                 "peaks_topk: no output requested");
     if (n_curves == 0) return PDC_OK;
-    PDC_TRY(use_device(device));
-    DeviceLock lock(device);
-    void *d_p;
-    PDC_TRY(cached(device, SLOT_OUT0, n_curves * nf * 8, &d_p));
-    hipStream_t st = nullptr;
-    PDC_TRY(host_stream(device, &st));
-    PDC_HIP(hipMemcpyAsync(d_p, power, n_curves * nf * 8, hipMemcpyHostToDevice, st));
-    return topk_outputs(device, st, (double *)d_p, n_curves, nf, k, by_prominence, count_out, idx_out,
-                        height_out, prominence_out, half_lo_out, half_hi_out);
+    HostCall hc(device);
+    double *d_p = hc.in(SLOT_OUT0, power, n_curves * nf * 8);
+    return topk_outputs(hc, d_p, n_curves, nf, k, by_prominence, count_out, idx_out, height_out, prominence_out, half_lo_out,
+                        half_hi_out);
 }
 
 // Batched periodograms reduced on the device to their k highest (or most prominent) peaks with
@@ -1112,35 +1097,18 @@ int pdc_gls_batch_peaks(const double *t, const double *y, const double *dy, cons
     PDC_REQUIRE(t && y && offsets, "gls_batch_peaks: NULL argument");
     PDC_REQUIRE(n_curves >= 1 && nf >= 0, "gls_batch_peaks: bad size");
     PDC_REQUIRE(k >= 1 && k <= kPkMaxKTotal, "gls_batch_peaks: k must be 1..%d", kPkMaxKTotal);
-    for (int64_t b = 0; b < n_curves; ++b) {
-        PDC_REQUIRE(offsets[b + 1] >= offsets[b], "gls: offsets must be non-decreasing");
-        PDC_REQUIRE(!shared_t || offsets[b + 1] - offsets[b] == offsets[1] - offsets[0],
-                    "gls: with a shared time axis every curve must have the same length");
-    }
-    PDC_REQUIRE(offsets[0] == 0, "gls: offsets[0] must be 0");
-    PDC_TRY(use_device(device));
-    DeviceLock lock(device);
-    const int64_t n_total = offsets[n_curves];
-    const int64_t n_t = shared_t ? offsets[1] : n_total;
-    const int64_t wb = pdc_gls_work_bytes(n_total, n_curves, nf);
-    void *d_t, *d_y, *d_dy = nullptr, *d_off, *d_pow, *d_work;
-    PDC_TRY(cached(device, SLOT_IN0, n_t * 8, &d_t));
-    PDC_TRY(cached(device, SLOT_IN1, n_total * 8, &d_y));
-    if (dy) PDC_TRY(cached(device, SLOT_IN2, n_total * 8, &d_dy));
-    PDC_TRY(cached(device, SLOT_IN3, (n_curves + 1) * 8, &d_off));
-    PDC_TRY(cached(device, SLOT_OUT0, n_curves * nf * 8, &d_pow));
-    PDC_TRY(cached(device, SLOT_WORK, wb, &d_work));
-    hipStream_t st = nullptr;
-    PDC_TRY(host_stream(device, &st));
-    PDC_HIP(hipMemcpyAsync(d_t, t, n_t * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_y, y, n_total * 8, hipMemcpyHostToDevice, st));
-    if (dy) PDC_HIP(hipMemcpyAsync(d_dy, dy, n_total * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_off, offsets, (n_curves + 1) * 8, hipMemcpyHostToDevice, st));
-    PDC_TRY(pdc_gls_scan_dev(device, st, (double *)d_t, (double *)d_y, (double *)d_dy, (int64_t *)d_off,
-                             n_total, n_curves, shared_t, f0, delta, 0, nf, fit_mean, psd,
-                             (double *)d_pow, nullptr, nullptr, d_work, wb));
-    return topk_outputs(device, st, (double *)d_pow, n_curves, nf, k, by_prominence, count_out, idx_out,
-                        height_out, prominence_out, half_lo_out, half_hi_out);
+    GlsBatchIn in;
+    PDC_TRY(in.check("gls", offsets, n_curves, shared_t));
+    HostCall hc(device);
+    const int64_t wb = pdc_gls_work_bytes(in.n_total, n_curves, nf);
+    in.upload(hc, t, y, dy, offsets, n_curves);
+    double *d_pow = hc.out<double>(SLOT_OUT0, n_curves * nf * 8);
+    void *d_work = hc.reserve(SLOT_WORK, wb);
+    PDC_TRY(hc.status);
+    PDC_TRY(pdc_gls_scan_dev(device, hc.stream(), in.d_t, in.d_y, in.d_dy, in.d_off, in.n_total, n_curves, shared_t, f0, delta,
+                             0, nf, fit_mean, psd, d_pow, nullptr, nullptr, d_work, wb));
+    return topk_outputs(hc, d_pow, n_curves, nf, k, by_prominence, count_out, idx_out, height_out, prominence_out, half_lo_out,
+                        half_hi_out);
 }
 
 // Batched periodograms reduced on the device to the highest peak of each (index into the grid and
@@ -1151,40 +1119,22 @@ int pdc_gls_batch_highest_peak(const double *t, const double *y, const double *d
                                double *val_out, int device) {
     PDC_REQUIRE(t && y && offsets && (idx_out || val_out), "gls_batch_highest_peak: NULL argument");
     PDC_REQUIRE(n_curves >= 1 && nf >= 0, "gls_batch_highest_peak: bad size");
-    for (int64_t b = 0; b < n_curves; ++b) {
-        PDC_REQUIRE(offsets[b + 1] >= offsets[b], "gls: offsets must be non-decreasing");
-        PDC_REQUIRE(!shared_t || offsets[b + 1] - offsets[b] == offsets[1] - offsets[0],
-                    "gls: with a shared time axis every curve must have the same length");
-    }
-    PDC_REQUIRE(offsets[0] == 0, "gls: offsets[0] must be 0");
-    PDC_TRY(use_device(device));
-    DeviceLock lock(device);
-    const int64_t n_total = offsets[n_curves];
-    const int64_t n_t = shared_t ? offsets[1] : n_total;
-    const int64_t wb = pdc_gls_work_bytes(n_total, n_curves, nf);
-    void *d_t, *d_y, *d_dy = nullptr, *d_off, *d_pow, *d_i, *d_v, *d_work;
-    PDC_TRY(cached(device, SLOT_IN0, n_t * 8, &d_t));
-    PDC_TRY(cached(device, SLOT_IN1, n_total * 8, &d_y));
-    if (dy) PDC_TRY(cached(device, SLOT_IN2, n_total * 8, &d_dy));
-    PDC_TRY(cached(device, SLOT_IN3, (n_curves + 1) * 8, &d_off));
-    PDC_TRY(cached(device, SLOT_OUT0, n_curves * nf * 8, &d_pow));
-    PDC_TRY(cached(device, SLOT_OUT1, n_curves * 8, &d_i));
-    PDC_TRY(cached(device, SLOT_OUT2, n_curves * 8, &d_v));
-    PDC_TRY(cached(device, SLOT_WORK, wb, &d_work));
-    hipStream_t st = nullptr;
-    PDC_TRY(host_stream(device, &st));
-    PDC_HIP(hipMemcpyAsync(d_t, t, n_t * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_y, y, n_total * 8, hipMemcpyHostToDevice, st));
-    if (dy) PDC_HIP(hipMemcpyAsync(d_dy, dy, n_total * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_off, offsets, (n_curves + 1) * 8, hipMemcpyHostToDevice, st));
-    PDC_TRY(pdc_gls_scan_dev(device, st, (double *)d_t, (double *)d_y, (double *)d_dy, (int64_t *)d_off,
-                             n_total, n_curves, shared_t, f0, delta, 0, nf, fit_mean, psd,
-                             (double *)d_pow, nullptr, nullptr, d_work, wb));
-    PDC_TRY(pdc_highest_peak_dev(device, st, (double *)d_pow, n_curves, nf, (int64_t *)d_i, (double *)d_v));
-    if (idx_out) PDC_HIP(hipMemcpyAsync(idx_out, d_i, n_curves * 8, hipMemcpyDeviceToHost, st));
-    if (val_out) PDC_HIP(hipMemcpyAsync(val_out, d_v, n_curves * 8, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipStreamSynchronize(st));
-    return PDC_OK;
+    GlsBatchIn in;
+    PDC_TRY(in.check("gls", offsets, n_curves, shared_t));
+    HostCall hc(device);
+    const int64_t wb = pdc_gls_work_bytes(in.n_total, n_curves, nf);
+    in.upload(hc, t, y, dy, offsets, n_curves);
+    double *d_pow = hc.out<double>(SLOT_OUT0, n_curves * nf * 8);
+    int64_t *d_i = hc.out<int64_t>(SLOT_OUT1, n_curves * 8);
+    double *d_v = hc.out<double>(SLOT_OUT2, n_curves * 8);
+    void *d_work = hc.reserve(SLOT_WORK, wb);
+    PDC_TRY(hc.status);
+    PDC_TRY(pdc_gls_scan_dev(device, hc.stream(), in.d_t, in.d_y, in.d_dy, in.d_off, in.n_total, n_curves, shared_t, f0, delta,
+                             0, nf, fit_mean, psd, d_pow, nullptr, nullptr, d_work, wb));
+    PDC_TRY(pdc_highest_peak_dev(device, hc.stream(), d_pow, n_curves, nf, d_i, d_v));
+    hc.back(idx_out, d_i, n_curves * 8);
+    hc.back(val_out, d_v, n_curves * 8);
+    return hc.finish();
 }
 
 }  // extern "C"

@@ -281,6 +281,33 @@ DeviceLock::~DeviceLock() {
     if (device >= 0 && device < (int)g_devices.size()) g_devices[device]->call_mutex.unlock();
 }
 
+HostCall::HostCall(int d) : status(use_device(d)), device(d), lock(status == PDC_OK ? d : -1) {
+    if (status == PDC_OK) status = host_stream(d, &st);
+}
+HostCall::~HostCall() {   // (before `lock` goes: members are destroyed after this body)
+    if (busy && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+}
+void *HostCall::reserve(Slot slot, int64_t bytes) {
+    void *block = nullptr;
+    if (status == PDC_OK) status = cached(device, slot, bytes, &block);
+    return block;
+}
+static int host_copy(void *dst, const void *src, int64_t bytes, hipMemcpyKind kind, hipStream_t st) {
+    PDC_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, kind, st));
+    return PDC_OK;
+}
+void HostCall::put(void *dev, const void *host, int64_t bytes) {
+    if (status == PDC_OK && host) status = host_copy(dev, host, bytes, hipMemcpyHostToDevice, stream());
+}
+void HostCall::back(void *host, const void *dev, int64_t bytes) {
+    if (status == PDC_OK && host) status = host_copy(host, dev, bytes, hipMemcpyDeviceToHost, stream());
+}
+int HostCall::finish() {
+    PDC_TRY(status);
+    busy = false;   // (whatever the wait says, it has been waited for)
+    PDC_HIP(hipStreamSynchronize(st));
+    return PDC_OK;
+}
 
 // ---- clock probe ------------------------------------------------------------------------------------------------
 // A fixed count of fp64 fmas with nothing else in the way: 16 independent chains per lane, 4 waves per SIMD (1024

@@ -3521,29 +3521,20 @@ int sorted_scan_host(int kind, const double *t, const double *v, int64_t n, cons
     const char *what = kind == 5 ? "supersmoother" : "stringlength";
     PDC_REQUIRE(t && v && (periods || n_periods == 0) && (out || n_periods == 0), "%s: NULL argument", what);
     PDC_REQUIRE(n >= 0 && n_periods >= 0, "%s: negative size", what);
-    PDC_TRY(use_device(device));
-    DeviceLock lock(device);
+    HostCall hc(device);
+    PDC_TRY(hc.status);
     // (time-ordered samples and periods that all take the slices / one-cycle modes: no lists in the workspace)
     const int hints = sorted_scan_hints(kind, t, n, periods, n_periods);
     WorkScale ws(host_work_budget(device), [&] { return sorted_scan_bytes(kind, n, n_periods, (hints & kHintLists) != 0); });
     PDC_REQUIRE_FITS(ws, what);
     const int64_t wb = ws.need;
-    void *d_t, *d_v, *d_p, *d_o, *d_w;
-    PDC_TRY(cached(device, SLOT_IN0, n * 8, &d_t));
-    PDC_TRY(cached(device, SLOT_IN1, n * 8, &d_v));
-    PDC_TRY(cached(device, SLOT_IN2, n_periods * 8, &d_p));
-    PDC_TRY(cached(device, SLOT_OUT0, n_periods * 8, &d_o));
-    PDC_TRY(cached(device, SLOT_WORK, wb, &d_w));
-    hipStream_t st = nullptr;
-    PDC_TRY(host_stream(device, &st));
-    PDC_HIP(hipMemcpyAsync(d_t, t, n * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_v, v, n * 8, hipMemcpyHostToDevice, st));
-    PDC_HIP(hipMemcpyAsync(d_p, periods, n_periods * 8, hipMemcpyHostToDevice, st));
-    PDC_TRY(sorted_scan_dev(kind, device, st, (double *)d_t, (double *)d_v, n, (double *)d_p, n_periods, alpha, (double *)d_o,
-                            d_w, wb, hints));
-    PDC_HIP(hipMemcpyAsync(out, d_o, n_periods * 8, hipMemcpyDeviceToHost, st));
-    PDC_HIP(hipStreamSynchronize(st));
-    return PDC_OK;
+    double *d_t = hc.in(SLOT_IN0, t, n * 8), *d_v = hc.in(SLOT_IN1, v, n * 8), *d_p = hc.in(SLOT_IN2, periods, n_periods * 8);
+    double *d_o = hc.out<double>(SLOT_OUT0, n_periods * 8);
+    void *d_w = hc.reserve(SLOT_WORK, wb);
+    PDC_TRY(hc.status);
+    PDC_TRY(sorted_scan_dev(kind, device, hc.stream(), d_t, d_v, n, d_p, n_periods, alpha, d_o, d_w, wb, hints));
+    hc.back(out, d_o, n_periods * 8);
+    return hc.finish();
 }
 }  // namespace
 
