@@ -219,6 +219,28 @@ int pdc_mhgls_scan_dev(int device, void *stream, const double *d_t, const double
                        double f0, double delta, int64_t j_begin, int64_t nf, int nterms, int fit_mean, int psd,
                        double *d_power);
 
+/* ---- Z^2_m and the H-test for event lists (Buccheri et al. 1983, A&A 128, 245; de Jager, Raubenheimer & Swanepoel 1989,
+ * A&A 221, 180; photon weights as Kerr 2011, ApJ 732, 38) ------------------------------------------------------------------
+ * The reference has no such class - PARITY UNPINNED BY THE REFERENCE.  Arrival times t[n] in ascending order, weights
+ * w[n] (NULL: 1), theta_i = 2 pi f (t_i - t[0]); per trial frequency f_j = f0 + (j_begin + j) delta (numpy's arange fill):
+ *     C_k = sum w_i cos(k theta_i), S_k = sum w_i sin(k theta_i), Z^2_m = (2 / sum w_i^2) sum_{k <= m} (C_k^2 + S_k^2),
+ *     h_out[j] = max_{1 <= m <= nharm} (Z^2_m - 4 m + 4), m_out[j] = the lowest m that reaches it, z2_out[j] = Z^2_nharm.
+ * Any output may be NULL, not all.  n >= 1; nf, j_begin >= 0; 1 <= nharm <= 20; delta finite and > 0.  Non-finite input
+ * gives IEEE values, never an error.  parts: workgroups that share one tile's events (0: chosen from n, nf, nharm and the
+ * device's CU count; with parts > 1 partial sums go through the workspace and are added in a fixed order, so a given
+ * count gives the same bits at every call; PDC_WORK_BUDGET_GB lowers the count, never fails).  The `_dev` form enqueues
+ * on `stream` and keeps its own workspace per (device, stream). */
+int pdc_htest_scan(const double *t, const double *w, int64_t n, double f0, double delta, int64_t j_begin, int64_t nf,
+                   int nharm, int parts, double *h_out, int32_t *m_out, double *z2_out, int device);
+int pdc_htest_scan_dev(int device, void *stream, const double *d_t, const double *d_w, int64_t n, double f0, double delta,
+                       int64_t j_begin, int64_t nf, int nharm, int parts, double *d_h, int32_t *d_m, double *d_z2);
+/* Bins per tile of the kernel instance `nharm` runs; -1 when nharm is out of range.  No GPU needed. */
+int64_t pdc_htest_tile_bins(int nharm);
+/* What the CALLING THREAD's last H-test scan launched (recorded on the host just before the launches, per host thread
+ * like pdc_test_gls_last_dispatch; zeros before the first): harmonics of the kernel instance, frequencies per thread,
+ * sample parts.  Any pointer may be NULL. */
+int pdc_htest_last_dispatch(int *ht, int *k, int *parts);
+
 /* ---- BLS: box least squares (Kovacs, Zucker & Mazeh 2002, A&A 391, 369) ----------------------------------------------
  * The reference has no such class - PARITY UNPINNED BY THE REFERENCE.  The search for a box-shaped dip (a transit, a
  * detached eclipse): per trial period the best two-level model of the folded curve.  Weights and centring as

@@ -48,6 +48,10 @@ PROTOTYPES = {
     "pdc_bglst_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _D, _D, _L, _L, _VP, _VP, _VP, _L]),
     "pdc_mhgls_scan": (_I, [_VP, _VP, _VP, _L, _D, _D, _L, _L, _I, _I, _I, _VP, _I]),
     "pdc_mhgls_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _D, _D, _L, _L, _I, _I, _I, _VP]),
+    "pdc_htest_scan": (_I, [_VP, _VP, _L, _D, _D, _L, _L, _I, _I, _VP, _VP, _VP, _I]),
+    "pdc_htest_scan_dev": (_I, [_I, _VP, _VP, _VP, _L, _D, _D, _L, _L, _I, _I, _VP, _VP, _VP]),
+    "pdc_htest_tile_bins": (_L, [_I]),
+    "pdc_htest_last_dispatch": (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "pdc_bls_scan": (_I, [_VP, _VP, _VP, _L, _VP, _L, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _I]),
     "pdc_bls_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _VP, _L, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "pdc_bls_scan_ragged": (_I, [_VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I,
@@ -286,6 +290,39 @@ def mhgls_scan(t, y, dy, f0, delta, nf, nterms=2, fit_mean=True, psd=False, j_be
     check(lib().pdc_mhgls_scan(_ptr(t), _ptr(y), _ptr(dy), t.size, f0, delta, j_begin, nf, int(nterms),
                                int(bool(fit_mean)), int(bool(psd)), _ptr(out), dev))
     return out
+
+
+def htest_scan(t, w, f0, delta, nf, nharm=20, parts=0, j_begin=0, want=("h", "m", "z2"), device=None):
+    """H-test and Z^2 of an event list per trial frequency (``pdc_htest_scan``): arrival times ``t`` in ascending
+    order, photon weights ``w`` (None: 1).  Returns ``(h, m, z2)`` - H, the harmonics that give it (int32) and
+    Z^2 at ``nharm`` harmonics -, None for what ``want`` leaves out; ``parts``: workgroups that share one tile's
+    events (0: chosen from the shape)."""
+    t = _f64(t, "t")
+    w = None if w is None else _f64(w, "w")
+    if w is not None and w.size != t.size:
+        raise ValueError("Input arrays have incompatible lengths.")
+    unknown = set(want) - {"h", "m", "z2"}
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    h = np.empty(nf, dtype=np.float64) if "h" in want else None
+    m = np.empty(nf, dtype=np.int32) if "m" in want else None
+    z2 = np.empty(nf, dtype=np.float64) if "z2" in want else None
+    dev = default_device() if device is None else device
+    check(lib().pdc_htest_scan(_ptr(t), _ptr(w), t.size, f0, delta, j_begin, nf, int(nharm), int(parts), _ptr(h), _ptr(m),
+                               _ptr(z2), dev))
+    return h, m, z2
+
+
+def htest_tile_bins(nharm):
+    """Bins per tile of the kernel instance ``nharm`` runs (-1 when out of range); no GPU needed."""
+    return int(lib().pdc_htest_tile_bins(int(nharm)))
+
+
+def htest_last_dispatch():
+    """``(ht, k, parts)`` of this thread's last H-test scan."""
+    ht, k, parts = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(lib().pdc_htest_last_dispatch(C.byref(ht), C.byref(k), C.byref(parts)))
+    return ht.value, k.value, parts.value
 
 
 def bls_scan(t, y, dy, periods, n_bins, len_min, len_max, min_points=5, dips_only=False, slices=0, device=None):

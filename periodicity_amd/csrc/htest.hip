@@ -1,0 +1,393 @@
+// Z^2_m (Rayleigh for m = 1; Buccheri et al. 1983, A&A 128, 245) and the H-test (de Jager, Raubenheimer & Swanepoel
+// 1989, A&A 221, 180) of an event list as an exact direct summation on gfx950.  Events t_i, photon weights w_i (1 where
+// none are given; Kerr 2011, ApJ 732, 38 for the weighted form), theta_i = 2 pi f (t_i - t_0), t_0 = t[0]:
+//     C_k(f) = sum w_i cos(k theta_i),  S_k(f) = sum w_i sin(k theta_i),
+//     Z^2_m(f) = (2 / sum w_i^2) sum_{k <= m} (C_k^2 + S_k^2),
+//     H(f) = max_{1 <= m <= nharm} (Z^2_m - 4 m + 4), with the lowest m that reaches the maximum.
+//
+// The reference (periodicity.spectral) has no such class: PARITY UNPINNED BY THE REFERENCE.
+//
+// Decomposition
+//   htest_prep_kernel    one workgroup: sum w^2 (block_sum, fixed order) and one 48-byte record per event
+//                        {w, w, cos(2 pi delta t'), sin(2 pi delta t'), 2 cos(2 pi delta t'), t' = t - t0}, plus the
+//                        two spare records the pipeline reads ahead.
+//   htest_scan_kernel    the skeleton of gls_sums.h as mhgls.hip uses it (rotation tables per 64-event chunk, two-set
+//                        scalar pipeline, grid walk), (sin, cos) carried unscaled; harmonics 2 .. HT of every (event,
+//                        frequency) by the Chebyshev recurrence, 2 HT running sums per frequency, one fma each with w
+//                        as the SGPR operand: 4 HT - 2 fma per pair plus the walk.  Workgroup (tile, part) streams
+//                        the part's run of whole chunks.  parts == 1: the epilogue is fused, only the outputs are
+//                        written.  parts > 1: the workgroup writes its sums to partial[part][2 HT][nf] (rows k < nharm
+//                        of C, then of S), and
+//   htest_finish_kernel  one thread per bin adds the parts in ascending order (reads coalesced over bins) and runs the
+//                        same epilogue.  No atomics: for a given `parts` the bits are the same from call to call.
+//
+// Instantiations <HT, K, BLOCK>: a call with nharm runs the smallest HT >= nharm and its epilogue takes the first nharm
+// harmonics.  The running sums are 4 HT K VGPRs; every tile is K BLOCK = 1024 frequencies, so a grid cuts into the
+// same tiles whatever nharm is.
+//     HT =  2  4  8 12 : K = 4, BLOCK = 256    32 .. 192 VGPRs of sums (192: the budget of mhgls_scan_kernel<4, 4>)
+//     HT = 16 20       : K = 2, BLOCK = 512   128, 160 VGPRs of sums; 512 threads bound the kernel to 256 VGPRs
+// A larger K at small HT would save half an fma per pair of the walk (3 per pair at K = 4, 2.5 at K = 8) against the
+// 4 HT - 2 of the harmonics; it is not worth another launch shape.
+//
+// The parts rule (parts == 0), a function of (n, nf, nharm, CU count) only:
+//     tiles = ceil(nf / 1024), chunks = ceil(n / 64)
+//     parts = min(ceil(2 CUs / tiles), max(1, chunks / 8))
+// two workgroups per CU where the grid alone does not give them, while a part keeps at least 8 chunks (512 events):
+// a part pays one write of 2 nharm K BLOCK sums and its share of the finish kernel, about what a sixteenth of a chunk
+// costs.  Under PDC_WORK_BUDGET_GB the records and the partial sums together stay within the budget: fewer parts (the
+// explicit count too), never an error.  An explicit count above 65535 (the launch grid's second dimension) is 65535.
+#include "pdc_internal.h"
+#include "gls_sums.h"
+
+#include <cmath>
+
+using namespace pdc;
+
+namespace {
+
+constexpr int kPrepBlock = 1024;
+constexpr int kFinishBlock = 256;
+constexpr int kChunk = 64;      // events per rotation-table chunk
+constexpr int kMaxHarm = 20;
+constexpr int kTile = 1024;     // frequencies per tile, every instantiation
+constexpr int kMinChunks = 8;   // chunks a part keeps under the automatic rule
+constexpr int kMaxParts = 65535;
+
+struct HtPrepArgs {
+    const double *t, *w;
+    int64_t n;
+    double delta;
+    double *rec;    // [n + 2][6]
+    double *scal;   // {sum w^2}
+};
+
+struct HtArgs {
+    const double *rec, *scal;
+    int64_t n;
+    double f0, delta;
+    int64_t j_begin, nf;
+    int nharm, parts;
+    double *partial;   // [parts][2 HT][nf], parts > 1
+    double *h;
+    int32_t *m;
+    double *z2;
+};
+
+__global__ __launch_bounds__(kPrepBlock) void htest_prep_kernel(HtPrepArgs a) {
+    __shared__ double red[kPrepBlock / 64];
+    const int tid = threadIdx.x;
+    const double t0 = a.t[0];
+    double w2 = 0.0;
+    for (int64_t i = tid; i < a.n + 2; i += kPrepBlock) {
+        if (i >= a.n) {   // the read-ahead records: finite, never accumulated
+            double2 *r = reinterpret_cast<double2 *>(a.rec + i * 6);
+            r[0] = r[1] = r[2] = make_double2(0.0, 0.0);
+            continue;
+        }
+        const double w = a.w ? a.w[i] : 1.0;
+        w2 += w * w;
+        put_record(a.rec + i * 6, w, w, a.delta, a.t[i] - t0);
+    }
+    w2 = block_sum<kPrepBlock>(w2, red);
+    if (tid == 0) a.scal[0] = w2;
+}
+
+// ---- epilogue, shared by the fused and the finish path ---------------------------------------------------------------
+// cs(k) = {C, S} of harmonic k + 1.  Cumulative Z^2_m in ascending m; H keeps the first maximum as np.argmax does (a NaN
+// candidate wins over finite ones, the first NaN stays).  Each output is written only where asked for.
+template <int HT, class Sums>
+__device__ __forceinline__ void htest_epilogue(int nharm, double scale, Sums cs, int64_t j, double *h_out, int32_t *m_out,
+                                               double *z2_out) {
+    double cum = 0.0, z = 0.0, best = 0.0;
+    int best_m = 1;
+#pragma unroll
+    for (int k = 1; k <= HT; ++k) {
+        if (k <= nharm) {
+            const double2 v = cs(k - 1);
+            cum += v.x * v.x + v.y * v.y;
+            z = scale * cum;
+            const double cand = z - (double)(4 * k - 4);
+            if (k == 1 || cand > best || (cand != cand && best == best)) {
+                best = cand;
+                best_m = k;
+            }
+        }
+    }
+    if (h_out) h_out[j] = best;
+    if (m_out) m_out[j] = best_m;
+    if (z2_out) z2_out[j] = z;
+}
+
+// ---- the scan --------------------------------------------------------------------------------------------------------
+// blockIdx.x = tile, blockIdx.y = part.  Dynamic LDS: the table of BLOCK = 512 is 76 KB.
+template <int HT, int K, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void htest_scan_kernel(HtArgs a) {
+    static_assert(K * BLOCK == kTile, "every tile is kTile frequencies");
+    constexpr int COLS = BLOCK / 64;      // 64-lane columns of the tile
+    constexpr int ROW = COLS * 8 + 8 + 1;   // + 1: rows start 16 B apart modulo 128 B (bank spread)
+    // per event: {sin, cos} of theta_tile + 8 q Theta, q < 8 COLS | {sin, cos}(b Theta), b < 8 (fill_rotation_tables)
+    extern __shared__ double2 htest_lds[];
+    double2(*tab)[ROW] = reinterpret_cast<double2(*)[ROW]>(htest_lds);   // [kChunk + 1][ROW]
+
+    const int64_t tile = blockIdx.x;
+    const int part = blockIdx.y;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int col = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t n = a.n;
+    const int64_t jt = tile * kTile;
+    const int64_t jl = jt + (int64_t)tid * K;
+    // numpy's arange fill rule: start + i*delta, two roundings (no fma)
+    const double f_tile = __dadd_rn(a.f0, __dmul_rn((double)(a.j_begin + jt), a.delta));
+    const double kdelta = (double)K * a.delta;   // spacing of the threads' first frequencies (exact)
+
+    // the part's run of whole chunks (an empty run adds zeros)
+    const int64_t chunks = (n + kChunk - 1) / kChunk;
+    const int64_t s_beg = (int64_t)part * chunks / a.parts * kChunk;
+    int64_t s_end = (int64_t)(part + 1) * chunks / a.parts * kChunk;
+    if (s_end > n) s_end = n;
+
+    double Ck[HT][K], Sk[HT][K];
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int m = 0; m < HT; ++m) Ck[m][k] = Sk[m][k] = 0.0;
+
+    const int slot_a = col * 8 + (lane >> 3), slot_b = COLS * 8 + (lane & 7);
+    for (int64_t base = s_beg; base < s_end; base += kChunk) {
+        __syncthreads();   // everyone is done with the previous chunk's tables
+        if (tid < 2 * kChunk) {   // rotation tables, two threads per event; (sin, cos) unscaled
+            const int il = tid >> 1;
+            // (rows past the end of the list are never accumulated; they only need finite input)
+            const double tp = base + il < n ? a.rec[(base + il) * 6 + 5] : 0.0;
+            fill_rotation_tables<COLS>(tab[il], tid & 1, tp, kdelta, f_tile, 1.0);
+        }
+        __syncthreads();
+        const int cnt = (int)((s_end - base) < kChunk ? (s_end - base) : kChunk);
+        // (the read-ahead touches up to two records past the run - real ones, or the prologue's spares - and the
+        // padding row of the table)
+        const double *rec = a.rec + base * 6;
+        two_set_pipeline(
+            0, cnt, [&](const int i) { return fetch_sample(tab, rec, i, slot_a, slot_b); },
+            [&](const Ahead &h) {
+                const double w = h.r[1];
+                walk_grid<K>(rot2(h.qa, h.qt), h.r[2], h.r[3], h.cd2, [&](const int k, const double s, const double c) {
+                    // harmonics of this (event, frequency): Chebyshev recurrence on the unscaled (sin, cos)
+                    const double c2 = c + c;
+                    double sm = s, cm = c, sl = 0.0, cl = 1.0;   // harmonic m and m - 1
+#pragma unroll
+                    for (int m = 1; m <= HT; ++m) {
+                        Ck[m - 1][k] = __builtin_fma(w, cm, Ck[m - 1][k]);
+                        Sk[m - 1][k] = __builtin_fma(w, sm, Sk[m - 1][k]);
+                        if (m < HT) {
+                            const double cn = __builtin_fma(c2, cm, -cl), sn = __builtin_fma(c2, sm, -sl);
+                            cl = cm;
+                            sl = sm;
+                            cm = cn;
+                            sm = sn;
+                        }
+                    }
+                });
+            });
+    }
+
+    if (a.parts == 1) {
+        const double scale = 2.0 / a.scal[0];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int64_t j = jl + k;
+            if (j < a.nf)
+                htest_epilogue<HT>(
+                    a.nharm, scale, [&](const int m) { return make_double2(Ck[m][k], Sk[m][k]); }, j, a.h, a.m, a.z2);
+        }
+        return;
+    }
+    double *out = a.partial + (int64_t)part * (2 * HT) * a.nf;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int64_t j = jl + k;
+        if (j < a.nf) {
+#pragma unroll
+            for (int m = 0; m < HT; ++m) {
+                if (m < a.nharm) {
+                    out[(int64_t)m * a.nf + j] = Ck[m][k];
+                    out[(int64_t)(HT + m) * a.nf + j] = Sk[m][k];
+                }
+            }
+        }
+    }
+}
+
+// One thread per bin; `ht` is the scan's HT (the row count of a part's block).
+__global__ __launch_bounds__(kFinishBlock) void htest_finish_kernel(HtArgs a, int ht) {
+    const int64_t j = (int64_t)blockIdx.x * kFinishBlock + threadIdx.x;
+    if (j >= a.nf) return;
+    const int64_t part_stride = (int64_t)2 * ht * a.nf;
+    htest_epilogue<kMaxHarm>(
+        a.nharm, 2.0 / a.scal[0],
+        [&](const int m) {
+            const double *pc = a.partial + (int64_t)m * a.nf + j, *ps = pc + (int64_t)ht * a.nf;
+            double c = 0.0, s = 0.0;
+            for (int p = 0; p < a.parts; ++p) {
+                c += pc[p * part_stride];
+                s += ps[p * part_stride];
+            }
+            return make_double2(c, s);
+        },
+        j, a.h, a.m, a.z2);
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------
+struct Rung {
+    int ht, k, block;
+};
+constexpr Rung kLadder[] = {{2, 4, 256}, {4, 4, 256}, {8, 4, 256}, {12, 4, 256}, {16, 2, 512}, {20, 2, 512}};
+
+const Rung *rung_of(int nharm) {
+    if (nharm < 1 || nharm > kMaxHarm) return nullptr;
+    for (const Rung &r : kLadder)
+        if (r.ht >= nharm) return &r;
+    return nullptr;
+}
+
+struct HtDispatch {
+    int ht, k, parts;
+};
+thread_local HtDispatch g_last = {};
+
+int64_t rec_bytes(int64_t n) { return up256((n + 2) * 48) + 256; }
+int64_t partial_bytes(int64_t nf, int ht, int parts) { return parts > 1 ? (int64_t)parts * 2 * ht * nf * 8 : 0; }
+
+// The parts a call runs: the automatic rule for asked == 0, then the launch limit and the budget.
+int parts_of(int asked, int64_t n, int64_t nf, int ht, int cus) {
+    int64_t parts = asked;
+    if (asked == 0) {
+        const int64_t tiles = (nf + kTile - 1) / kTile, chunks = (n + kChunk - 1) / kChunk;
+        const int64_t want = (2 * (int64_t)cus + tiles - 1) / tiles, keep = chunks / kMinChunks;
+        parts = want < keep ? want : keep;
+    }
+    if (parts > kMaxParts) parts = kMaxParts;
+    const int64_t budget = work_budget();
+    if (budget > 0 && parts > 1 && rec_bytes(n) + partial_bytes(nf, ht, (int)parts) > budget)
+        parts = (budget - rec_bytes(n)) / ((int64_t)2 * ht * nf * 8);
+    return parts < 2 ? 1 : (int)parts;
+}
+
+int ht_validate(int64_t n, double delta, int64_t j_begin, int64_t nf, int nharm, int parts, bool any_output) {
+    PDC_REQUIRE(n >= 1, "htest: at least one event is needed (got %lld)", (long long)n);
+    PDC_REQUIRE(nf >= 0 && j_begin >= 0, "htest: negative size");
+    PDC_REQUIRE(nharm >= 1 && nharm <= kMaxHarm, "htest: nharm must be 1 .. %d (got %d)", kMaxHarm, nharm);
+    PDC_REQUIRE(parts >= 0, "htest: parts must be >= 0 (got %d)", parts);
+    PDC_REQUIRE(std::isfinite(delta) && delta > 0.0, "htest: the grid step must be finite and positive");
+    PDC_REQUIRE(any_output, "htest: every output is NULL");
+    PDC_REQUIRE((nf + kTile - 1) / kTile < ((int64_t)1 << 31), "htest: grid too large");
+    return PDC_OK;
+}
+
+template <int HT, int K, int BLOCK>
+int launch_scan(hipStream_t st, const HtArgs &a) {
+    const int lds = (kChunk + 1) * (BLOCK / 64 * 8 + 8 + 1) * (int)sizeof(double2);
+    PDC_TRY(allow_dynamic_lds((const void *)htest_scan_kernel<HT, K, BLOCK>, lds));
+    const dim3 grid((unsigned)((a.nf + kTile - 1) / kTile), (unsigned)a.parts);
+    hipLaunchKernelGGL((htest_scan_kernel<HT, K, BLOCK>), grid, dim3(BLOCK), lds, st, a);
+    return PDC_OK;
+}
+
+// `work`: rec_bytes(n) of records and scalars, then partial_bytes(nf, rung.ht, parts)
+int ht_enqueue(hipStream_t st, const double *d_t, const double *d_w, int64_t n, double f0, double delta, int64_t j_begin,
+               int64_t nf, int nharm, const Rung &rung, int parts, double *d_h, int32_t *d_m, double *d_z2, void *work) {
+    HtPrepArgs p;
+    p.t = d_t;
+    p.w = d_w;
+    p.n = n;
+    p.delta = delta;
+    p.rec = static_cast<double *>(work);
+    p.scal = reinterpret_cast<double *>(static_cast<char *>(work) + up256((n + 2) * 48));
+    hipLaunchKernelGGL(htest_prep_kernel, dim3(1), dim3(kPrepBlock), 0, st, p);
+    PDC_HIP(hipGetLastError());
+    HtArgs a;
+    a.rec = p.rec;
+    a.scal = p.scal;
+    a.n = n;
+    a.f0 = f0;
+    a.delta = delta;
+    a.j_begin = j_begin;
+    a.nf = nf;
+    a.nharm = nharm;
+    a.parts = parts;
+    a.partial = reinterpret_cast<double *>(static_cast<char *>(work) + rec_bytes(n));
+    a.h = d_h;
+    a.m = d_m;
+    a.z2 = d_z2;
+    g_last = {rung.ht, rung.k, parts};
+    switch (rung.ht) {
+        case 2: PDC_TRY((launch_scan<2, 4, 256>(st, a))); break;
+        case 4: PDC_TRY((launch_scan<4, 4, 256>(st, a))); break;
+        case 8: PDC_TRY((launch_scan<8, 4, 256>(st, a))); break;
+        case 12: PDC_TRY((launch_scan<12, 4, 256>(st, a))); break;
+        case 16: PDC_TRY((launch_scan<16, 2, 512>(st, a))); break;
+        default: PDC_TRY((launch_scan<20, 2, 512>(st, a))); break;
+    }
+    PDC_HIP(hipGetLastError());
+    if (parts > 1) {
+        hipLaunchKernelGGL(htest_finish_kernel, dim3((unsigned)((nf + kFinishBlock - 1) / kFinishBlock)), dim3(kFinishBlock),
+                           0, st, a, rung.ht);
+        PDC_HIP(hipGetLastError());
+    }
+    return PDC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t pdc_htest_tile_bins(int nharm) {
+    const Rung *r = rung_of(nharm);
+    return r ? (int64_t)r->k * r->block : -1;
+}
+
+int pdc_htest_last_dispatch(int *ht, int *k, int *parts) {
+    if (ht) *ht = g_last.ht;
+    if (k) *k = g_last.k;
+    if (parts) *parts = g_last.parts;
+    return PDC_OK;
+}
+
+int pdc_htest_scan_dev(int device, void *stream, const double *d_t, const double *d_w, int64_t n, double f0, double delta,
+                       int64_t j_begin, int64_t nf, int nharm, int parts, double *d_h, int32_t *d_m, double *d_z2) {
+    PDC_TRY(ht_validate(n, delta, j_begin, nf, nharm, parts, d_h || d_m || d_z2));
+    PDC_REQUIRE(d_t, "htest: NULL argument");
+    if (nf == 0) return PDC_OK;
+    PDC_TRY(use_device(device));
+    const Rung &rung = *rung_of(nharm);
+    parts = parts_of(parts, n, nf, rung.ht, cu_count(device));
+    hipStream_t st = (hipStream_t)stream;
+    void *work = nullptr;
+    ScratchPin pin;
+    PDC_TRY(pin.take(device, st, rec_bytes(n) + partial_bytes(nf, rung.ht, parts), &work));
+    return ht_enqueue(st, d_t, d_w, n, f0, delta, j_begin, nf, nharm, rung, parts, d_h, d_m, d_z2, work);
+}
+
+int pdc_htest_scan(const double *t, const double *w, int64_t n, double f0, double delta, int64_t j_begin, int64_t nf,
+                   int nharm, int parts, double *h_out, int32_t *m_out, double *z2_out, int device) {
+    PDC_TRY(ht_validate(n, delta, j_begin, nf, nharm, parts, h_out || m_out || z2_out));
+    PDC_REQUIRE(t, "htest: NULL argument");
+    if (nf == 0) return PDC_OK;
+    HostCall hc(device);
+    PDC_TRY(hc.status);
+    const Rung &rung = *rung_of(nharm);
+    parts = parts_of(parts, n, nf, rung.ht, cu_count(device));
+    double *d_t = hc.in(SLOT_IN0, t, n * 8), *d_w = hc.in(SLOT_IN1, w, n * 8);
+    double *d_h = h_out ? hc.out<double>(SLOT_OUT0, nf * 8) : nullptr;
+    int32_t *d_m = m_out ? hc.out<int32_t>(SLOT_OUT1, nf * 4) : nullptr;
+    double *d_z2 = z2_out ? hc.out<double>(SLOT_OUT2, nf * 8) : nullptr;
+    void *d_work = hc.reserve(SLOT_WORK, rec_bytes(n) + partial_bytes(nf, rung.ht, parts));
+    PDC_TRY(hc.status);
+    PDC_TRY(ht_enqueue(hc.stream(), d_t, d_w, n, f0, delta, j_begin, nf, nharm, rung, parts, d_h, d_m, d_z2, d_work));
+    hc.back(h_out, d_h, nf * 8);
+    hc.back(m_out, d_m, nf * 4);
+    hc.back(z2_out, d_z2, nf * 8);
+    return hc.finish();
+}
+
+}  // extern "C"

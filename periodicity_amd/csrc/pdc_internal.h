@@ -242,6 +242,9 @@ struct WorkScale {
 // hipSetDevice + range check; every entry point starts here.
 int use_device(int device);
 
+// Compute units of a device (cached per device; 256 where the runtime does not say).
+int cu_count(int device);
+
 // Raises a kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) on the CURRENT device,
 // once per (device, kernel): the attribute belongs to the device's copy of the kernel, so a process that
 // drives several GPUs has to set it on each of them.

@@ -62,6 +62,18 @@ int use_device(int device) {
     return PDC_OK;
 }
 
+// Compute units of a device, asked once per device (256 where the runtime does not say).
+int cu_count(int device) {
+    static int cached[64] = {};
+    if (device < 0 || device >= 64) return 256;
+    if (cached[device] == 0) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || v <= 0) v = 256;
+        cached[device] = v;
+    }
+    return cached[device];
+}
+
 static std::atomic<int64_t> g_device_allocs{0}, g_pinned_allocs{0};
 
 int device_alloc(void **dptr, int64_t bytes) {

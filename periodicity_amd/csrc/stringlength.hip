@@ -2763,17 +2763,6 @@ int launch_duo(const duo::DuoArgs &a, int64_t grid, hipStream_t st) {
     return PDC_OK;
 }
 
-int cu_count(int device) {
-    static int cached[64] = {};
-    if (device < 0 || device >= 64) return 256;
-    if (cached[device] == 0) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || v <= 0) v = 256;
-        cached[device] = v;
-    }
-    return cached[device];
-}
-
 
 stream::StreamArgs stream_args(const StreamShape &h, char *area, const double *d_t, const double *d_m,
                                const double *d_periods, int64_t n, double *d_ell) {

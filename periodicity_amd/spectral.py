@@ -19,7 +19,7 @@ import numpy as np
 from . import _cabi
 from .core import FSeries, TSeries, _batch_errs, _batch_offsets, _batch_request, _batch_slots
 
-__all__ = ["GLS", "LombScargle", "BGLST", "MultiHarmonicGLS", "GLSBatch", "PeakTable"]
+__all__ = ["GLS", "LombScargle", "BGLST", "MultiHarmonicGLS", "HTest", "ZTest", "GLSBatch", "PeakTable"]
 
 
 def _as_tseries(signal):
@@ -474,3 +474,136 @@ class MultiHarmonicGLS(GLS):
 
     def batch(self, *args, **kwargs):
         raise NotImplementedError("MultiHarmonicGLS.batch is not implemented: the ragged-grid batch computes GLS power only")
+
+
+class _EventScan(object):
+    """What ``HTest`` and ``ZTest`` share: the event list, its grid (the rule of ``GLS``) and the one library call."""
+
+    MAX_HARMONICS = 20
+
+    def __init__(self, fmin, fmax, n, harmonics, name, device):
+        if isinstance(harmonics, bool) or harmonics != int(harmonics) or not 1 <= int(harmonics) <= self.MAX_HARMONICS:
+            raise ValueError(f"{name} must be an integer 1 .. {self.MAX_HARMONICS}")
+        self.fmin = fmin
+        self.fmax = fmax
+        self.n = n
+        self.device = device
+        self._nharm = int(harmonics)
+
+    def _scan(self, signal, weights, want):
+        """Sorts the events (weights follow), builds the grid, calls the library; ``(h, m, z2)`` as ``want`` asks."""
+        if isinstance(signal, TSeries) or (hasattr(signal, "time") and hasattr(signal, "values")):
+            t = np.asarray(signal.time, dtype=float)
+        else:
+            t = np.asarray(signal, dtype=float)
+        if t.ndim != 1:
+            raise ValueError("Only one-dimensional event lists are supported.")
+        if t.size < 2:
+            raise ValueError("At least two events are needed to build the frequency grid.")
+        w = None
+        if weights is not None:
+            w = np.asarray(weights, dtype=float)
+            if w.ndim != 1 or w.size != t.size:
+                raise ValueError("Input arrays have incompatible lengths.")
+        order = np.argsort(t, kind="stable")
+        t = t[order]
+        w = None if w is None else w[order]
+        events = TSeries(t, assume_sorted=True)
+        self.frequency = self._grid(events)
+        f0, delta, nf = _cabi.grid_params(self.frequency)
+        if nf < 2:   # a grid of one bin has no step of its own; any positive step rebuilds it
+            delta = 1.0
+        out = _cabi.htest_scan(t, w, f0, delta, nf, nharm=self._nharm, want=want,
+                               device=_cabi.pick_device(self.device, None))
+        self.signal = events
+        self.weights = w
+        return out
+
+    def _grid(self, events):
+        """The grid of ``GLS._grid`` with the events as time stamps."""
+        df = 1.0 / events.baseline / self.n
+        fmin = 0.5 * df if self.fmin is None else self.fmin
+        fmax = 0.5 / events.median_dt if self.fmax is None else self.fmax
+        return np.arange(fmin, fmax + df, df)
+
+    def copy(self):
+        return _copy.deepcopy(self)
+
+
+class HTest(_EventScan):
+    """H-test periodogram of an event list (de Jager, Raubenheimer & Swanepoel 1989, A&A 221, 180): the search for
+    pulsations in photon arrival times when the pulse shape is not known.  The reference has no such class -
+    **parity unpinned by the reference**.
+
+    With ``theta_i = 2 pi f (t_i - t_0)``, ``t_0`` the earliest event, and photon weights ``w_i`` (1 without;
+    Kerr 2011, ApJ 732, 38), ``C_k = sum w_i cos(k theta_i)``, ``S_k = sum w_i sin(k theta_i)``,
+
+        ``Z2_m(f) = (2 / sum w_i**2) sum_{k <= m} (C_k**2 + S_k**2)``   (Buccheri et al. 1983, A&A 128, 245),
+        ``H(f) = max_{1 <= m <= max_harmonics} (Z2_m - 4 m + 4)``,
+
+    and ``harmonics(f)`` is the lowest ``m`` that reaches the maximum.  The grid is that of ``GLS`` with the events
+    as time stamps.  Its default ``fmin``, half a cycle per baseline, sits where the finite window leaks into every
+    ``Z2_m`` - events spread evenly over the baseline give ``H`` of about ``8 N / pi**2`` in the first bin - so a
+    search should set ``fmin`` to a few cycles per baseline.  Evaluated by ``csrc/htest.hip``; nothing here
+    computes a periodogram on the CPU.
+
+    ``signal``: a ``TSeries`` contributes its time stamps (its values are not used, as in ``GregoryLoredo``); a raw
+    one-dimensional array IS the list of arrival times.  Events are sorted before the grid is built and
+    ``weights`` follow their events.
+
+    Parameters
+    ----------
+    fmin, fmax, n: as ``GLS``.
+    max_harmonics: int, keyword-only, optional
+        Largest number of harmonics tried, 1 .. 20 (default 20, as in the paper).
+    device: int, keyword-only, optional
+
+    After a call: ``.frequency``, ``.periodogram`` (H), ``.harmonics`` (int array), ``.z2`` (``FSeries`` of Z2 at
+    ``max_harmonics``), ``.signal`` (the sorted events) and ``.weights``.
+    """
+
+    def __init__(self, fmin=None, fmax=None, n=5, *, max_harmonics=20, device=None):
+        super().__init__(fmin, fmax, n, max_harmonics, "max_harmonics", device)
+        self.max_harmonics = self._nharm
+
+    def __call__(self, signal, weights=None):
+        h, m, z2 = self._scan(signal, weights, ("h", "m", "z2"))
+        self.harmonics = m
+        self.z2 = FSeries(self.frequency, z2)
+        self.periodogram = FSeries(self.frequency, h)
+        return self.periodogram
+
+    @staticmethod
+    def fap(h):
+        """Single-trial tail probability of H, ``min(1, exp(-0.4 H))`` (de Jager & Busching 2010, A&A 517, L9)."""
+        return np.minimum(1.0, np.exp(-0.4 * np.asarray(h, dtype=float)))
+
+
+class ZTest(_EventScan):
+    """Z2_n periodogram of an event list (Buccheri et al. 1983, A&A 128, 245) with a fixed number of harmonics;
+    ``nharm=1`` is the Rayleigh test.  The reference has no such class - **parity unpinned by the reference**.
+    Definitions, grid, inputs and the advice on ``fmin`` as for ``HTest``; evaluated by ``csrc/htest.hip``.
+
+    Parameters
+    ----------
+    fmin, fmax, n: as ``GLS``.
+    nharm: int, keyword-only, optional
+        Harmonics summed, 1 .. 20 (default 2).
+    device: int, keyword-only, optional
+
+    After a call: ``.frequency``, ``.periodogram``, ``.signal`` (the sorted events) and ``.weights``.
+    """
+
+    def __init__(self, fmin=None, fmax=None, n=5, *, nharm=2, device=None):
+        super().__init__(fmin, fmax, n, nharm, "nharm", device)
+        self.nharm = self._nharm
+
+    def __call__(self, signal, weights=None):
+        _, _, z2 = self._scan(signal, weights, ("z2",))
+        self.periodogram = FSeries(self.frequency, z2)
+        return self.periodogram
+
+    def fap(self, z):
+        """Single-trial tail probability of Z2: chi-squared with ``2 nharm`` degrees of freedom."""
+        from scipy.stats import chi2
+        return chi2.sf(z, 2 * self.nharm)
