@@ -241,6 +241,41 @@ int64_t pdc_htest_tile_bins(int nharm);
  * sample parts.  Any pointer may be NULL. */
 int pdc_htest_last_dispatch(int *ht, int *k, int *parts);
 
+/* ---- the H-test and Z^2_m over the (frequency, spin-down) plane ---------------------------------------------------------
+ * The statistic of pdc_htest_scan with the phase f tau_i + fdot tau_i^2 / 2 cycles, tau_i = t_i - epoch, for every
+ * frequency f_j of the grid (as pdc_htest_scan) and every fdot[r], r < nfd (any finite values, any order), reduced on
+ * the device.  stat 0: the value of a cell is H (and its m the lowest number of harmonics that reaches it); stat 1: the
+ * value is Z^2_nharm, there is no m, and m_plane_out and ridge_m_out must be NULL.  A row with fdot = 0 holds the bits
+ * pdc_htest_scan gives with the same `parts`, whatever the epoch.  Outputs, any of them NULL, not all:
+ *     plane_out[nfd][nf], m_plane_out[nfd][nf]   the value and m of every cell;
+ *     ridge_out[nf], ridge_row_out[nf], ridge_m_out[nf]   per frequency the largest value over the rows, its row and m
+ *         as np.nanargmax(plane, axis=0) finds it: NaN never wins, the lowest row of equal maxima wins; a bin with no
+ *         finite value has value NaN, row -1 and m -1;
+ *     best_out[1], best_at_out[3] = (bin, row, m)   the largest ridge value as np.nanargmax(ridge) finds it (the lowest
+ *         bin of equal maxima; m is nharm with stat 1); NaN and (-1, -1, -1) where nothing is finite.
+ * Checked before any device is looked for: what pdc_htest_scan checks, nfd >= 1, a finite epoch, stat, and in the host
+ * form finite fdot entries (the `_dev` form cannot look at them: a non-finite entry gives a NaN row there).
+ * parts: as pdc_htest_scan, 0 chooses from n, nf, nfd, nharm and the CU count with the rows of a launch counted as
+ * workgroups.  A launch takes min(nfd, 65535) rows; the workspace holds, per row of a launch, the partial sums
+ * (parts > 1) or the values and m the caller does not take (parts == 1).  PDC_WORK_BUDGET_GB lowers the rows per launch
+ * first, then the parts, never fails, and changes no bit of the plane, the ridge or the best cell as long as the
+ * parts stay.  No atomics: the same bits from call to call.  The `_dev` form takes device pointers (fdot too), enqueues
+ * on `stream` and keeps its own workspace per (device, stream). */
+int pdc_htest_fdot_scan(const double *t, const double *w, int64_t n, double f0, double delta, int64_t j_begin, int64_t nf,
+                        const double *fdot, int64_t nfd, double epoch, int nharm, int stat, int parts, double *plane_out,
+                        int32_t *m_plane_out, double *ridge_out, int32_t *ridge_row_out, int32_t *ridge_m_out,
+                        double *best_out, int64_t *best_at_out, int device);
+int pdc_htest_fdot_scan_dev(int device, void *stream, const double *d_t, const double *d_w, int64_t n, double f0,
+                            double delta, int64_t j_begin, int64_t nf, const double *d_fdot, int64_t nfd, double epoch,
+                            int nharm, int stat, int parts, double *d_plane, int32_t *d_m_plane, double *d_ridge,
+                            int32_t *d_ridge_row, int32_t *d_ridge_m, double *d_best, int64_t *d_best_at);
+/* What the CALLING THREAD's last plane scan launched (as pdc_htest_last_dispatch), with the rows of a launch and the
+ * number of launches.  Any pointer may be NULL. */
+int pdc_htest_fdot_last_dispatch(int *ht, int *k, int *parts, int *rows_per_launch, int64_t *launches);
+/* Workspace bytes of a plane scan under the current PDC_WORK_BUDGET_GB, for the H-test with (want_plane != 0) or without
+ * both planes; a device of 256 CUs is assumed for parts == 0.  -1 for sizes out of range.  No GPU needed. */
+int64_t pdc_htest_fdot_work_bytes(int64_t n, int64_t nf, int64_t nfd, int nharm, int parts, int want_plane);
+
 /* ---- BLS: box least squares (Kovacs, Zucker & Mazeh 2002, A&A 391, 369) ----------------------------------------------
  * The reference has no such class - PARITY UNPINNED BY THE REFERENCE.  The search for a box-shaped dip (a transit, a
  * detached eclipse): per trial period the best two-level model of the folded curve.  Weights and centring as

@@ -52,6 +52,11 @@ PROTOTYPES = {
     "pdc_htest_scan_dev": (_I, [_I, _VP, _VP, _VP, _L, _D, _D, _L, _L, _I, _I, _VP, _VP, _VP]),
     "pdc_htest_tile_bins": (_L, [_I]),
     "pdc_htest_last_dispatch": (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "pdc_htest_fdot_scan": (_I, [_VP, _VP, _L, _D, _D, _L, _L, _VP, _L, _D, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I]),
+    "pdc_htest_fdot_scan_dev": (_I, [_I, _VP, _VP, _VP, _L, _D, _D, _L, _L, _VP, _L, _D, _I, _I, _I,
+                                     _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pdc_htest_fdot_last_dispatch": (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), c_int64_p]),
+    "pdc_htest_fdot_work_bytes": (_L, [_L, _L, _L, _I, _I, _I]),
     "pdc_bls_scan": (_I, [_VP, _VP, _VP, _L, _VP, _L, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _I]),
     "pdc_bls_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _VP, _L, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "pdc_bls_scan_ragged": (_I, [_VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I,
@@ -323,6 +328,52 @@ def htest_last_dispatch():
     ht, k, parts = C.c_int(0), C.c_int(0), C.c_int(0)
     check(lib().pdc_htest_last_dispatch(C.byref(ht), C.byref(k), C.byref(parts)))
     return ht.value, k.value, parts.value
+
+
+FDOT_OUTPUTS = ("plane", "m_plane", "ridge", "ridge_row", "ridge_m", "best")
+
+
+def htest_fdot_scan(t, w, f0, delta, nf, fdot, epoch, nharm=20, stat="h", parts=0, j_begin=0,
+                    want=("plane", "m_plane", "ridge", "ridge_row", "ridge_m", "best"), device=None):
+    """H (``stat="h"``) or Z^2 at ``nharm`` (``"z2"``) of an event list over the grid of frequencies times the rows
+    ``fdot``, phase ``f tau + fdot tau**2 / 2`` with ``tau = t - epoch`` (``pdc_htest_fdot_scan``).  Returns a dict
+    with what ``want`` names (None for the rest): ``plane`` / ``m_plane`` ``[nfd][nf]``, ``ridge`` / ``ridge_row`` /
+    ``ridge_m`` ``[nf]`` (per frequency the best row), ``best`` = ``(value, bin, row, m)``.  Z^2 has no ``m``."""
+    t, fdot = _f64(t, "t"), _f64(fdot, "fdot")
+    w = None if w is None else _f64(w, "w")
+    if w is not None and w.size != t.size:
+        raise ValueError("Input arrays have incompatible lengths.")
+    if stat not in ("h", "z2"):
+        raise ValueError("stat must be 'h' or 'z2'")
+    unknown = set(want) - set(FDOT_OUTPUTS)
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    want = set(want) - ({"m_plane", "ridge_m"} if stat == "z2" else set())
+    nfd = fdot.size
+    shapes = {"plane": ((nfd, nf), np.float64), "m_plane": ((nfd, nf), np.int32), "ridge": (nf, np.float64),
+              "ridge_row": (nf, np.int32), "ridge_m": (nf, np.int32)}
+    out = {name: np.empty(*shapes[name]) if name in want else None for name in shapes}
+    best = np.full(1, np.nan) if "best" in want else None
+    best_at = np.full(3, -1, dtype=np.int64) if "best" in want else None
+    dev = default_device() if device is None else device
+    check(lib().pdc_htest_fdot_scan(_ptr(t), _ptr(w), t.size, f0, delta, j_begin, nf, _ptr(fdot), nfd, float(epoch),
+                                    int(nharm), 0 if stat == "h" else 1, int(parts), _ptr(out["plane"]),
+                                    _ptr(out["m_plane"]), _ptr(out["ridge"]), _ptr(out["ridge_row"]), _ptr(out["ridge_m"]),
+                                    _ptr(best), _ptr(best_at), dev))
+    out["best"] = None if best is None else (float(best[0]), int(best_at[0]), int(best_at[1]), int(best_at[2]))
+    return out
+
+
+def htest_fdot_last_dispatch():
+    """``(ht, k, parts, rows_per_launch, launches)`` of this thread's last plane scan."""
+    ht, k, parts, rows, launches = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+    check(lib().pdc_htest_fdot_last_dispatch(C.byref(ht), C.byref(k), C.byref(parts), C.byref(rows), C.byref(launches)))
+    return ht.value, k.value, parts.value, rows.value, launches.value
+
+
+def htest_fdot_work_bytes(n, nf, nfd, nharm=20, parts=0, want_plane=True):
+    """Workspace bytes of a plane scan under the current ``PDC_WORK_BUDGET_GB`` (-1: sizes out of range); no GPU needed."""
+    return int(lib().pdc_htest_fdot_work_bytes(int(n), int(nf), int(nfd), int(nharm), int(parts), int(bool(want_plane))))
 
 
 def bls_scan(t, y, dy, periods, n_bins, len_min, len_max, min_points=5, dips_only=False, slices=0, device=None):

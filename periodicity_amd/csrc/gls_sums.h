@@ -100,6 +100,45 @@ __device__ __forceinline__ void fill_rotation_tables(double2 *row, bool odd, dou
     }
 }
 
+// fill_rotation_tables with the tile's base phase moved by `offset` cycles (any finite value: sincos_cycles reduces it):
+// base = frac(f_tile t') + offset, added before the one sincos.  offset = 0 gives the bits of fill_rotation_tables.
+// For phases that are not linear in the frequency alone, such as the spin-down term of htest_fdot.hip.
+// A copy, because fill_rotation_tables itself has to stay as it is for the units whose assembly is pinned: a change to
+// either must be made to both.  What holds them together is the test that a row with fdot = 0 has the bits of the plain
+// H-test scan (tests/test_htest_fdot_gpu.py::test_sample_parts).
+template <int COLS>
+__device__ __forceinline__ void fill_rotation_tables_at(double2 *row, bool odd, double tp, double kdelta, double f_tile,
+                                                        double scale, double offset) {
+    double2 step1, cur = make_double2(0.0, 0.0);
+    if (!odd) {
+        sincos_cycles(frac_product(kdelta, tp), step1.x, step1.y);
+        row[COLS * 8] = make_double2(0.0, 1.0);
+        row[COLS * 8 + 1] = step1;
+        cur = step1;
+#pragma unroll
+        for (int q = 2; q < 8; ++q) {
+            cur = rot2(cur, step1);
+            row[COLS * 8 + q] = cur;
+        }
+        sincos_cycles(frac_product(f_tile, tp) + offset, cur.x, cur.y);
+        cur.x *= scale;
+        cur.y *= scale;
+    } else {
+        sincos_cycles(frac_product(8.0 * kdelta, tp), step1.x, step1.y);
+    }
+    double2 b0;
+    b0.x = __shfl_xor(cur.x, 1, 64);
+    b0.y = __shfl_xor(cur.y, 1, 64);
+    if (odd) {
+        row[0] = b0;
+#pragma unroll
+        for (int q = 1; q < COLS * 8; ++q) {
+            b0 = rot2(b0, step1);
+            row[q] = b0;
+        }
+    }
+}
+
 // ---- the two-set scalar pipeline ---------------------------------------------------------------------------------------
 // Everything sample i + 1 needs is requested while sample i is accumulated; two samples per trip with two register
 // sets (A, B) that swap roles, so the read-ahead costs no register copies.  The record fields are wave-uniform: they

@@ -7,7 +7,7 @@
 //
 // The reference (periodicity.spectral) has no such class: PARITY UNPINNED BY THE REFERENCE.
 //
-// Decomposition
+// Decomposition (records, prep kernel, epilogue, ladder and sizes are in htest_common.h, shared with htest_fdot.hip)
 //   htest_prep_kernel    one workgroup: sum w^2 (block_sum, fixed order) and one 48-byte record per event
 //                        {w, w, cos(2 pi delta t'), sin(2 pi delta t'), 2 cos(2 pi delta t'), t' = t - t0}, plus the
 //                        two spare records the pipeline reads ahead.
@@ -36,30 +36,9 @@
 // a part pays one write of 2 nharm K BLOCK sums and its share of the finish kernel, about what a sixteenth of a chunk
 // costs.  Under PDC_WORK_BUDGET_GB the records and the partial sums together stay within the budget: fewer parts (the
 // explicit count too), never an error.  An explicit count above 65535 (the launch grid's second dimension) is 65535.
-#include "pdc_internal.h"
-#include "gls_sums.h"
-
-#include <cmath>
-
-using namespace pdc;
+#include "htest_common.h"
 
 namespace {
-
-constexpr int kPrepBlock = 1024;
-constexpr int kFinishBlock = 256;
-constexpr int kChunk = 64;      // events per rotation-table chunk
-constexpr int kMaxHarm = 20;
-constexpr int kTile = 1024;     // frequencies per tile, every instantiation
-constexpr int kMinChunks = 8;   // chunks a part keeps under the automatic rule
-constexpr int kMaxParts = 65535;
-
-struct HtPrepArgs {
-    const double *t, *w;
-    int64_t n;
-    double delta;
-    double *rec;    // [n + 2][6]
-    double *scal;   // {sum w^2}
-};
 
 struct HtArgs {
     const double *rec, *scal;
@@ -72,51 +51,6 @@ struct HtArgs {
     int32_t *m;
     double *z2;
 };
-
-__global__ __launch_bounds__(kPrepBlock) void htest_prep_kernel(HtPrepArgs a) {
-    __shared__ double red[kPrepBlock / 64];
-    const int tid = threadIdx.x;
-    const double t0 = a.t[0];
-    double w2 = 0.0;
-    for (int64_t i = tid; i < a.n + 2; i += kPrepBlock) {
-        if (i >= a.n) {   // the read-ahead records: finite, never accumulated
-            double2 *r = reinterpret_cast<double2 *>(a.rec + i * 6);
-            r[0] = r[1] = r[2] = make_double2(0.0, 0.0);
-            continue;
-        }
-        const double w = a.w ? a.w[i] : 1.0;
-        w2 += w * w;
-        put_record(a.rec + i * 6, w, w, a.delta, a.t[i] - t0);
-    }
-    w2 = block_sum<kPrepBlock>(w2, red);
-    if (tid == 0) a.scal[0] = w2;
-}
-
-// ---- epilogue, shared by the fused and the finish path ---------------------------------------------------------------
-// cs(k) = {C, S} of harmonic k + 1.  Cumulative Z^2_m in ascending m; H keeps the first maximum as np.argmax does (a NaN
-// candidate wins over finite ones, the first NaN stays).  Each output is written only where asked for.
-template <int HT, class Sums>
-__device__ __forceinline__ void htest_epilogue(int nharm, double scale, Sums cs, int64_t j, double *h_out, int32_t *m_out,
-                                               double *z2_out) {
-    double cum = 0.0, z = 0.0, best = 0.0;
-    int best_m = 1;
-#pragma unroll
-    for (int k = 1; k <= HT; ++k) {
-        if (k <= nharm) {
-            const double2 v = cs(k - 1);
-            cum += v.x * v.x + v.y * v.y;
-            z = scale * cum;
-            const double cand = z - (double)(4 * k - 4);
-            if (k == 1 || cand > best || (cand != cand && best == best)) {
-                best = cand;
-                best_m = k;
-            }
-        }
-    }
-    if (h_out) h_out[j] = best;
-    if (m_out) m_out[j] = best_m;
-    if (z2_out) z2_out[j] = z;
-}
 
 // ---- the scan --------------------------------------------------------------------------------------------------------
 // blockIdx.x = tile, blockIdx.y = part.  Dynamic LDS: the table of BLOCK = 512 is 76 KB.
@@ -171,23 +105,9 @@ __global__ __launch_bounds__(BLOCK) void htest_scan_kernel(HtArgs a) {
             0, cnt, [&](const int i) { return fetch_sample(tab, rec, i, slot_a, slot_b); },
             [&](const Ahead &h) {
                 const double w = h.r[1];
-                walk_grid<K>(rot2(h.qa, h.qt), h.r[2], h.r[3], h.cd2, [&](const int k, const double s, const double c) {
-                    // harmonics of this (event, frequency): Chebyshev recurrence on the unscaled (sin, cos)
-                    const double c2 = c + c;
-                    double sm = s, cm = c, sl = 0.0, cl = 1.0;   // harmonic m and m - 1
-#pragma unroll
-                    for (int m = 1; m <= HT; ++m) {
-                        Ck[m - 1][k] = __builtin_fma(w, cm, Ck[m - 1][k]);
-                        Sk[m - 1][k] = __builtin_fma(w, sm, Sk[m - 1][k]);
-                        if (m < HT) {
-                            const double cn = __builtin_fma(c2, cm, -cl), sn = __builtin_fma(c2, sm, -sl);
-                            cl = cm;
-                            sl = sm;
-                            cm = cn;
-                            sm = sn;
-                        }
-                    }
-                });
+                // harmonics of this (event, frequency): Chebyshev recurrence on the unscaled (sin, cos)
+                walk_grid<K>(rot2(h.qa, h.qt), h.r[2], h.r[3], h.cd2,
+                             [&](const int k, const double s, const double c) { add_harmonics<HT, K>(Ck, Sk, k, w, s, c); });
             });
     }
 
@@ -238,34 +158,15 @@ __global__ __launch_bounds__(kFinishBlock) void htest_finish_kernel(HtArgs a, in
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-struct Rung {
-    int ht, k, block;
-};
-constexpr Rung kLadder[] = {{2, 4, 256}, {4, 4, 256}, {8, 4, 256}, {12, 4, 256}, {16, 2, 512}, {20, 2, 512}};
-
-const Rung *rung_of(int nharm) {
-    if (nharm < 1 || nharm > kMaxHarm) return nullptr;
-    for (const Rung &r : kLadder)
-        if (r.ht >= nharm) return &r;
-    return nullptr;
-}
-
 struct HtDispatch {
     int ht, k, parts;
 };
 thread_local HtDispatch g_last = {};
 
-int64_t rec_bytes(int64_t n) { return up256((n + 2) * 48) + 256; }
-int64_t partial_bytes(int64_t nf, int ht, int parts) { return parts > 1 ? (int64_t)parts * 2 * ht * nf * 8 : 0; }
-
 // The parts a call runs: the automatic rule for asked == 0, then the launch limit and the budget.
 int parts_of(int asked, int64_t n, int64_t nf, int ht, int cus) {
     int64_t parts = asked;
-    if (asked == 0) {
-        const int64_t tiles = (nf + kTile - 1) / kTile, chunks = (n + kChunk - 1) / kChunk;
-        const int64_t want = (2 * (int64_t)cus + tiles - 1) / tiles, keep = chunks / kMinChunks;
-        parts = want < keep ? want : keep;
-    }
+    if (asked == 0) parts = auto_parts(n, (nf + kTile - 1) / kTile, cus);
     if (parts > kMaxParts) parts = kMaxParts;
     const int64_t budget = work_budget();
     if (budget > 0 && parts > 1 && rec_bytes(n) + partial_bytes(nf, ht, (int)parts) > budget)
@@ -273,20 +174,9 @@ int parts_of(int asked, int64_t n, int64_t nf, int ht, int cus) {
     return parts < 2 ? 1 : (int)parts;
 }
 
-int ht_validate(int64_t n, double delta, int64_t j_begin, int64_t nf, int nharm, int parts, bool any_output) {
-    PDC_REQUIRE(n >= 1, "htest: at least one event is needed (got %lld)", (long long)n);
-    PDC_REQUIRE(nf >= 0 && j_begin >= 0, "htest: negative size");
-    PDC_REQUIRE(nharm >= 1 && nharm <= kMaxHarm, "htest: nharm must be 1 .. %d (got %d)", kMaxHarm, nharm);
-    PDC_REQUIRE(parts >= 0, "htest: parts must be >= 0 (got %d)", parts);
-    PDC_REQUIRE(std::isfinite(delta) && delta > 0.0, "htest: the grid step must be finite and positive");
-    PDC_REQUIRE(any_output, "htest: every output is NULL");
-    PDC_REQUIRE((nf + kTile - 1) / kTile < ((int64_t)1 << 31), "htest: grid too large");
-    return PDC_OK;
-}
-
 template <int HT, int K, int BLOCK>
 int launch_scan(hipStream_t st, const HtArgs &a) {
-    const int lds = (kChunk + 1) * (BLOCK / 64 * 8 + 8 + 1) * (int)sizeof(double2);
+    const int lds = scan_lds_bytes(BLOCK);
     PDC_TRY(allow_dynamic_lds((const void *)htest_scan_kernel<HT, K, BLOCK>, lds));
     const dim3 grid((unsigned)((a.nf + kTile - 1) / kTile), (unsigned)a.parts);
     hipLaunchKernelGGL((htest_scan_kernel<HT, K, BLOCK>), grid, dim3(BLOCK), lds, st, a);
@@ -297,14 +187,7 @@ int launch_scan(hipStream_t st, const HtArgs &a) {
 int ht_enqueue(hipStream_t st, const double *d_t, const double *d_w, int64_t n, double f0, double delta, int64_t j_begin,
                int64_t nf, int nharm, const Rung &rung, int parts, double *d_h, int32_t *d_m, double *d_z2, void *work) {
     HtPrepArgs p;
-    p.t = d_t;
-    p.w = d_w;
-    p.n = n;
-    p.delta = delta;
-    p.rec = static_cast<double *>(work);
-    p.scal = reinterpret_cast<double *>(static_cast<char *>(work) + up256((n + 2) * 48));
-    hipLaunchKernelGGL(htest_prep_kernel, dim3(1), dim3(kPrepBlock), 0, st, p);
-    PDC_HIP(hipGetLastError());
+    PDC_TRY(ht_enqueue_prep(st, d_t, d_w, n, delta, work, p));
     HtArgs a;
     a.rec = p.rec;
     a.scal = p.scal;

@@ -12,6 +12,7 @@ docstring defines (``spectral.py:13-15``), evaluated by the HIP kernel in
 ``csrc/gls.hip``.  The frequency grid, weights and epilogue follow the reference line by line.
 Nothing in this module computes a periodogram on the CPU.
 """
+import collections as _collections
 import copy as _copy
 
 import numpy as np
@@ -19,7 +20,7 @@ import numpy as np
 from . import _cabi
 from .core import FSeries, TSeries, _batch_errs, _batch_offsets, _batch_request, _batch_slots
 
-__all__ = ["GLS", "LombScargle", "BGLST", "MultiHarmonicGLS", "HTest", "ZTest", "GLSBatch", "PeakTable"]
+__all__ = ["GLS", "LombScargle", "BGLST", "MultiHarmonicGLS", "HTest", "ZTest", "SpinSearch", "GLSBatch", "PeakTable"]
 
 
 def _as_tseries(signal):
@@ -476,8 +477,37 @@ class MultiHarmonicGLS(GLS):
         raise NotImplementedError("MultiHarmonicGLS.batch is not implemented: the ragged-grid batch computes GLS power only")
 
 
+BestCell = _collections.namedtuple("BestCell", "frequency fdot value harmonics index fdot_index")
+
+
+class SpinSearch(object):
+    """What ``HTest.search`` / ``ZTest.search`` return: the statistic over frequency x spin-down, reduced on the device.
+
+    ``.frequency`` ``[nf]``, ``.fdot`` ``[nfd]``, ``.epoch``; ``.plane`` ``[nfd][nf]`` and ``.harmonics`` (the plane of
+    m, ``HTest`` only), both None without ``want_plane``; ``.ridge`` (``FSeries``: per frequency the largest value over
+    the rows, as ``np.nanargmax(plane, axis=0)`` picks it), ``.ridge_fdot`` (its fdot; NaN where no row is finite),
+    ``.ridge_index`` (its row, -1 there), ``.ridge_harmonics`` (``HTest`` only); ``.best``, the largest cell as a
+    ``BestCell(frequency, fdot, value, harmonics, index, fdot_index)`` - NaN and -1 where nothing is finite.
+    """
+
+    def __init__(self, frequency, fdot, epoch, out, nharm):
+        self.frequency = frequency
+        self.fdot = fdot
+        self.epoch = epoch
+        self.plane = out["plane"]
+        self.harmonics = out["m_plane"]
+        self.ridge = FSeries(frequency, out["ridge"])
+        self.ridge_index = out["ridge_row"]
+        self.ridge_fdot = np.where(self.ridge_index >= 0, fdot[np.maximum(self.ridge_index, 0)], np.nan)
+        self.ridge_harmonics = out["ridge_m"]
+        value, j, row, m = out["best"]
+        found = j >= 0
+        self.best = BestCell(float(frequency[j]) if found else np.nan, float(fdot[row]) if found else np.nan, value,
+                             (m if nharm is None else nharm) if found else -1, j, row)
+
+
 class _EventScan(object):
-    """What ``HTest`` and ``ZTest`` share: the event list, its grid (the rule of ``GLS``) and the one library call."""
+    """What ``HTest`` and ``ZTest`` share: the event list, its grid (the rule of ``GLS``) and the library calls."""
 
     MAX_HARMONICS = 20
 
@@ -492,6 +522,16 @@ class _EventScan(object):
 
     def _scan(self, signal, weights, want):
         """Sorts the events (weights follow), builds the grid, calls the library; ``(h, m, z2)`` as ``want`` asks."""
+        t, w, events, (f0, delta, nf) = self._prepare(signal, weights)
+        out = _cabi.htest_scan(t, w, f0, delta, nf, nharm=self._nharm, want=want,
+                               device=_cabi.pick_device(self.device, None))
+        self.signal = events
+        self.weights = w
+        return out
+
+    def _prepare(self, signal, weights):
+        """The sorted events and their weights as arrays, the events as a ``TSeries``, ``(f0, delta, nf)`` of the grid
+        (``self.frequency``)."""
         if isinstance(signal, TSeries) or (hasattr(signal, "time") and hasattr(signal, "values")):
             t = np.asarray(signal.time, dtype=float)
         else:
@@ -513,11 +553,35 @@ class _EventScan(object):
         f0, delta, nf = _cabi.grid_params(self.frequency)
         if nf < 2:   # a grid of one bin has no step of its own; any positive step rebuilds it
             delta = 1.0
-        out = _cabi.htest_scan(t, w, f0, delta, nf, nharm=self._nharm, want=want,
-                               device=_cabi.pick_device(self.device, None))
+        return t, w, events, (f0, delta, nf)
+
+    def search(self, signal, weights=None, *, fdot, epoch=None, want_plane=True):
+        """The statistic over the plane of trial frequencies (the grid of a plain call) and spin-down rates ``fdot``,
+        with the phase ``f tau + fdot tau**2 / 2`` cycles, ``tau = t - epoch``: for a source whose frequency drifts
+        during the observation.  The plane is reduced on the device; a ``SpinSearch`` comes back.
+
+        fdot: one-dimensional array of finite values, any order (a row each).
+        epoch: where ``f`` is the frequency; None: the earliest event.
+        want_plane: False leaves the plane (and its harmonics) on the device: ridge and best cell only.
+        """
+        fdot = np.array(fdot, dtype=float)
+        if fdot.ndim != 1 or fdot.size < 1:
+            raise ValueError("fdot must be a one-dimensional array with at least one entry.")
+        if not np.all(np.isfinite(fdot)):
+            raise ValueError("fdot must be finite.")
+        t, w, events, (f0, delta, nf) = self._prepare(signal, weights)
+        epoch = float(t[0]) if epoch is None else float(epoch)
+        if not np.isfinite(epoch):
+            raise ValueError("epoch must be finite.")
+        with_m = self._stat == "h"
+        want = ["ridge", "ridge_row", "best"] + (["ridge_m"] if with_m else [])
+        if want_plane:
+            want += ["plane"] + (["m_plane"] if with_m else [])
+        out = _cabi.htest_fdot_scan(t, w, f0, delta, nf, fdot, epoch, nharm=self._nharm, stat=self._stat, want=want,
+                                    device=_cabi.pick_device(self.device, None))
         self.signal = events
         self.weights = w
-        return out
+        return SpinSearch(self.frequency, fdot, epoch, out, None if with_m else self._nharm)
 
     def _grid(self, events):
         """The grid of ``GLS._grid`` with the events as time stamps."""
@@ -559,11 +623,13 @@ class HTest(_EventScan):
     device: int, keyword-only, optional
 
     After a call: ``.frequency``, ``.periodogram`` (H), ``.harmonics`` (int array), ``.z2`` (``FSeries`` of Z2 at
-    ``max_harmonics``), ``.signal`` (the sorted events) and ``.weights``.
+    ``max_harmonics``), ``.signal`` (the sorted events) and ``.weights``.  ``.search(signal, weights, fdot=...)`` covers
+    the frequency - spin-down plane (``csrc/htest_fdot.hip``) and returns a ``SpinSearch``.
     """
 
     def __init__(self, fmin=None, fmax=None, n=5, *, max_harmonics=20, device=None):
         super().__init__(fmin, fmax, n, max_harmonics, "max_harmonics", device)
+        self._stat = "h"
         self.max_harmonics = self._nharm
 
     def __call__(self, signal, weights=None):
@@ -591,11 +657,13 @@ class ZTest(_EventScan):
         Harmonics summed, 1 .. 20 (default 2).
     device: int, keyword-only, optional
 
-    After a call: ``.frequency``, ``.periodogram``, ``.signal`` (the sorted events) and ``.weights``.
+    After a call: ``.frequency``, ``.periodogram``, ``.signal`` (the sorted events) and ``.weights``.  ``.search`` as for
+    ``HTest``, with Z2 as the value of a cell.
     """
 
     def __init__(self, fmin=None, fmax=None, n=5, *, nharm=2, device=None):
         super().__init__(fmin, fmax, n, nharm, "nharm", device)
+        self._stat = "z2"
         self.nharm = self._nharm
 
     def __call__(self, signal, weights=None):
