@@ -219,6 +219,32 @@ int pdc_mhgls_scan_dev(int device, void *stream, const double *d_t, const double
                        double f0, double delta, int64_t j_begin, int64_t nf, int nterms, int fit_mean, int psd,
                        double *d_power);
 
+/* ---- shared-phase multiband generalised Lomb-Scargle (VanderPlas & Ivezic 2015, ApJ 812, 18: Nbase = nterms, Nband = 0) ----
+ * The reference has no such class - PARITY UNPINNED BY THE REFERENCE.  One light curve whose samples carry a band label
+ * band[i] in 0 .. n_bands - 1 (n_bands 1 .. 32; filters, instruments): per trial frequency the weighted least-squares fit
+ * of ONE Fourier series of `nterms` (1 .. 3) harmonics common to all bands plus, with fit_mean, one floating offset PER
+ * BAND.  w_i = dy_i^-2 / sum dy^-2 over all samples, theta_i = 2 pi f (t_i - t_min), grid rule as pdc_gls_scan; y is
+ * centred per band on the band's weighted mean (for conditioning: the offsets still float).  With the design
+ * 1[band_i = b] (b < n_bands), cos(h theta), sin(h theta) (h = 1 .. nterms), M = Phi^T diag(w) Phi, b = Phi^T diag(w) yc,
+ * YY = sum w yc^2:
+ *     power_out[j] = b^T M^-1 b / YY        (psd: b^T M^-1 b * 0.5 * sum dy^-2),
+ * with one band the value of pdc_mhgls_scan.  Without fit_mean there are no offsets and no centring, the labels do not
+ * enter, and the value is that of pdc_mhgls_scan with fit_mean = 0 on the merged curve.  A bin whose reduced normal
+ * matrix is not positive definite to rounding (a Cholesky pivot that is not > 0 or not finite) is NaN.
+ * Checked before any device is looked for: NULL arguments (band too), negative sizes, nterms, n_bands, delta finite and
+ * > 0, n >= n_bands + 2 nterms + 1 (2 nterms + 1 without fit_mean), and in the host form every label in range and every
+ * band with at least one sample.  The `_dev` form cannot look at the labels: they are its caller's precondition, a label
+ * out of range never indexes memory and makes EVERY bin NaN, a band without samples is skipped.  No atomics: the same
+ * bits from call to call.  The `_dev` form enqueues on `stream` and keeps its own workspace per (device, stream). */
+int pdc_mbgls_scan(const double *t, const double *y, const double *dy, const int32_t *band, int64_t n, int n_bands,
+                   double f0, double delta, int64_t j_begin, int64_t nf, int nterms, int fit_mean, int psd,
+                   double *power_out, int device);
+int pdc_mbgls_scan_dev(int device, void *stream, const double *d_t, const double *d_y, const double *d_dy,
+                       const int32_t *d_band, int64_t n, int n_bands, double f0, double delta, int64_t j_begin, int64_t nf,
+                       int nterms, int fit_mean, int psd, double *d_power);
+/* Frequencies per tile of the kernel instance `nterms` runs; -1 when nterms is out of range.  No GPU needed. */
+int pdc_mbgls_tile_bins(int nterms);
+
 /* ---- Z^2_m and the H-test for event lists (Buccheri et al. 1983, A&A 128, 245; de Jager, Raubenheimer & Swanepoel 1989,
  * A&A 221, 180; photon weights as Kerr 2011, ApJ 732, 38) ------------------------------------------------------------------
  * The reference has no such class - PARITY UNPINNED BY THE REFERENCE.  Arrival times t[n] in ascending order, weights

@@ -48,6 +48,9 @@ PROTOTYPES = {
     "pdc_bglst_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _D, _D, _L, _L, _VP, _VP, _VP, _L]),
     "pdc_mhgls_scan": (_I, [_VP, _VP, _VP, _L, _D, _D, _L, _L, _I, _I, _I, _VP, _I]),
     "pdc_mhgls_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _D, _D, _L, _L, _I, _I, _I, _VP]),
+    "pdc_mbgls_scan": (_I, [_VP, _VP, _VP, _VP, _L, _I, _D, _D, _L, _L, _I, _I, _I, _VP, _I]),
+    "pdc_mbgls_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _L, _I, _D, _D, _L, _L, _I, _I, _I, _VP]),
+    "pdc_mbgls_tile_bins": (_I, [_I]),
     "pdc_htest_scan": (_I, [_VP, _VP, _L, _D, _D, _L, _L, _I, _I, _VP, _VP, _VP, _I]),
     "pdc_htest_scan_dev": (_I, [_I, _VP, _VP, _VP, _L, _D, _D, _L, _L, _I, _I, _VP, _VP, _VP]),
     "pdc_htest_tile_bins": (_L, [_I]),
@@ -295,6 +298,27 @@ def mhgls_scan(t, y, dy, f0, delta, nf, nterms=2, fit_mean=True, psd=False, j_be
     check(lib().pdc_mhgls_scan(_ptr(t), _ptr(y), _ptr(dy), t.size, f0, delta, j_begin, nf, int(nterms),
                                int(bool(fit_mean)), int(bool(psd)), _ptr(out), dev))
     return out
+
+
+def mbgls_scan(t, y, dy, band, n_bands, f0, delta, nf, nterms=1, fit_mean=True, psd=False, j_begin=0, device=None):
+    """Shared-phase multiband GLS power per trial frequency (``pdc_mbgls_scan``): one Fourier series of ``nterms``
+    harmonics common to all bands and, with ``fit_mean``, one floating offset per band; ``band``: int labels in
+    ``0 .. n_bands - 1``, one per sample."""
+    t, y = _f64(t, "t"), _f64(y, "y")
+    dy = None if dy is None else _f64(dy, "dy")
+    band = np.ascontiguousarray(band, dtype=np.int32)
+    if y.size != t.size or (dy is not None and dy.size != t.size) or band.ndim != 1 or band.size != t.size:
+        raise ValueError("Input arrays have incompatible lengths.")
+    out = np.empty(nf, dtype=np.float64)
+    dev = default_device() if device is None else device
+    check(lib().pdc_mbgls_scan(_ptr(t), _ptr(y), _ptr(dy), _ptr(band), t.size, int(n_bands), f0, delta, j_begin, nf,
+                               int(nterms), int(bool(fit_mean)), int(bool(psd)), _ptr(out), dev))
+    return out
+
+
+def mbgls_tile_bins(nterms):
+    """Frequencies per tile of the kernel instance ``nterms`` runs (-1 when out of range); no GPU needed."""
+    return int(lib().pdc_mbgls_tile_bins(int(nterms)))
 
 
 def htest_scan(t, w, f0, delta, nf, nharm=20, parts=0, j_begin=0, want=("h", "m", "z2"), device=None):

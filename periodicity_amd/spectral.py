@@ -20,7 +20,7 @@ import numpy as np
 from . import _cabi
 from .core import FSeries, TSeries, _batch_errs, _batch_offsets, _batch_request, _batch_slots
 
-__all__ = ["GLS", "LombScargle", "BGLST", "MultiHarmonicGLS", "HTest", "ZTest", "SpinSearch", "GLSBatch", "PeakTable"]
+__all__ = ["GLS", "LombScargle", "BGLST", "MultiHarmonicGLS", "MultibandGLS", "HTest", "ZTest", "SpinSearch", "GLSBatch", "PeakTable"]
 
 
 def _as_tseries(signal):
@@ -475,6 +475,111 @@ class MultiHarmonicGLS(GLS):
 
     def batch(self, *args, **kwargs):
         raise NotImplementedError("MultiHarmonicGLS.batch is not implemented: the ragged-grid batch computes GLS power only")
+
+
+class MultibandGLS(GLS):
+    """Shared-phase multiband generalised Lomb-Scargle periodogram (VanderPlas & Ivezic 2015, ApJ 812, 18, the
+    ``Nbase = nterms, Nband = 0`` model; ``LombScargleMultiband`` elsewhere): ONE period from a light curve whose samples
+    come from several filters or instruments, each with its own mean.  At every trial frequency one truncated Fourier
+    series common to all bands plus one floating offset per band is fitted by weighted least squares.
+
+    The reference has no such class - **parity unpinned by the reference**.  Grid, weights (``err**-2`` normalised over
+    ALL samples) and the two normalisations are those of ``GLS`` on the merged curve.  With ``fit_mean`` every band is
+    centred on its own weighted mean (for conditioning; the offsets still float), the design has one indicator column
+    per band and ``cos(h theta), sin(h theta)`` for ``h = 1 .. nterms``, and
+
+        ``power(f) = b^T M^-1 b / YY``   (``psd``: ``b^T M^-1 b * 0.5 * sum err**-2``);
+
+    with one band that is ``MultiHarmonicGLS(nterms)``.  Without ``fit_mean`` there are no offsets and the bands do not
+    enter: ``MultiHarmonicGLS(nterms)(..., fit_mean=False)`` on the merged curve.  A bin whose Cholesky pivot is not
+    positive is NaN.  Evaluated by ``csrc/mbgls.hip``; nothing here computes a periodogram on the CPU.
+
+    Parameters
+    ----------
+    fmin, fmax, n, psd: as ``GLS``.
+    nterms: int, keyword-only, optional
+        Harmonics of the shared series, 1 .. 3 (default 1).
+    device: int, keyword-only, optional
+    """
+
+    MAX_TERMS = 3
+    MAX_BANDS = 32
+
+    def __init__(self, fmin=None, fmax=None, n=5, psd=False, *, nterms=1, device=None):
+        if isinstance(nterms, bool) or nterms != int(nterms) or not 1 <= int(nterms) <= self.MAX_TERMS:
+            raise ValueError(f"nterms must be an integer 1 .. {self.MAX_TERMS}")
+        super().__init__(fmin, fmax, n, psd, device=device)
+        self.nterms = int(nterms)
+
+    def __call__(self, signal, bands, err=None, fit_mean=True):
+        """``FSeries(frequency, power)`` on the grid of ``GLS``.  ``bands``: one label per sample (strings or integers),
+        aligned with the time-sorted samples of the ``TSeries`` as ``err`` is."""
+        signal = _as_tseries(signal)
+        labels, index = np.unique(np.asarray(bands), return_inverse=True)
+        index = np.ascontiguousarray(index.reshape(-1), dtype=np.int32)
+        if np.asarray(bands).ndim != 1 or index.size != len(signal):
+            raise ValueError("Input arrays have incompatible lengths.")
+        if labels.size > self.MAX_BANDS:
+            raise ValueError(f"at most {self.MAX_BANDS} bands (got {labels.size})")
+        self.frequency = self._grid(signal)
+        f0, delta, nf = _cabi.grid_params(self.frequency)
+        if nf < 2:   # a grid of one bin has no step of its own; any positive step rebuilds it
+            delta = 1.0
+        have_err = err is not None
+        if not have_err:
+            err = np.ones_like(signal.values)
+        dy = np.asarray(err, dtype=float) if have_err else None
+        t = np.asarray(signal.time, dtype=float)
+        y = np.asarray(signal.values, dtype=float)
+        dev = _cabi.pick_device(self.device, None)
+        power = _cabi.mbgls_scan(t, y, dy, index, labels.size, f0, delta, nf, self.nterms, fit_mean, self.psd, device=dev)
+        self.err = err
+        self.fit_mean = bool(fit_mean)
+        self.signal = signal
+        self.bands = labels
+        self.band_index = index
+        self.periodogram = FSeries(self.frequency, power)
+        return self.periodogram
+
+    def _harmonics(self, times, f0):
+        arg = 2 * np.pi * f0 * (np.asarray(times, dtype=float) - float(self.signal.time[0]))
+        return np.stack([f(h * arg) for h in range(1, self.nterms + 1) for f in (np.cos, np.sin)], axis=1)
+
+    def _fit(self, f0):
+        """``(offsets [n_bands], harmonic coefficients [2 nterms])`` of the last call's model at frequency ``f0``: a host
+        weighted least-squares fit, O(N)."""
+        sigma = np.asarray(self.err, dtype=float)
+        y = np.asarray(self.signal.values, dtype=float)
+        nb = self.bands.size if self.fit_mean else 0
+        onehot = (self.band_index[:, None] == np.arange(nb)[None, :]).astype(float)
+        A = np.hstack([onehot, self._harmonics(self.signal.time, f0)])
+        theta = np.linalg.lstsq(A / sigma[:, None], y / sigma, rcond=None)[0]
+        return (theta[:nb] if self.fit_mean else np.zeros(self.bands.size)), theta[nb:]
+
+    def model(self, tf, band, f0):
+        """The fitted series of the last call plus the offset of ``band`` (one of the labels) at frequency ``f0``,
+        evaluated at times ``tf``.  O(N) host arithmetic, not part of the scan."""
+        where = np.flatnonzero(self.bands == band)
+        if where.size != 1:
+            raise ValueError(f"{band!r} is not one of the bands {list(self.bands)}")
+        offsets, coef = self._fit(f0)
+        return TSeries(tf, offsets[where[0]] + self._harmonics(tf, f0) @ coef)
+
+    def band_offsets(self, f0):
+        """``{label: fitted offset}`` of the last call's model at frequency ``f0`` (zeros without ``fit_mean``)."""
+        offsets, _ = self._fit(f0)
+        return {label: float(o) for label, o in zip(self.bands.tolist(), offsets)}
+
+    def window(self):
+        raise NotImplementedError("MultibandGLS has no window: GLS.window calls the periodogram without band labels")
+
+    def bootstrap(self, *args, **kwargs):
+        raise NotImplementedError("MultibandGLS has no bootstrap: the batched replicate kernels compute GLS power only")
+
+    fap = fal = bootstrap
+
+    def batch(self, *args, **kwargs):
+        raise NotImplementedError("MultibandGLS.batch is not implemented: the ragged-grid batch computes GLS power only")
 
 
 BestCell = _collections.namedtuple("BestCell", "frequency fdot value harmonics index fdot_index")
