@@ -11,9 +11,9 @@ EPOCHS = ("first", "middle", "before")        # t[0], the midpoint of the list, 
 CYCLES = (0.0, 2.0, -4.5, 1.2e6)              # drift at the event farthest from the epoch; the last: the exact reduction
 
 
-def z2_fdot(t, w, freq, fdot, epoch, M, dtype=np.float64):
+def z2_fdot(t, w, freq, fdot, epoch, M, dtype=np.float64, chunk=ho.CHUNK):
     """Cumulative ``Z2_m`` for ``m = 1 .. M`` of one row ``fdot``, ``[M][F]``, as ``htest_oracle.z2`` with
-    ``theta = 2 pi (f tau + fdot tau**2 / 2)``, ``tau = t - epoch``; ``w`` None: unit weights."""
+    ``theta = 2 pi (f tau + fdot tau**2 / 2)``, ``tau = t - epoch``; ``w`` None: unit weights.  ``chunk`` frequencies at a time."""
     t = np.asarray(t, dtype=dtype)
     w = np.ones_like(t) if w is None else np.asarray(w, dtype=dtype)
     freq = np.asarray(freq, dtype=dtype)
@@ -22,14 +22,14 @@ def z2_fdot(t, w, freq, fdot, epoch, M, dtype=np.float64):
     two_pi = 2 * np.arccos(dtype(-1))
     scale = 2 / np.sum(w * w)
     out = np.empty((M, freq.size), dtype=dtype)
-    for lo in range(0, freq.size, ho.CHUNK):
-        theta = two_pi * (freq[lo:lo + ho.CHUNK, None] * tau[None, :] + drift[None, :])
+    for lo in range(0, freq.size, chunk):
+        theta = two_pi * (freq[lo:lo + chunk, None] * tau[None, :] + drift[None, :])
         cum = np.zeros(theta.shape[0], dtype=dtype)
         for k in range(1, M + 1):
             c = np.sum(w * np.cos(k * theta), axis=1)
             s = np.sum(w * np.sin(k * theta), axis=1)
             cum = cum + (c * c + s * s)
-            out[k - 1, lo:lo + ho.CHUNK] = scale * cum
+            out[k - 1, lo:lo + chunk] = scale * cum
     return out
 
 

@@ -6,7 +6,8 @@ Every ``cos(k theta)``, ``sin(k theta)`` is evaluated directly per (sample, freq
 product-to-sum rule - so the oracle shares no shortcut with the kernel it checks."""
 import numpy as np
 
-CHUNK = 256   # frequencies per block of the dense evaluation
+CHUNK = 256   # frequencies per block of the dense evaluation, unless the caller names another
+LONG_PERIOD = 0.0031   # days: the signal of ``long_curve``
 
 
 def curve(n, seed):
@@ -29,9 +30,21 @@ def _weights(y, err, fit_mean, dtype):
     return w, y, W
 
 
-def normal_equations(t, y, err, freq, nterms, fit_mean, dtype=np.float64):
+def long_curve(n=300, seed=31, span=3000.0, offset=2454900.5, period=LONG_PERIOD):
+    """A long-baseline curve: ``n`` samples over ``span`` days at a Julian-date ``offset``, a two-harmonic signal of
+    ``period`` days - about 1e6 cycles over the baseline.  Draws in the order t, err, noise."""
+    rng = np.random.default_rng(seed)
+    t = np.sort(rng.uniform(0, span, n)) + offset
+    err = rng.uniform(0.1, 0.3, n)
+    y = (1 + 0.7 * np.sin(2 * np.pi * (t - t[0]) / period) + 0.3 * np.sin(4 * np.pi * (t - t[0]) / period + 1)
+         + err * rng.standard_normal(n))
+    return t, y, err
+
+
+def normal_equations(t, y, err, freq, nterms, fit_mean, dtype=np.float64, chunk=CHUNK):
     """``M [F, D, D]``, ``b [F, D]``, ``YY`` and ``sum err**-2`` for the design ``1, cos th, sin th, ..., cos H th,
-    sin H th`` (no constant without ``fit_mean``), ``th = 2 pi f (t - t[0])``."""
+    sin H th`` (no constant without ``fit_mean``), ``th = 2 pi f (t - t[0])``; ``chunk`` frequencies at a time (the
+    block ``[chunk][D][N]`` is what the evaluation holds in memory)."""
     w, yc, W = _weights(y, err, fit_mean, dtype)
     t = np.asarray(t, dtype=dtype)
     freq = np.asarray(freq, dtype=dtype)
@@ -40,14 +53,14 @@ def normal_equations(t, y, err, freq, nterms, fit_mean, dtype=np.float64):
     D = 2 * nterms + (1 if fit_mean else 0)
     M = np.empty((freq.size, D, D), dtype=dtype)
     b = np.empty((freq.size, D), dtype=dtype)
-    for lo in range(0, freq.size, CHUNK):
-        theta = two_pi * freq[lo:lo + CHUNK, None] * tp[None, :]
+    for lo in range(0, freq.size, chunk):
+        theta = two_pi * freq[lo:lo + chunk, None] * tp[None, :]
         cols = [np.ones_like(theta)] if fit_mean else []
         for k in range(1, nterms + 1):
             cols += [np.cos(k * theta), np.sin(k * theta)]
         phi = np.stack(cols, axis=1)                       # [f, D, N]
-        M[lo:lo + CHUNK] = np.matmul(phi * w, np.swapaxes(phi, 1, 2))
-        b[lo:lo + CHUNK] = np.matmul(phi, w * yc)
+        M[lo:lo + chunk] = np.matmul(phi * w, np.swapaxes(phi, 1, 2))
+        b[lo:lo + chunk] = np.matmul(phi, w * yc)
     return M, b, np.dot(w, yc * yc), W
 
 
@@ -82,13 +95,13 @@ def cond_from(M):
     return out
 
 
-def power(t, y, err, freq, nterms, fit_mean=True, psd=False, dtype=np.longdouble):
+def power(t, y, err, freq, nterms, fit_mean=True, psd=False, dtype=np.longdouble, chunk=CHUNK):
     """Multi-harmonic GLS power on ``freq``, solved by Cholesky in ``dtype``."""
-    return power_from(*normal_equations(t, y, err, freq, nterms, fit_mean, dtype), psd=psd)
+    return power_from(*normal_equations(t, y, err, freq, nterms, fit_mean, dtype, chunk), psd=psd)
 
 
-def cond(t, y, err, freq, nterms, fit_mean=True):
-    return cond_from(normal_equations(t, y, err, freq, nterms, fit_mean, np.float64)[0])
+def cond(t, y, err, freq, nterms, fit_mean=True, chunk=CHUNK):
+    return cond_from(normal_equations(t, y, err, freq, nterms, fit_mean, np.float64, chunk)[0])
 
 
 COND_LIMIT = 1e6   # bins compared in value: cond <= COND_LIMIT (M is nearly singular at the lowest few frequencies)
