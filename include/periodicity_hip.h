@@ -398,12 +398,14 @@ int pdc_gls_scan_dev(int device, void *stream,
 /* TEST HOOK (not for callers): the route the CALLING THREAD's last direct-sum scan took inside the library (every entry
  * above, pdc_gls_bootstrap with method 0 and the plans' enqueueing thread end in the same dispatcher) and its launch
  * shape, recorded on the host just before the launches.  The record is per host thread, so concurrent scans on other
- * threads do not disturb it; all zeros before the thread's first scan.  out[12] = route (1 general, 2 general with
+ * threads do not disturb it; all zeros before the thread's first scan.  out[13] = route (1 general, 2 general with
  * sample parts, 3 balanced pieces, 4 shared time axis, 5 shared time axis with two frequencies per lane), K (frequencies
  * per thread; per lane on the shared routes), S (waves per frequency tile; 0 on the shared routes), frequency tiles,
  * final sample part count (1: not cut), 1 when the parts are dealt to the XCDs, workgroup slots of the balanced launch
  * (0: not balanced), 1 when the grid-wide prologue ran, curves per padded row of the shared weight table, its curve
- * groups, samples per part, 128-sample chunks per tile of the balanced launch. */
+ * groups, samples per part, 128-sample chunks per tile of the balanced launch, 1 when the odd column-waves of the
+ * mirrored-pair kernel took every sample's table halves in the opposite order (only with PDC_GLS_LEAD=1 in the
+ * environment; always 0 at S = 4 and where the pair kernel did not run). */
 int pdc_test_gls_last_dispatch(int64_t *out);
 /* TEST HOOK (not for callers): whether the CALLING THREAD's last direct-sum scan ran the mirrored-pair kernel (K = 16 in
  * the two GLS modes; PDC_GLS_PAIR=0 in the environment keeps the plain kernel), per host thread like the record above.

@@ -65,6 +65,10 @@ struct GlsArgs {
     double f0, delta;
     int64_t j_begin, nf;
     int psd;
+    // lead swap (pair instances with two or more column-waves per stream): the odd columns take every sample's table
+    // halves in the opposite order, see the scalar pipeline of the kernel.  (Here, in the padding after `psd`: the
+    // argument block of every instance keeps its size and offsets.)
+    int lead_swap = 0;
     double *power;     // [n_curves][nf] or nullptr
     double *raw_s;     // MODE_RAW outputs
     double *raw_c;
@@ -574,6 +578,17 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
             // and the 48 fmas of the first half | wait | request the next sample's first half, record and two LDS
             // entries | the 48 fmas of the second half.  (Reads one row past the stretch: the table carries two
             // spare rows, the LDS table one.)
+            // Lead swap (GlsArgs::lead_swap, COLS >= 2): the column-waves of a stream read the same rows in the same
+            // order, so each line comes from L2 once and both waves of a pair wait for it.  The accumulators of m < 4
+            // and m >= 4 are disjoint, so the order of a row's halves changes no bit of any sum: the odd columns take
+            // (m >= 4, then m < 4).  The half an even wave asks for one phase ahead is then, every other phase, the one
+            // its odd neighbour is working on (a scalar-cache hit), and the other way round: every wave leads on one
+            // half and follows on the other instead of sharing every miss.
+            // ONE loop serves both orders: the quarter where the half taken first begins (q0 = 0 or 2) is a scalar
+            // offset on the table pointers, set per chunk, and in a swapped wave the register slots of m < 4 hold the
+            // sums of m + 4 and the other way round, until they trade back right before the recombination.
+            // (Two copies of the loop behind a wave-uniform branch: the allocator gave some accumulators other
+            // registers in the second copy and moved them through scratch, 37 - 220 spilled VGPRs.)
             using d8 = double __attribute__((ext_vector_type(8)));
             using cd8 = __attribute__((address_space(4))) const d8;
             using d2 = double __attribute__((ext_vector_type(2)));
@@ -587,12 +602,21 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
             const cd8 *stab = reinterpret_cast<const cd8 *>(uniform(a.pair_tab + (off + base) * kPairRow));
             const cd2 *srec = reinterpret_cast<const cd2 *>(uniform(a.rec + (off + base) * 6));
             const int i_last = __builtin_amdgcn_readfirstlane(i_end);
-            d8 h0a, h0b, h1a, h1b;   // {c, s, c2, s2} of m = 0, 1 | 2, 3 | 4, 5 | 6, 7
-            d2 r;                    // {sqrt(w) y, sqrt(w)}
+            d8 fa, fb, ga, gb;   // {c, s, c2, s2} of two offsets each: the half taken first | second
+            d2 r;                // {sqrt(w) y, sqrt(w)}
             double2 qa, qt;
+#ifdef PDC_GLS_PROBE_ROW0
+            // TIMING PROBE (never defined by the Makefile; wrong results): every table load reads the chunk's row 0, so
+            // all of them hit the scalar cache - the headline time without any table latency
+            auto trow = [](const int) { return 0; };
+#else
+            auto trow = [](const int i) { return i * 4; };
+#endif
+            const int q0 = COLS >= 2 ? (a.lead_swap & col & 1) * 2 : 0;   // (wave-uniform: `col` came through readfirstlane)
+            const cd8 *stab_f = stab + q0, *stab_g = stab + (2 - q0);
             auto request_first = [&](const int i) {
-                h0a = stab[i * 4];
-                h0b = stab[i * 4 + 1];
+                fa = stab_f[trow(i)];
+                fb = stab_f[trow(i) + 1];
                 r = srec[i * 3];
                 qa = tab[i][slot_a];
                 qt = tab[i][slot_b];
@@ -623,8 +647,8 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
                 request_first(i_beg);
                 for (int i = i_beg; i < i_last; ++i) {
                     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the first half, the record and the seed entries
-                    h1a = stab[i * 4 + 2];
-                    h1b = stab[i * 4 + 3];
+                    ga = stab_g[trow(i)];
+                    gb = stab_g[trow(i) + 1];
                     __builtin_amdgcn_sched_barrier(0);
                     const double2 seed = rot2(qa, qt);
                     A1 = r[0] * seed.x;
@@ -633,14 +657,14 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
                     B2 = r[1] * seed.y;
                     a2 = seed.x * seed.x;
                     ab = seed.x * seed.y;
-                    pair_fmas(h0a, 0);
-                    pair_fmas(h0b, 2);
+                    pair_fmas(fa, 0);
+                    pair_fmas(fb, 2);
                     __builtin_amdgcn_sched_barrier(0);
                     __builtin_amdgcn_s_waitcnt(0xc07f);  // the second half
                     request_first(i + 1);
                     __builtin_amdgcn_sched_barrier(0);
-                    pair_fmas(h1a, 4);
-                    pair_fmas(h1b, 6);
+                    pair_fmas(ga, 4);
+                    pair_fmas(gb, 6);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -715,6 +739,28 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
         // the twelve sums of offset m -> the six sums of its two frequencies; the sample-only remainders enter once per
         // tile piece, in the waves whose sums survive the SPLIT fold
         __syncthreads();   // gf_acc is complete
+        // lead swap: the slots of offsets m and m + 4 trade back (a wave-uniform branch, once per tile piece)
+        if (COLS >= 2 && (a.lead_swap & col & 1)) {
+#pragma unroll
+            for (int m = 0; m < K / 4; ++m) {
+                const int hi = K / 2 + m, lo = K / 2 - 1 - m, hi4 = hi + K / 4, lo4 = lo - K / 4;
+                auto trade = [](double &x, double &y) { const double t = x; x = y; y = t; };
+                trade(Sh[hi], Sh[hi4]);
+                trade(Sh[lo], Sh[lo4]);
+                trade(Ch[hi], Ch[hi4]);
+                trade(Ch[lo], Ch[lo4]);
+                if (mode_sums_w(MODE)) {
+                    trade(S[hi], S[hi4]);
+                    trade(S[lo], S[lo4]);
+                    trade(C[hi], C[hi4]);
+                    trade(C[lo], C[lo4]);
+                }
+                trade(SS[hi], SS[hi4]);
+                trade(SS[lo], SS[lo4]);
+                trade(SC[hi], SC[hi4]);
+                trade(SC[lo], SC[lo4]);
+            }
+        }
         const bool keeps = part == 0;
 #pragma unroll
         for (int m = 0; m < K / 2; ++m) {
@@ -1385,7 +1431,7 @@ struct WorkLayout {
 // scan meanwhile.
 enum Route { ROUTE_NONE = 0, ROUTE_GENERAL = 1, ROUTE_PARTS = 2, ROUTE_BALANCED = 3, ROUTE_SHARED = 4, ROUTE_SHARED2 = 5 };
 struct Dispatch {
-    int64_t route, K, S, tiles, parts, parts_by_xcd, bal_slots, wide_prep, bpad, groups, z_len, bal_chunks;
+    int64_t route, K, S, tiles, parts, parts_by_xcd, bal_slots, wide_prep, bpad, groups, z_len, bal_chunks, lead_swap;
 };
 thread_local Dispatch g_last_dispatch = {};
 // TEST HOOK (pdc_test_gls_last_pair): whether that scan ran the mirrored-pair kernel, and the bytes of its offset table
@@ -1576,6 +1622,14 @@ int scan_dev(int device, hipStream_t st, const double *d_t, const double *d_y, c
                            (const double *)p.rec, tab, n_total, delta);
         PDC_HIP(hipGetLastError());
         a.pair_tab = tab;
+        // Lead swap: the odd column-waves of the pair kernel take the table halves in the opposite order (S = 4 has
+        // one column per stream: nothing to swap).  OFF unless PDC_GLS_LEAD=1 (read once per process; 0 states the
+        // default): the same bits either way, and on the headline the swap measured 0.1 - 0.3 % against the one
+        // order, inside the run-to-run spread, where 3 % was asked of it to become the default
+        // (profiles/r15_lead_ab.txt).
+        static const int env_lead = [] { const char *e = getenv("PDC_GLS_LEAD"); return e ? atoi(e) : 0; }();
+        a.lead_swap = (env_lead == 1 && S <= 2) ? 1 : 0;
+        rec.lead_swap = a.lead_swap;
         g_last_pair.ran = 1;
         g_last_pair.table_bytes = (n_total + 2) * kPairRow * 8;
     }
@@ -1681,9 +1735,9 @@ extern "C" {
 int pdc_test_gls_last_dispatch(int64_t *out) {
     PDC_REQUIRE(out, "pdc_test_gls_last_dispatch: NULL argument");
     const Dispatch &d = g_last_dispatch;
-    const int64_t v[12] = {d.route, d.K, d.S, d.tiles, d.parts, d.parts_by_xcd, d.bal_slots, d.wide_prep,
-                           d.bpad, d.groups, d.z_len, d.bal_chunks};
-    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    const int64_t v[13] = {d.route, d.K, d.S, d.tiles, d.parts, d.parts_by_xcd, d.bal_slots, d.wide_prep,
+                           d.bpad, d.groups, d.z_len, d.bal_chunks, d.lead_swap};
+    for (int i = 0; i < 13; ++i) out[i] = v[i];
     return PDC_OK;
 }
 
