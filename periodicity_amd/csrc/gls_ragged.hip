@@ -144,35 +144,25 @@ __global__ __launch_bounds__(kRBlock) void gls_ragged_scan_kernel(RaggedArgs a) 
     for (int k = 0; k < kRK; ++k) Sh[k] = Ch[k] = S[k] = C[k] = SS[k] = SC[k] = 0.0;
 
     const int slot_a = col * 8 + (lane >> 3), slot_b = kRCols * 8 + (lane & 7);
-    for (int64_t base = 0; base < n; base += kRChunk) {
-        __syncthreads();  // everyone is done with the previous chunk's tables
-        {   // rotation tables, two threads per sample: the whole block
-            const int il = tid >> 1;
-            const bool live = base + il < n;   // (rows past the end are never accumulated; they need finite input)
-            const double tp = live ? a.rec[(off + base + il) * 6 + 5] : 0.0;
-            const double sqw = live ? a.rec[(off + base + il) * 6 + 1] : 0.0;
-            fill_rotation_tables<kRCols>(tab[il], tid & 1, tp, kdelta, f_tile, sqw);
-        }
-        __syncthreads();
-        const int cnt = (int)((n - base) < kRChunk ? (n - base) : kRChunk);
-        // (the read-ahead touches one record past the curve: the workspace keeps two spare records after the last curve)
-        const double *rec = a.rec + (off + base) * 6;
-        two_set_pipeline(
-            0, cnt, [&](const int i) { return fetch_sample(tab, rec, i, slot_a, slot_b); },
-            [&](const Ahead &h) {
-                const double wy = h.r[0], w = h.r[1];
-                walk_grid<kRK>(rot2(h.qa, h.qt), h.r[2], h.r[3], h.cd2, [&](const int k, const double s, const double c) {
-                    Sh[k] = __builtin_fma(wy, s, Sh[k]);
-                    Ch[k] = __builtin_fma(wy, c, Ch[k]);
-                    if (FIT_MEAN) {
-                        S[k] = __builtin_fma(w, s, S[k]);
-                        C[k] = __builtin_fma(w, c, C[k]);
-                    }
-                    SS[k] = __builtin_fma(s, s, SS[k]);
-                    SC[k] = __builtin_fma(s, c, SC[k]);
-                });
-            });
-    }
+    const double *recs = a.rec + off * 6;   // (the workspace keeps the two spare records after the last curve)
+    scan_stretch<kRChunk, kRK>(
+        tab, recs, n, 0, n, tid, slot_a, slot_b,
+        [&](double2 *row, const int64_t i, const bool real) {   // two threads per sample: the whole block
+            const double tp = real ? recs[i * 6 + 5] : 0.0;
+            const double sqw = real ? recs[i * 6 + 1] : 0.0;
+            fill_rotation_tables<kRCols>(row, tid & 1, tp, kdelta, f_tile, sqw);
+        },
+        [&](const Ahead &h, const int k, const double s, const double c) {
+            const double wy = h.r[0], w = h.r[1];
+            Sh[k] = __builtin_fma(wy, s, Sh[k]);
+            Ch[k] = __builtin_fma(wy, c, Ch[k]);
+            if (FIT_MEAN) {
+                S[k] = __builtin_fma(w, s, S[k]);
+                C[k] = __builtin_fma(w, c, C[k]);
+            }
+            SS[k] = __builtin_fma(s, s, SS[k]);
+            SC[k] = __builtin_fma(s, c, SC[k]);
+        });
 
     // fused epilogue (spectral.py:113-132); the 2-omega sums from sin 2a = 2 sin a cos a, cos 2a = 1 - 2 sin^2 a
     const double *sc = a.scal + curve * 4;

@@ -1,7 +1,8 @@
 // The device-side skeleton of the GLS direct sums, one copy: the prologue arithmetic (weights, weighted mean, the
-// 48-byte sample record), a chunk row of the rotation tables, the two-set scalar pipeline over a chunk's samples, the
-// walk of a thread's K grid frequencies, and the NaN-aware (max, lowest index) fold.  Everything here is inlined into
-// its caller: the kernels, their launch shapes and their registers are the callers' own.
+// 48-byte sample record and the two spare ones), the XCD order of the tiles, a chunk row of the rotation
+// tables, the two-set scalar pipeline over a chunk's samples, the walk of a thread's K grid frequencies, the loop that
+// runs these over a stretch of samples chunk by chunk, and the NaN-aware (max, lowest index) fold.  Everything here is
+// inlined into its caller: the kernels, their launch shapes and their registers are the callers' own.
 //
 // Each piece encodes a rule that every caller must keep in the same way:
 //   - sums are taken in one fixed order (per-thread stride loop, wave tree, waves in order): bitwise reproducible;
@@ -9,14 +10,26 @@
 //   - maxima follow np.nanargmax: NaN never wins, the first of equal maxima does;
 //   - the pipeline reads one record and one table row past the stretch it accumulates.
 //
-// Who uses what.  gls_ragged.hip and mhgls.hip are built from all of it; bls.hip and glsfft.hip take inv_var.
-// gls.hip takes rot2, walk_grid and inv_var (the wide prologue): gls_scan_kernel keeps its own table fill (with the
-// TIGHT / PAIR variants), pipeline, prologue and maxima, because the register allocation of that kernel - the headline
-// number - moves with the smallest change of the source around it (a local pointer to a table row re-allocates 38 of
-// its 60 instances), and its device assembly is required to stay byte-identical across a refactor.
-// Each of those four pieces, called from here, changed it.
+// Who uses what.  The scan of gls_ragged.hip and the four harmonic-sum scans (mhgls.hip, mbgls.hip, htest.hip,
+// htest_fdot.hip, with harmonic_sums.h on top) are scan_stretch with their own table fill and their own sums: mhgls and
+// htest one stretch per workgroup, mbgls one per band, htest_fdot with the spin-down offset in its fill.  mhgls and
+// mbgls take xcd_tile; their prologues and the H-test one take put_record and put_spare_records.  bls.hip and
+// glsfft.hip take inv_var.
+// The standing rule: a piece that raises the registers of an instance across an occupancy step, makes it spill, or
+// slows it beyond the run-to-run spread is not used by that instance, and the piece is not bent to fit it.  Three cases:
+//   - every scan kernel writes its tile preamble out: a shared frame for it cost the <12, 4, 256> H-test instances
+//     their second wave per SIMD;
+//   - mbgls.hip types its Chebyshev ladder out inside scan_stretch: through add_fourier_sums (harmonic_sums.h) the
+//     sample loop of mbgls_scan_kernel<1, 4> came out in another order and ran over its bound;
+//   - gls.hip takes rot2, walk_grid and inv_var (the wide prologue) only: gls_scan_kernel keeps its own table fill
+//     (with the TIGHT / PAIR variants), pipeline, prologue and maxima, because the register allocation of that kernel -
+//     the headline number - moves with the smallest change of the source around it (a local pointer to a table row
+//     re-allocates 38 of its 60 instances), and its device assembly is required to stay byte-identical across a
+//     refactor.  Each of those four pieces, called from here, changed it.
 #pragma once
 #include "pdc_device.h"
+
+#include <type_traits>
 
 namespace pdc {
 
@@ -54,6 +67,22 @@ __device__ __forceinline__ void put_record(double *rec_i, double wy, double w, d
     r[2] = make_double2(cd + cd, tp);
 }
 
+// The two spare records behind the n real ones, which the pipeline's read-ahead may load: finite, never accumulated.
+__device__ __forceinline__ void put_spare_records(double *rec, int64_t n, int tid) {
+    if (tid < 2) {
+        double2 *r = reinterpret_cast<double2 *>(rec + (n + tid) * 6);
+        r[0] = r[1] = r[2] = make_double2(0.0, 0.0);
+    }
+}
+
+// ---- a workgroup's tile of the frequency grid ---------------------------------------------------------------------------
+// Workgroup p runs on XCD p % 8 (observed dispatch rule, used for speed only): a contiguous run of tiles per XCD.  The
+// launch rounds the tiles up to a multiple of 8; a result >= tiles has no tile.
+__device__ __forceinline__ int64_t xcd_tile(unsigned block, int64_t tiles) {
+    const int64_t per_xcd = (tiles + 7) / 8;
+    return (int64_t)(block % 8) * per_xcd + block / 8;
+}
+
 // ---- rotation tables ---------------------------------------------------------------------------------------------------
 // plane rotation of {sin, cos} pairs: angle(x) + angle(y)
 __device__ __forceinline__ double2 rot2(const double2 x, const double2 y) {
@@ -66,10 +95,13 @@ __device__ __forceinline__ double2 rot2(const double2 x, const double2 y) {
 // sincos.  The even thread makes {sin, cos}(b Theta), b < 8 (one sincos, a chain of 6 rotations) and the tile's base
 // phase f_tile t' (one sincos), times `scale` (sqrt(w) where the sums want it carried, else 1); the odd thread walks
 // that base in steps of 8 Theta (one sincos, 8 COLS - 1 rotations).  Three software sincos per SAMPLE, whatever the
-// tile holds.  The caller keeps its guard (two threads per sample of the chunk), its barriers and its loads of tp.
-template <int COLS>
+// tile holds.  `offset()`, where one is given, moves the tile's base phase by that many cycles (any finite value:
+// sincos_cycles reduces it), base = frac(f_tile t') + offset(), added before the one sincos - for phases that are not
+// linear in the frequency alone, such as the spin-down term of htest_fdot.hip.  Without one nothing is added.
+struct NoOffset {};
+template <int COLS, class Offset = NoOffset>
 __device__ __forceinline__ void fill_rotation_tables(double2 *row, bool odd, double tp, double kdelta, double f_tile,
-                                                     double scale) {
+                                                     double scale, Offset offset = {}) {
     double2 step1, cur = make_double2(0.0, 0.0);
     if (!odd) {
         sincos_cycles(frac_product(kdelta, tp), step1.x, step1.y);
@@ -81,46 +113,9 @@ __device__ __forceinline__ void fill_rotation_tables(double2 *row, bool odd, dou
             cur = rot2(cur, step1);
             row[COLS * 8 + q] = cur;
         }
-        sincos_cycles(frac_product(f_tile, tp), cur.x, cur.y);
-        cur.x *= scale;
-        cur.y *= scale;
-    } else {
-        sincos_cycles(frac_product(8.0 * kdelta, tp), step1.x, step1.y);
-    }
-    double2 b0;
-    b0.x = __shfl_xor(cur.x, 1, 64);
-    b0.y = __shfl_xor(cur.y, 1, 64);
-    if (odd) {
-        row[0] = b0;
-#pragma unroll
-        for (int q = 1; q < COLS * 8; ++q) {
-            b0 = rot2(b0, step1);
-            row[q] = b0;
-        }
-    }
-}
-
-// fill_rotation_tables with the tile's base phase moved by `offset` cycles (any finite value: sincos_cycles reduces it):
-// base = frac(f_tile t') + offset, added before the one sincos.  offset = 0 gives the bits of fill_rotation_tables.
-// For phases that are not linear in the frequency alone, such as the spin-down term of htest_fdot.hip.
-// A copy, because fill_rotation_tables itself has to stay as it is for the units whose assembly is pinned: a change to
-// either must be made to both.  What holds them together is the test that a row with fdot = 0 has the bits of the plain
-// H-test scan (tests/test_htest_fdot_gpu.py::test_sample_parts).
-template <int COLS>
-__device__ __forceinline__ void fill_rotation_tables_at(double2 *row, bool odd, double tp, double kdelta, double f_tile,
-                                                        double scale, double offset) {
-    double2 step1, cur = make_double2(0.0, 0.0);
-    if (!odd) {
-        sincos_cycles(frac_product(kdelta, tp), step1.x, step1.y);
-        row[COLS * 8] = make_double2(0.0, 1.0);
-        row[COLS * 8 + 1] = step1;
-        cur = step1;
-#pragma unroll
-        for (int q = 2; q < 8; ++q) {
-            cur = rot2(cur, step1);
-            row[COLS * 8 + q] = cur;
-        }
-        sincos_cycles(frac_product(f_tile, tp) + offset, cur.x, cur.y);
+        double base = frac_product(f_tile, tp);
+        if constexpr (!std::is_same<Offset, NoOffset>::value) base += offset();
+        sincos_cycles(base, cur.x, cur.y);
         cur.x *= scale;
         cur.y *= scale;
     } else {
@@ -144,8 +139,7 @@ __device__ __forceinline__ void fill_rotation_tables_at(double2 *row, bool odd, 
 // sets (A, B) that swap roles, so the read-ahead costs no register copies.  The record fields are wave-uniform: they
 // come through the scalar cache (s_load, constant address space) and feed the fmas as SGPR operands - no LDS or VGPR
 // traffic for them; the two table entries are LDS reads.  Scalar loads return out of order, so the wait for set A
-// (lgkmcnt(0)) sits right before the request for set B goes out.  The read-ahead touches up to two records past
-// the last one accumulated (the workspaces keep two spare, finite records) and one padding table row.
+// (lgkmcnt(0)) sits right before the request for set B goes out.  What the read-ahead may touch: see scan_stretch.
 using d4 = double __attribute__((ext_vector_type(4)));
 using cd4 = __attribute__((address_space(4))) const d4;
 using cdbl = __attribute__((address_space(4))) const double;
@@ -210,6 +204,35 @@ __device__ __forceinline__ void walk_grid(const double2 seed, double cd, double 
             c = cn;
             s = sn;
         }
+    }
+}
+
+// ---- a stretch of samples, chunk by chunk --------------------------------------------------------------------------------
+// Samples [beg, end) of the records `recs` (n real ones), CHUNK at a time: the chunk's table rows are made by two
+// threads per sample, fill(row, i, real) for sample i (`real`: i < n; a row past the curve is never accumulated, it
+// only needs finite input), then every thread runs the pipeline over the chunk's samples and walks its K frequencies,
+// per_frequency(h, k, s, c) with the sample's record in h.r.  Every thread of the workgroup must call it, with the
+// same bounds (barriers).
+// What the read-ahead may touch: up to two records past `end` - real ones where the stretch ends inside the curve, else
+// the two spare records (put_spare_records) - and the table's padding row CHUNK.  None of it is accumulated.
+template <int CHUNK, int K, class Tab, class Fill, class PerFrequency>
+__device__ __forceinline__ void scan_stretch(Tab &tab, const double *recs, int64_t n, int64_t beg, int64_t end, int tid,
+                                             int slot_a, int slot_b, Fill fill, PerFrequency per_frequency) {
+    for (int64_t base = beg; base < end; base += CHUNK) {
+        __syncthreads();   // everyone is done with the previous chunk's tables
+        if (tid < 2 * CHUNK) {
+            const int il = tid >> 1;
+            fill(tab[il], base + il, base + il < n);
+        }
+        __syncthreads();
+        const int cnt = (int)((end - base) < CHUNK ? (end - base) : CHUNK);
+        const double *rec = recs + base * 6;
+        two_set_pipeline(
+            0, cnt, [&](const int i) { return fetch_sample(tab, rec, i, slot_a, slot_b); },
+            [&](const Ahead &h) {
+                walk_grid<K>(rot2(h.qa, h.qt), h.r[2], h.r[3], h.cd2,
+                             [&](const int k, const double s, const double c) { per_frequency(h, k, s, c); });
+            });
     }
 }
 

@@ -7,15 +7,16 @@
 //
 // The reference (periodicity.spectral) has no such class: PARITY UNPINNED BY THE REFERENCE.
 //
-// Decomposition (records, prep kernel, epilogue, ladder and sizes are in htest_common.h, shared with htest_fdot.hip)
+// Decomposition (records, prep kernel, part runs, partial sums, epilogue, ladder and sizes are in htest_common.h, shared
+// with htest_fdot.hip)
 //   htest_prep_kernel    one workgroup: sum w^2 (block_sum, fixed order) and one 48-byte record per event
 //                        {w, w, cos(2 pi delta t'), sin(2 pi delta t'), 2 cos(2 pi delta t'), t' = t - t0}, plus the
 //                        two spare records the pipeline reads ahead.
-//   htest_scan_kernel    the skeleton of gls_sums.h as mhgls.hip uses it (rotation tables per 64-event chunk, two-set
-//                        scalar pipeline, grid walk), (sin, cos) carried unscaled; harmonics 2 .. HT of every (event,
-//                        frequency) by the Chebyshev recurrence, 2 HT running sums per frequency, one fma each with w
-//                        as the SGPR operand: 4 HT - 2 fma per pair plus the walk.  Workgroup (tile, part) streams
-//                        the part's run of whole chunks.  parts == 1: the epilogue is fused, only the outputs are
+//   htest_scan_kernel    scan_stretch of gls_sums.h (rotation tables per 64-event chunk, two-set scalar pipeline,
+//                        grid walk) over the part's run, (sin, cos) carried unscaled; harmonics 2 .. HT of every (event,
+//                        frequency) by harmonic_ladder (harmonic_sums.h), 2 HT running sums per frequency, one fma
+//                        each with w as the SGPR operand: 4 HT - 2 fma per pair plus the walk.  Workgroup (tile, part)
+//                        streams the part's run of whole chunks.  parts == 1: the epilogue is fused, only the outputs are
 //                        written.  parts > 1: the workgroup writes its sums to partial[part][2 HT][nf] (rows k < nharm
 //                        of C, then of S), and
 //   htest_finish_kernel  one thread per bin adds the parts in ascending order (reads coalesced over bins) and runs the
@@ -68,18 +69,13 @@ __global__ __launch_bounds__(BLOCK) void htest_scan_kernel(HtArgs a) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int col = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int64_t n = a.n;
     const int64_t jt = tile * kTile;
     const int64_t jl = jt + (int64_t)tid * K;
     // numpy's arange fill rule: start + i*delta, two roundings (no fma)
     const double f_tile = __dadd_rn(a.f0, __dmul_rn((double)(a.j_begin + jt), a.delta));
     const double kdelta = (double)K * a.delta;   // spacing of the threads' first frequencies (exact)
-
-    // the part's run of whole chunks (an empty run adds zeros)
-    const int64_t chunks = (n + kChunk - 1) / kChunk;
-    const int64_t s_beg = (int64_t)part * chunks / a.parts * kChunk;
-    int64_t s_end = (int64_t)(part + 1) * chunks / a.parts * kChunk;
-    if (s_end > n) s_end = n;
+    int64_t s_beg, s_end;
+    part_run(part, a.parts, a.n, s_beg, s_end);
 
     double Ck[HT][K], Sk[HT][K];
 #pragma unroll
@@ -88,28 +84,12 @@ __global__ __launch_bounds__(BLOCK) void htest_scan_kernel(HtArgs a) {
         for (int m = 0; m < HT; ++m) Ck[m][k] = Sk[m][k] = 0.0;
 
     const int slot_a = col * 8 + (lane >> 3), slot_b = COLS * 8 + (lane & 7);
-    for (int64_t base = s_beg; base < s_end; base += kChunk) {
-        __syncthreads();   // everyone is done with the previous chunk's tables
-        if (tid < 2 * kChunk) {   // rotation tables, two threads per event; (sin, cos) unscaled
-            const int il = tid >> 1;
-            // (rows past the end of the list are never accumulated; they only need finite input)
-            const double tp = base + il < n ? a.rec[(base + il) * 6 + 5] : 0.0;
-            fill_rotation_tables<COLS>(tab[il], tid & 1, tp, kdelta, f_tile, 1.0);
-        }
-        __syncthreads();
-        const int cnt = (int)((s_end - base) < kChunk ? (s_end - base) : kChunk);
-        // (the read-ahead touches up to two records past the run - real ones, or the prologue's spares - and the
-        // padding row of the table)
-        const double *rec = a.rec + base * 6;
-        two_set_pipeline(
-            0, cnt, [&](const int i) { return fetch_sample(tab, rec, i, slot_a, slot_b); },
-            [&](const Ahead &h) {
-                const double w = h.r[1];
-                // harmonics of this (event, frequency): Chebyshev recurrence on the unscaled (sin, cos)
-                walk_grid<K>(rot2(h.qa, h.qt), h.r[2], h.r[3], h.cd2,
-                             [&](const int k, const double s, const double c) { add_harmonics<HT, K>(Ck, Sk, k, w, s, c); });
-            });
-    }
+    scan_stretch<kChunk, K>(
+        tab, a.rec, a.n, s_beg, s_end, tid, slot_a, slot_b,
+        [&](double2 *row, const int64_t i, const bool real) {   // (sin, cos) unscaled
+            fill_rotation_tables<COLS>(row, tid & 1, real ? a.rec[i * 6 + 5] : 0.0, kdelta, f_tile, 1.0);
+        },
+        [&](const Ahead &h, const int k, const double s, const double c) { add_harmonics<HT, K>(Ck, Sk, k, h.r[1], s, c); });
 
     if (a.parts == 1) {
         const double scale = 2.0 / a.scal[0];
@@ -122,39 +102,16 @@ __global__ __launch_bounds__(BLOCK) void htest_scan_kernel(HtArgs a) {
         }
         return;
     }
-    double *out = a.partial + (int64_t)part * (2 * HT) * a.nf;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int64_t j = jl + k;
-        if (j < a.nf) {
-#pragma unroll
-            for (int m = 0; m < HT; ++m) {
-                if (m < a.nharm) {
-                    out[(int64_t)m * a.nf + j] = Ck[m][k];
-                    out[(int64_t)(HT + m) * a.nf + j] = Sk[m][k];
-                }
-            }
-        }
-    }
+    store_partial<HT, K>(a.partial + (int64_t)part * (2 * HT) * a.nf, a.nf, a.nharm, jl, Ck, Sk);
 }
 
 // One thread per bin; `ht` is the scan's HT (the row count of a part's block).
 __global__ __launch_bounds__(kFinishBlock) void htest_finish_kernel(HtArgs a, int ht) {
     const int64_t j = (int64_t)blockIdx.x * kFinishBlock + threadIdx.x;
     if (j >= a.nf) return;
-    const int64_t part_stride = (int64_t)2 * ht * a.nf;
     htest_epilogue<kMaxHarm>(
-        a.nharm, 2.0 / a.scal[0],
-        [&](const int m) {
-            const double *pc = a.partial + (int64_t)m * a.nf + j, *ps = pc + (int64_t)ht * a.nf;
-            double c = 0.0, s = 0.0;
-            for (int p = 0; p < a.parts; ++p) {
-                c += pc[p * part_stride];
-                s += ps[p * part_stride];
-            }
-            return make_double2(c, s);
-        },
-        j, a.h, a.m, a.z2);
+        a.nharm, 2.0 / a.scal[0], [&](const int m) { return sum_parts(a.partial, ht, a.nf, a.parts, j, m); }, j, a.h, a.m,
+        a.z2);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
@@ -203,14 +160,7 @@ int ht_enqueue(hipStream_t st, const double *d_t, const double *d_w, int64_t n, 
     a.m = d_m;
     a.z2 = d_z2;
     g_last = {rung.ht, rung.k, parts};
-    switch (rung.ht) {
-        case 2: PDC_TRY((launch_scan<2, 4, 256>(st, a))); break;
-        case 4: PDC_TRY((launch_scan<4, 4, 256>(st, a))); break;
-        case 8: PDC_TRY((launch_scan<8, 4, 256>(st, a))); break;
-        case 12: PDC_TRY((launch_scan<12, 4, 256>(st, a))); break;
-        case 16: PDC_TRY((launch_scan<16, 2, 512>(st, a))); break;
-        default: PDC_TRY((launch_scan<20, 2, 512>(st, a))); break;
-    }
+    PDC_TRY(with_rung(rung, [&](auto r) { return launch_scan<decltype(r)::ht, decltype(r)::k, decltype(r)::block>(st, a); }));
     PDC_HIP(hipGetLastError());
     if (parts > 1) {
         hipLaunchKernelGGL(htest_finish_kernel, dim3((unsigned)((nf + kFinishBlock - 1) / kFinishBlock)), dim3(kFinishBlock),

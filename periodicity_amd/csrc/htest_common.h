@@ -1,10 +1,11 @@
 // What the H-test units share (htest.hip: one frequency axis; htest_fdot.hip: the frequency - spin-down plane): the
-// 48-byte event records and the kernel that makes them, the epilogue from the 2 HT sums of a bin to Z^2_m, H and its m,
-// the ladder of kernel instances, the workspace sizes and the argument checks.  Everything is internal to the unit that
-// includes it (anonymous namespace): each unit carries its own copy of the prep kernel.
+// 48-byte event records and the kernel that makes them, the harmonics' running sums, a part's run of chunks, the store
+// and the ascending-order sum of the parts' partial sums, the epilogue from the 2 HT sums of a bin to Z^2_m, H and its
+// m, the ladder of kernel instances with its dispatch, the workspace sizes and the argument checks.  Everything is
+// internal to the unit that includes it (anonymous namespace): each unit carries its own copy of the prep kernel.
 #pragma once
 #include "pdc_internal.h"
-#include "gls_sums.h"
+#include "harmonic_sums.h"
 
 #include <cmath>
 
@@ -33,16 +34,12 @@ __global__ __launch_bounds__(kPrepBlock) void htest_prep_kernel(HtPrepArgs a) {
     const int tid = threadIdx.x;
     const double t0 = a.t[0];
     double w2 = 0.0;
-    for (int64_t i = tid; i < a.n + 2; i += kPrepBlock) {
-        if (i >= a.n) {   // the read-ahead records: finite, never accumulated
-            double2 *r = reinterpret_cast<double2 *>(a.rec + i * 6);
-            r[0] = r[1] = r[2] = make_double2(0.0, 0.0);
-            continue;
-        }
+    for (int64_t i = tid; i < a.n; i += kPrepBlock) {
         const double w = a.w ? a.w[i] : 1.0;
         w2 += w * w;
         put_record(a.rec + i * 6, w, w, a.delta, a.t[i] - t0);
     }
+    put_spare_records(a.rec, a.n, tid);
     w2 = block_sum<kPrepBlock>(w2, red);
     if (tid == 0) a.scal[0] = w2;
 }
@@ -73,25 +70,56 @@ __device__ __forceinline__ void htest_epilogue(int nharm, double scale, Sums cs,
     if (z2_out) z2_out[j] = z;
 }
 
-// The Chebyshev ladder of one (event, frequency) pair: harmonics 1 .. HT from the unscaled (sin, cos) of the first,
-// each added to its running sums with weight w: 4 HT - 2 fma.
+// Harmonics 1 .. HT of one (event, frequency) pair (harmonic_ladder), each added to its running sums with weight w:
+// 4 HT - 2 fma.
 template <int HT, int K>
 __device__ __forceinline__ void add_harmonics(double (&Ck)[HT][K], double (&Sk)[HT][K], const int k, const double w,
                                               const double s, const double c) {
-    const double c2 = c + c;
-    double sm = s, cm = c, sl = 0.0, cl = 1.0;   // harmonic m and m - 1
-#pragma unroll
-    for (int m = 1; m <= HT; ++m) {
+    harmonic_ladder<HT>(s, c, [&](const int m, const double sm, const double cm) {
         Ck[m - 1][k] = __builtin_fma(w, cm, Ck[m - 1][k]);
         Sk[m - 1][k] = __builtin_fma(w, sm, Sk[m - 1][k]);
-        if (m < HT) {
-            const double cn = __builtin_fma(c2, cm, -cl), sn = __builtin_fma(c2, sm, -sl);
-            cl = cm;
-            sl = sm;
-            cm = cn;
-            sm = sn;
+    });
+}
+
+// ---- sample parts -----------------------------------------------------------------------------------------------------
+// Part `part` of `parts` takes a run of whole chunks, events [s_beg, s_end) (an empty run adds zeros).
+__device__ __forceinline__ void part_run(int part, int parts, int64_t n, int64_t &s_beg, int64_t &s_end) {
+    const int64_t chunks = (n + kChunk - 1) / kChunk;
+    s_beg = (int64_t)part * chunks / parts * kChunk;
+    s_end = (int64_t)(part + 1) * chunks / parts * kChunk;
+    if (s_end > n) s_end = n;
+}
+
+// A part's sums of a thread's K bins from jl on, to its block out[2 HT][nf]: rows k < nharm of C, then of S.
+template <int HT, int K>
+__device__ __forceinline__ void store_partial(double *out, int64_t nf, int nharm, int64_t jl, const double (&Ck)[HT][K],
+                                              const double (&Sk)[HT][K]) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int64_t j = jl + k;
+        if (j < nf) {
+#pragma unroll
+            for (int m = 0; m < HT; ++m) {
+                if (m < nharm) {
+                    out[(int64_t)m * nf + j] = Ck[m][k];
+                    out[(int64_t)(HT + m) * nf + j] = Sk[m][k];
+                }
+            }
         }
     }
+}
+
+// {C, S} of harmonic m + 1 at bin j: the parts' blocks from p0 on (`ht` rows of C, `ht` of S each) added in ascending
+// order, reads coalesced over bins.  No atomics: for a given `parts` the bits are the same from call to call.
+__device__ __forceinline__ double2 sum_parts(const double *p0, int ht, int64_t nf, int parts, int64_t j, int m) {
+    const int64_t part_stride = (int64_t)2 * ht * nf;
+    const double *pc = p0 + (int64_t)m * nf + j, *ps = pc + (int64_t)ht * nf;
+    double c = 0.0, s = 0.0;
+    for (int p = 0; p < parts; ++p) {
+        c += pc[p * part_stride];
+        s += ps[p * part_stride];
+    }
+    return make_double2(c, s);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
@@ -100,11 +128,27 @@ struct Rung {
 };
 constexpr Rung kLadder[] = {{2, 4, 256}, {4, 4, 256}, {8, 4, 256}, {12, 4, 256}, {16, 2, 512}, {20, 2, 512}};
 
+constexpr int kRungs = sizeof(kLadder) / sizeof(kLadder[0]);
+
 inline const Rung *rung_of(int nharm) {
     if (nharm < 1 || nharm > kMaxHarm) return nullptr;
     for (const Rung &r : kLadder)
         if (r.ht >= nharm) return &r;
     return nullptr;
+}
+
+// f(RungAt<I>()) for the entry I of kLadder with rung.ht, and its status: the kernel instances a unit launches are
+// <R::ht, R::k, R::block> of that one table.
+template <int I>
+struct RungAt {
+    static constexpr int ht = kLadder[I].ht, k = kLadder[I].k, block = kLadder[I].block;
+};
+template <int I = 0, class F>
+int with_rung(const Rung &rung, F f) {
+    if (rung.ht == kLadder[I].ht) return f(RungAt<I>());
+    if constexpr (I + 1 < kRungs) return with_rung<I + 1>(rung, f);
+    PDC_REQUIRE(false, "htest: HT = %d is no entry of the ladder", rung.ht);
+    return PDC_OK;
 }
 
 // dynamic LDS of a scan instance: [kChunk + 1] table rows of 8 COLS + 8 + 1 entries

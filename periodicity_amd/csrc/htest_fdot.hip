@@ -4,15 +4,16 @@
 // the best fdot) and the best cell.  f (t_0 - epoch) is common to all events and drops out of every C_k^2 + S_k^2, so
 // the scan keeps f t' with t' = t - t[0] from htest.hip's records and adds only the offset
 //     phi_i = frac(fdot tau_i^2 / 2)
-// to an event's tile base phase, in cycles, before the one sincos of the table fill (fill_rotation_tables_at).  phi is
+// to an event's tile base phase, in cycles, before the one sincos of the table fill (its `offset`).  phi is
 // reduced exactly: tau^2 as the pair (hi, lo) of a product and its fma error, frac_product(fdot / 2, hi) + fdot / 2 lo.
 // A handful of flops per (event, tile, row): no further sincos, no [nfd][n] table in memory, and the 1024 frequencies
 // of the tile walk from the base as before at 4 HT - 2 fma per pair.  fdot = 0 gives phi = 0 and the bits of
 // pdc_htest_scan at the same `parts`.
 //
-// Decomposition (records, ladder, epilogue, sizes: htest_common.h)
+// Decomposition (records, part runs, partial sums, ladder, epilogue, sizes: htest_common.h)
 //   htest_prep_kernel        as htest.hip.
-//   htest_fdot_scan_kernel   htest_scan_kernel with blockIdx = (tile, part, row); `row` indexes the fdot values of this
+//   htest_fdot_scan_kernel   scan_stretch of gls_sums.h over the part's run, with phi in the fill; blockIdx = (tile, part,
+//                            row) and `row` indexes the fdot values of this
 //                            launch; the row is an SGPR, fdot / 2 and the epoch wait in LDS for the table fills (in
 //                            SGPRs across the hot loop they cost two VGPRs).  parts == 1: the epilogue is fused and
 //                            writes the row's values (H, or Z^2 at nharm) and m to the plane, or to a [rows][nf] slab
@@ -79,24 +80,21 @@ __global__ __launch_bounds__(BLOCK) void htest_fdot_scan_kernel(FdArgs a) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int col = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int64_t n = a.n;
     const int64_t jt = tile * kTile;
     const int64_t jl = jt + (int64_t)tid * K;
+    // numpy's arange fill rule: start + i*delta, two roundings (no fma)
     const double f_tile = __dadd_rn(a.f0, __dmul_rn((double)(a.j_begin + jt), a.delta));
-    const double kdelta = (double)K * a.delta;
-    // The row's two constants, fdot / 2 and the epoch, wait in LDS for the table fills (the first read is behind the chunk
-    // loop's first barrier).  Held in scalar registers across the hot loop they cost every instance two VGPRs at its
+    const double kdelta = (double)K * a.delta;   // spacing of the threads' first frequencies (exact)
+    // The row's two constants, fdot / 2 and the epoch, wait in LDS for the table fills (the first read is behind the
+    // stretch's first barrier).  Held in scalar registers across the hot loop they cost every instance two VGPRs at its
     // peak, and <12, 4, 256>, which sits at 256, its second wave per SIMD.
     __shared__ double fd_const[2];
     if (tid == 0) {
         fd_const[0] = 0.5 * a.fdot[a.row0 + row];
         fd_const[1] = a.epoch;
     }
-
-    const int64_t chunks = (n + kChunk - 1) / kChunk;
-    const int64_t s_beg = (int64_t)part * chunks / a.parts * kChunk;
-    int64_t s_end = (int64_t)(part + 1) * chunks / a.parts * kChunk;
-    if (s_end > n) s_end = n;
+    int64_t s_beg, s_end;
+    part_run(part, a.parts, a.n, s_beg, s_end);
 
     double Ck[HT][K], Sk[HT][K];
 #pragma unroll
@@ -105,26 +103,14 @@ __global__ __launch_bounds__(BLOCK) void htest_fdot_scan_kernel(FdArgs a) {
         for (int m = 0; m < HT; ++m) Ck[m][k] = Sk[m][k] = 0.0;
 
     const int slot_a = col * 8 + (lane >> 3), slot_b = COLS * 8 + (lane & 7);
-    for (int64_t base = s_beg; base < s_end; base += kChunk) {
-        __syncthreads();   // everyone is done with the previous chunk's tables
-        if (tid < 2 * kChunk) {
-            const int il = tid >> 1;
-            const bool real = base + il < n;   // (rows past the end are never accumulated; they only need finite input)
-            const double tp = real ? a.rec[(base + il) * 6 + 5] : 0.0;
-            const double tau = real ? a.t[base + il] - fd_const[1] : 0.0;
-            fill_rotation_tables_at<COLS>(tab[il], tid & 1, tp, kdelta, f_tile, 1.0, spin_down_cycles(fd_const[0], tau));
-        }
-        __syncthreads();
-        const int cnt = (int)((s_end - base) < kChunk ? (s_end - base) : kChunk);
-        const double *rec = a.rec + base * 6;
-        two_set_pipeline(
-            0, cnt, [&](const int i) { return fetch_sample(tab, rec, i, slot_a, slot_b); },
-            [&](const Ahead &h) {
-                const double w = h.r[1];
-                walk_grid<K>(rot2(h.qa, h.qt), h.r[2], h.r[3], h.cd2,
-                             [&](const int k, const double s, const double c) { add_harmonics<HT, K>(Ck, Sk, k, w, s, c); });
+    scan_stretch<kChunk, K>(
+        tab, a.rec, a.n, s_beg, s_end, tid, slot_a, slot_b,
+        [&](double2 *trow, const int64_t i, const bool real) {   // (sin, cos) unscaled, the base moved by phi_i
+            fill_rotation_tables<COLS>(trow, tid & 1, real ? a.rec[i * 6 + 5] : 0.0, kdelta, f_tile, 1.0, [&] {
+                return spin_down_cycles(fd_const[0], real ? a.t[i] - fd_const[1] : 0.0);
             });
-    }
+        },
+        [&](const Ahead &h, const int k, const double s, const double c) { add_harmonics<HT, K>(Ck, Sk, k, h.r[1], s, c); });
 
     if (a.parts == 1) {
         const double scale = 2.0 / a.scal[0];
@@ -140,20 +126,7 @@ __global__ __launch_bounds__(BLOCK) void htest_fdot_scan_kernel(FdArgs a) {
         }
         return;
     }
-    double *out = a.partial + ((int64_t)row * a.parts + part) * (2 * HT) * a.nf;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int64_t j = jl + k;
-        if (j < a.nf) {
-#pragma unroll
-            for (int m = 0; m < HT; ++m) {
-                if (m < a.nharm) {
-                    out[(int64_t)m * a.nf + j] = Ck[m][k];
-                    out[(int64_t)(HT + m) * a.nf + j] = Sk[m][k];
-                }
-            }
-        }
-    }
+    store_partial<HT, K>(a.partial + ((int64_t)row * a.parts + part) * (2 * HT) * a.nf, a.nf, a.nharm, jl, Ck, Sk);
 }
 
 // One thread per bin; `ht` is the scan's HT (the row count of a part's block).
@@ -177,15 +150,7 @@ __global__ __launch_bounds__(kFinishBlock) void htest_fdot_fold_kernel(FdArgs a,
             const double *p0 = a.partial + (int64_t)row * a.parts * part_stride;
             htest_epilogue<kMaxHarm>(
                 a.nharm, scale,
-                [&](const int m) {
-                    const double *pc = p0 + (int64_t)m * a.nf + j, *ps = pc + (int64_t)ht * a.nf;
-                    double c = 0.0, s = 0.0;
-                    for (int p = 0; p < a.parts; ++p) {
-                        c += pc[p * part_stride];
-                        s += ps[p * part_stride];
-                    }
-                    return make_double2(c, s);
-                },
+                [&](const int m) { return sum_parts(p0, ht, a.nf, a.parts, j, m); },
                 0, &h, &mv, &z2);
             v = a.stat == 0 ? h : z2;
             if (a.val) a.val[(int64_t)row * a.nf + j] = v;
@@ -346,14 +311,8 @@ int fd_enqueue(hipStream_t st, const double *d_t, const double *d_w, int64_t n, 
             }
             if (plan.slab_m) a.m = reinterpret_cast<int32_t *>(slab);
         }
-        switch (ht) {
-            case 2: PDC_TRY((launch_scan<2, 4, 256>(st, a))); break;
-            case 4: PDC_TRY((launch_scan<4, 4, 256>(st, a))); break;
-            case 8: PDC_TRY((launch_scan<8, 4, 256>(st, a))); break;
-            case 12: PDC_TRY((launch_scan<12, 4, 256>(st, a))); break;
-            case 16: PDC_TRY((launch_scan<16, 2, 512>(st, a))); break;
-            default: PDC_TRY((launch_scan<20, 2, 512>(st, a))); break;
-        }
+        PDC_TRY(with_rung(*plan.rung,
+                          [&](auto r) { return launch_scan<decltype(r)::ht, decltype(r)::k, decltype(r)::block>(st, a); }));
         PDC_HIP(hipGetLastError());
         hipLaunchKernelGGL(htest_fdot_fold_kernel, dim3((unsigned)((nf + kFinishBlock - 1) / kFinishBlock)),
                            dim3(kFinishBlock), 0, st, a, ht);

@@ -16,16 +16,16 @@
 //                       waves walks a sixteenth of the samples 64 at a time, once per band; a ballot on `label == b`
 //                       and a prefix popcount give each sample its place: no atomics, the same bits at every call, and
 //                       a label never indexes memory.
-//   mbgls_scan_kernel   the tile, tables, pipeline and grid walk of mhgls_scan_kernel.  The chunk loop runs band by band
-//                       (a band that ends mid-chunk ends its stretch); the 6 H sums per frequency run across all bands
-//                       with the fmas of mhgls; at a band's end v_b is the difference to a snapshot of (C_h, S_h) taken
+//   mbgls_scan_kernel   the tile (xcd_tile) and one scan_stretch of gls_sums.h PER BAND (a band that ends
+//                       mid-chunk ends its stretch); the 6 H sums per frequency run across all bands (the ladder of
+//                       add_fourier_sums typed out: gls_sums.h, who uses what); at a band's end v_b is the difference to a snapshot of (C_h, S_h) taken
 //                       at the previous boundary, and the rank-one updates above go into H (2H + 1) + 2H registers
-//                       per frequency - none of it grows with the number of bands.  Epilogue: unrolled Cholesky over
-//                       the 2H harmonic columns.
+//                       per frequency - none of it grows with the number of bands.  Epilogue: cholesky_quadratic over
+//                       the 2H harmonic columns, its entries fourier_entry minus the rank-one terms.
 // Without fit_mean there are no offsets and no centring: the labels are not read and the curve is one stretch - the sums
-// of mhgls with fit_mean = 0.
+// of mhgls.hip with fit_mean = 0.
 #include "pdc_internal.h"
-#include "gls_sums.h"
+#include "harmonic_sums.h"
 
 #include <cmath>
 
@@ -198,10 +198,7 @@ __global__ __launch_bounds__(kPrepBlock) void mbgls_prep_kernel(MbPrepArgs a) {
             s_q[b][wave] = y1;
         }
     }
-    if (tid < 2) {   // the read-ahead records: finite, never accumulated
-        double2 *r = reinterpret_cast<double2 *>(a.rec + (n + tid) * 6);
-        r[0] = r[1] = r[2] = make_double2(0.0, 0.0);
-    }
+    put_spare_records(a.rec, n, tid);
     __syncthreads();
     if (tid < B) {
         double yy = 0.0, y1 = 0.0;
@@ -228,56 +225,6 @@ __global__ __launch_bounds__(kPrepBlock) void mbgls_prep_kernel(MbPrepArgs a) {
     }
 }
 
-// ---- epilogue: b'^T M'^-1 b' by an unrolled Cholesky over the 2H harmonic columns ------------------------------------
-// Basis order (cos th, sin th, ..., cos H th, sin H th).  Cs[m] = sum w cos(m th), Ss[m] = sum w sin(m th) for
-// m = 0 .. 2H (Cs[0] = sum w, Ss[0] = 0); entry (r, c), r >= c, of M_hh by the product-to-sum rules (the rule of
-// mh_entry in mhgls.hip, whose unit must stay as it is), minus the bands' rank-one terms in corr[r (r + 1) / 2 + c].
-template <int H>
-__device__ __forceinline__ double mb_entry(const double (&Cs)[2 * H + 1], const double (&Ss)[2 * H + 1],
-                                           const double (&corr)[H * (2 * H + 1)], int r, int c) {
-    const int hr = r / 2 + 1, hc = c / 2 + 1;
-    double e;
-    if ((r & 1) == (c & 1)) {
-        const double far = Cs[hr + hc], near = Cs[hr - hc];
-        e = (r & 1) ? 0.5 * (near - far) : 0.5 * (near + far);
-    } else {
-        // sin(hr th) cos(hc th) = (sin((hr + hc) th) + sin((hr - hc) th)) / 2;  cos(hr th) sin(hc th): minus
-        e = (r & 1) ? 0.5 * (Ss[hr + hc] + Ss[hr - hc]) : 0.5 * (Ss[hr + hc] - Ss[hr - hc]);
-    }
-    return e - corr[r * (r + 1) / 2 + c];
-}
-
-// A pivot that is not > 0, or is not finite, makes the bin NaN (the rule of mh_quadratic).
-template <int H>
-__device__ __forceinline__ double mb_quadratic(const double (&Cs)[2 * H + 1], const double (&Ss)[2 * H + 1],
-                                               const double (&corr)[H * (2 * H + 1)], const double (&b)[2 * H]) {
-    constexpr int D = 2 * H;
-    double L[D][D], z[D];
-    double quad = 0.0;
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        double d = mb_entry<H>(Cs, Ss, corr, j, j);
-#pragma unroll
-        for (int q = 0; q < j; ++q) d -= L[j][q] * L[j][q];
-        bad = bad || !(d > 0.0) || !(d < HUGE_VAL);
-        const double inv = 1.0 / __builtin_sqrt(d);
-        double zj = b[j];
-#pragma unroll
-        for (int q = 0; q < j; ++q) zj -= L[j][q] * z[q];
-        z[j] = zj * inv;
-        quad += z[j] * z[j];
-#pragma unroll
-        for (int i = j + 1; i < D; ++i) {
-            double v = mb_entry<H>(Cs, Ss, corr, i, j);
-#pragma unroll
-            for (int q = 0; q < j; ++q) v -= L[i][q] * L[j][q];
-            L[i][j] = v * inv;
-        }
-    }
-    return bad ? __builtin_nan("") : quad;
-}
-
 // ---- the scan -------------------------------------------------------------------------------------------------------
 // The scalar block is read as wave-uniform values through the scalar cache (as the records are): the band loop's
 // bounds, and with them the barriers and the record addresses inside it, are uniform to the compiler too.
@@ -291,22 +238,22 @@ __device__ __forceinline__ int64_t start_at(const double *scal, int b) {
 
 // H = harmonics, K = trial frequencies per thread: (6 H + 2 H + H (2H + 1)) K doubles of sums, snapshots and rank-one
 // terms, whatever the number of bands.
+// Epilogue: basis order (cos th, sin th, ..., cos H th, sin H th); entry (r, c), r >= c, of M' is that of M_hh minus the
+// bands' rank-one terms in corr[r (r + 1) / 2 + c].
 template <int H, int K>
 __global__ __launch_bounds__(kBlock) void mbgls_scan_kernel(MbArgs a) {
     constexpr int COLS = kBlock / 64;   // 64-lane columns of the tile
     constexpr int NC = H * (2 * H + 1);
-    // per sample: {sin, cos} of theta_tile + 8 q Theta, q < 8 COLS | {sin, cos}(b Theta), b < 8 (see mhgls.hip)
+    // per sample: {sin, cos} of theta_tile + 8 q Theta, q < 8 COLS | {sin, cos}(b Theta), b < 8 (fill_rotation_tables)
     __shared__ double2 tab[kChunk + 1][COLS * 8 + 8 + 1];   // + 1: rows start 16 B apart modulo 128 B (bank spread)
 
-    // Workgroup p runs on XCD p % 8 (observed dispatch rule, used for speed only): a contiguous run of tiles per XCD.
-    const int64_t per_xcd = (a.tiles + 7) / 8;
-    const int64_t tile = (int64_t)(blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
+    const int64_t tile = xcd_tile(blockIdx.x, a.tiles);
     if (tile >= a.tiles) return;
-
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int col = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int64_t n = a.n;
+    // first local frequency of the tile and of this thread
     const int64_t jt = tile * kBlock * (int64_t)K;
     const int64_t jl = jt + (int64_t)tid * K;
 
@@ -339,46 +286,33 @@ __global__ __launch_bounds__(kBlock) void mbgls_scan_kernel(MbArgs a) {
     for (int b = 0; b < a.n_bands; ++b) {
         const int64_t end = start_at(a.scal, b + 1);
         if (end <= beg) continue;   // an empty band
-        for (int64_t base = beg; base < end; base += kChunk) {
-            __syncthreads();   // everyone is done with the previous chunk's tables
-            if (tid < 2 * kChunk) {   // rotation tables, two threads per sample; (sin, cos) unscaled
-                const int il = tid >> 1;
-                // (rows past the band's end are never accumulated; they only need finite input)
-                const double tp = base + il < n ? a.rec[(base + il) * 6 + 5] : 0.0;
-                fill_rotation_tables<COLS>(tab[il], tid & 1, tp, kdelta, f_tile, 1.0);
-            }
-            __syncthreads();
-            const int cnt = (int)((end - base) < kChunk ? (end - base) : kChunk);
-            // (the read-ahead touches records past the stretch - the next band's, or the spare ones the prologue wrote -
-            // and the padding row of the table)
-            const double *rec = a.rec + base * 6;
-            two_set_pipeline(
-                0, cnt, [&](const int i) { return fetch_sample(tab, rec, i, slot_a, slot_b); },
-                [&](const Ahead &h) {
-                    const double wy = h.r[0], w = h.r[1];
-                    walk_grid<K>(rot2(h.qa, h.qt), h.r[2], h.r[3], h.cd2, [&](const int k, const double s, const double c) {
-                        // harmonics of this (sample, frequency): Chebyshev recurrence on the unscaled (sin, cos)
-                        const double c2 = c + c;
-                        double sm = s, cm = c, sl = 0.0, cl = 1.0;   // harmonic m and m - 1
+        // one stretch per band (a band that ends mid-chunk ends its stretch: the read-ahead sees the next band's records)
+        scan_stretch<kChunk, K>(
+            tab, a.rec, n, beg, end, tid, slot_a, slot_b,
+            [&](double2 *row, const int64_t i, const bool real) {   // (sin, cos) unscaled
+                fill_rotation_tables<COLS>(row, tid & 1, real ? a.rec[i * 6 + 5] : 0.0, kdelta, f_tile, 1.0);
+            },
+            [&](const Ahead &h, const int k, const double s, const double c) {
+                const double wy = h.r[0], w = h.r[1];
+                const double c2 = c + c;
+                double sm = s, cm = c, sl = 0.0, cl = 1.0;   // harmonic m and m - 1
 #pragma unroll
-                        for (int m = 1; m <= 2 * H; ++m) {
-                            Cm[m - 1][k] = __builtin_fma(w, cm, Cm[m - 1][k]);
-                            Sm[m - 1][k] = __builtin_fma(w, sm, Sm[m - 1][k]);
-                            if (m <= H) {
-                                YC[m - 1][k] = __builtin_fma(wy, cm, YC[m - 1][k]);
-                                YS[m - 1][k] = __builtin_fma(wy, sm, YS[m - 1][k]);
-                            }
-                            if (m < 2 * H) {
-                                const double cn = __builtin_fma(c2, cm, -cl), sn = __builtin_fma(c2, sm, -sl);
-                                cl = cm;
-                                sl = sm;
-                                cm = cn;
-                                sm = sn;
-                            }
-                        }
-                    });
-                });
-        }
+                for (int m = 1; m <= 2 * H; ++m) {
+                    Cm[m - 1][k] = __builtin_fma(w, cm, Cm[m - 1][k]);
+                    Sm[m - 1][k] = __builtin_fma(w, sm, Sm[m - 1][k]);
+                    if (m <= H) {
+                        YC[m - 1][k] = __builtin_fma(wy, cm, YC[m - 1][k]);
+                        YS[m - 1][k] = __builtin_fma(wy, sm, YS[m - 1][k]);
+                    }
+                    if (m < 2 * H) {
+                        const double cn = __builtin_fma(c2, cm, -cl), sn = __builtin_fma(c2, sm, -sl);
+                        cl = cm;
+                        sl = sm;
+                        cm = cn;
+                        sm = sn;
+                    }
+                }
+            });
         if (a.fit_mean) {   // the band's offset leaves the normal equations
             const double iw = 1.0 / scal_at(a.scal, kScalWb + b), Yb = scal_at(a.scal, kScalYb + b);
             const double yw = Yb * iw;
@@ -411,26 +345,12 @@ __global__ __launch_bounds__(kBlock) void mbgls_scan_kernel(MbArgs a) {
     for (int k = 0; k < K; ++k) {
         const int64_t j = jl + k;
         if (j < a.nf) {
-            double Cs[2 * H + 1], Ss[2 * H + 1], bv[2 * H], ck[NC];
-            Cs[0] = Wsum;
-            Ss[0] = 0.0;
-#pragma unroll
-            for (int m = 1; m <= 2 * H; ++m) {
-                Cs[m] = Cm[m - 1][k];
-                Ss[m] = Sm[m - 1][k];
-            }
-#pragma unroll
-            for (int h = 0; h < H; ++h) {
-                bv[2 * h] = YC[h][k];
-                bv[2 * h + 1] = YS[h][k];
-            }
-#pragma unroll
-            for (int e = 0; e < NC; ++e) ck[e] = corr[e][k];
-            double p = q0 + mb_quadratic<H>(Cs, Ss, ck, bv);
-            // the two normalisations of GLS (gls_epilogue.h)
-            if (a.psd) p *= 0.5 * Werr;
-            else p /= YY;
-            a.power[j] = p;
+            double Cs[2 * H + 1], Ss[2 * H + 1], bv[2 * H];
+            gather_fourier_sums<H, K>(Cm, Sm, YC, YS, k, Wsum, Cs, Ss, bv);
+            const double quad = cholesky_quadratic<2 * H>(
+                [&](const int r, const int c) { return fourier_entry<H>(Cs, Ss, r, c) - corr[r * (r + 1) / 2 + c][k]; }, bv,
+                2 * H);
+            a.power[j] = normalised_power(q0 + quad, a.psd, Werr, YY);
         }
     }
 }

@@ -8,20 +8,20 @@
 // Decomposition
 //   mhgls_prep_kernel   one workgroup: weights, weighted mean, YY, and one 48-byte record per sample
 //                       {w y, w, cos(2 pi delta t'), sin(2 pi delta t'), 2 cos(2 pi delta t'), t' = t - t0}.
-//   mhgls_scan_kernel   the skeleton of gls_sums.h: each thread owns K consecutive frequencies, the
-//                       records come through the scalar cache, the seed of a (sample, thread) is one plane rotation of
-//                       two LDS table entries built per 64-sample chunk from exact cycle reductions, and a rotation
-//                       plus the three-term recurrence walk the K frequencies.  (sin, cos) are carried UNscaled here:
-//                       harmonics 2 .. 2H of every (sample, frequency) follow from them by the Chebyshev recurrence
-//                       x[m+1] = 2 cos(theta) x[m] - x[m-1], and 6H running sums per frequency take one fma each:
-//                       C_m = sum w cos(m theta), S_m = sum w sin(m theta), m = 1 .. 2H; YC_h = sum w y cos(h theta),
-//                       YS_h = sum w y sin(h theta), h = 1 .. H.  The product-to-sum rules turn them into M and b, and
-//                       an unrolled Cholesky in registers is the epilogue: only power[nf] is written.
+//   mhgls_scan_kernel   one stretch [0, n) of scan_stretch (gls_sums.h): each thread owns K consecutive frequencies,
+//                       the records come through the scalar cache, the seed of a (sample, thread) is one
+//                       plane rotation of two LDS table entries built per 64-sample chunk from exact cycle reductions,
+//                       and a rotation plus the three-term recurrence walk the K frequencies.  (sin, cos) are carried
+//                       UNscaled here: harmonics 2 .. 2H of every (sample, frequency) follow from them by
+//                       harmonic_ladder, and add_fourier_sums keeps the 6H running sums per frequency, one fma each
+//                       (harmonic_sums.h).  Epilogue, from the same header: fourier_entry turns the sums into M by the
+//                       product-to-sum rules and cholesky_quadratic, unrolled in registers, into b^T M^-1 b: only
+//                       power[nf] is written.
 //
 // One workgroup per tile of 256 K frequencies streams the whole curve (as the MODE_TREND instances of gls.hip do); no
 // sample parts, no balanced pieces, one device.
 #include "pdc_internal.h"
-#include "gls_sums.h"
+#include "harmonic_sums.h"
 
 #include <cmath>
 
@@ -60,12 +60,7 @@ __global__ __launch_bounds__(kPrepBlock) void mhgls_prep_kernel(MhPrepArgs a) {
     double W, ybar;
     weights_and_mean<kPrepBlock>(a.y, a.dy, a.n, a.fit_mean, red, W, ybar);
     double yy = 0.0, wsum = 0.0, y1 = 0.0;
-    for (int64_t i = tid; i < a.n + 2; i += kPrepBlock) {
-        double2 *r = reinterpret_cast<double2 *>(a.rec + i * 6);
-        if (i >= a.n) {   // the read-ahead records: finite, never accumulated
-            r[0] = r[1] = r[2] = make_double2(0.0, 0.0);
-            continue;
-        }
+    for (int64_t i = tid; i < a.n; i += kPrepBlock) {
         const double tp = a.t[i] - t0;
         const double w = inv_var(a.dy, i) / W;
         const double yc = a.y[i] - ybar;
@@ -75,6 +70,7 @@ __global__ __launch_bounds__(kPrepBlock) void mhgls_prep_kernel(MhPrepArgs a) {
         y1 += wy;
         put_record(a.rec + i * 6, wy, w, a.delta, tp);
     }
+    put_spare_records(a.rec, a.n, tid);
     yy = block_sum<kPrepBlock>(yy, red);
     wsum = block_sum<kPrepBlock>(wsum, red);
     y1 = block_sum<kPrepBlock>(y1, red);
@@ -86,59 +82,10 @@ __global__ __launch_bounds__(kPrepBlock) void mhgls_prep_kernel(MhPrepArgs a) {
     }
 }
 
-// ---- epilogue: b^T M^-1 b by an unrolled Cholesky (as bglst_loglik in gls.hip does it for 4 x 4) ----------------------
-// Basis order (cos th, sin th, ..., cos H th, sin H th, 1): the constant comes LAST, so the model without a floating
-// mean is the same factorisation stopped one column early.  Cs[m] = sum w cos(m th), Ss[m] = sum w sin(m th) for
-// m = 0 .. 2H (Cs[0] = sum w, Ss[0] = 0); b = {YC_1, YS_1, ..., YC_H, YS_H, sum w y}.
-// Entry (r, c), r >= c, of M by the product-to-sum rules.
-template <int H>
-__device__ __forceinline__ double mh_entry(const double (&Cs)[2 * H + 1], const double (&Ss)[2 * H + 1], int r, int c) {
-    const int hc = c / 2 + 1;
-    if (r == 2 * H) return c == 2 * H ? Cs[0] : ((c & 1) ? Ss[hc] : Cs[hc]);
-    const int hr = r / 2 + 1;
-    if ((r & 1) == (c & 1)) {
-        const double far = Cs[hr + hc], near = Cs[hr - hc];
-        return (r & 1) ? 0.5 * (near - far) : 0.5 * (near + far);
-    }
-    // sin(hr th) cos(hc th) = (sin((hr + hc) th) + sin((hr - hc) th)) / 2;  cos(hr th) sin(hc th): minus
-    return (r & 1) ? 0.5 * (Ss[hr + hc] + Ss[hr - hc]) : 0.5 * (Ss[hr + hc] - Ss[hr - hc]);
-}
-
-// A pivot that is not > 0, or is not finite, makes the bin NaN (the fit is singular there to rounding).
-template <int H>
-__device__ __forceinline__ double mh_quadratic(const double (&Cs)[2 * H + 1], const double (&Ss)[2 * H + 1],
-                                               const double (&b)[2 * H + 1], int fit_mean) {
-    constexpr int D = 2 * H + 1;
-    double L[D][D], z[D];
-    double quad = 0.0;
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        if (j < D - 1 || fit_mean) {
-            double d = mh_entry<H>(Cs, Ss, j, j);
-#pragma unroll
-            for (int q = 0; q < j; ++q) d -= L[j][q] * L[j][q];
-            bad = bad || !(d > 0.0) || !(d < HUGE_VAL);
-            const double inv = 1.0 / __builtin_sqrt(d);
-            double zj = b[j];
-#pragma unroll
-            for (int q = 0; q < j; ++q) zj -= L[j][q] * z[q];
-            z[j] = zj * inv;
-            quad += z[j] * z[j];
-#pragma unroll
-            for (int i = j + 1; i < D; ++i) {
-                double v = mh_entry<H>(Cs, Ss, i, j);
-#pragma unroll
-                for (int q = 0; q < j; ++q) v -= L[i][q] * L[j][q];
-                L[i][j] = v * inv;
-            }
-        }
-    }
-    return bad ? __builtin_nan("") : quad;
-}
-
 // ---- the scan -----------------------------------------------------------------------------------------------------
 // H = harmonics, K = trial frequencies per thread: 6 H K accumulators (12 H K VGPRs).
+// Epilogue: basis order (cos th, sin th, ..., cos H th, sin H th, 1).  The constant comes LAST, so the model without a
+// floating mean is the same factorisation stopped one column early; b = {YC_1, YS_1, ..., YC_H, YS_H, sum w y}.
 template <int H, int K>
 __global__ __launch_bounds__(kBlock) void mhgls_scan_kernel(MhArgs a) {
     constexpr int COLS = kBlock / 64;   // 64-lane columns of the tile
@@ -146,11 +93,8 @@ __global__ __launch_bounds__(kBlock) void mhgls_scan_kernel(MhArgs a) {
     // offset) | {sin, cos}(b Theta), b < 8
     __shared__ double2 tab[kChunk + 1][COLS * 8 + 8 + 1];   // + 1: rows start 16 B apart modulo 128 B (bank spread)
 
-    // Workgroup p runs on XCD p % 8 (observed dispatch rule, used for speed only): a contiguous run of tiles per XCD.
-    const int64_t per_xcd = (a.tiles + 7) / 8;
-    const int64_t tile = (int64_t)(blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
+    const int64_t tile = xcd_tile(blockIdx.x, a.tiles);
     if (tile >= a.tiles) return;
-
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int col = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -172,70 +116,31 @@ __global__ __launch_bounds__(kBlock) void mhgls_scan_kernel(MhArgs a) {
     }
 
     const int slot_a = col * 8 + (lane >> 3), slot_b = COLS * 8 + (lane & 7);
-    for (int64_t base = 0; base < n; base += kChunk) {
-        __syncthreads();   // everyone is done with the previous chunk's tables
-        if (tid < 2 * kChunk) {   // rotation tables, two threads per sample; (sin, cos) unscaled
-            const int il = tid >> 1;
-            // (rows past the end of the curve are never accumulated; they only need finite input)
-            const double tp = base + il < n ? a.rec[(base + il) * 6 + 5] : 0.0;
-            fill_rotation_tables<COLS>(tab[il], tid & 1, tp, kdelta, f_tile, 1.0);
-        }
-        __syncthreads();
-        const int cnt = (int)((n - base) < kChunk ? (n - base) : kChunk);
-        // (the read-ahead touches one record past the curve - the prologue wrote it - and the padding row of the table)
-        const double *rec = a.rec + base * 6;
-        two_set_pipeline(
-            0, cnt, [&](const int i) { return fetch_sample(tab, rec, i, slot_a, slot_b); },
-            [&](const Ahead &h) {
-                const double wy = h.r[0], w = h.r[1];
-                walk_grid<K>(rot2(h.qa, h.qt), h.r[2], h.r[3], h.cd2, [&](const int k, const double s, const double c) {
-                    // harmonics of this (sample, frequency): Chebyshev recurrence on the unscaled (sin, cos)
-                    const double c2 = c + c;
-                    double sm = s, cm = c, sl = 0.0, cl = 1.0;   // harmonic m and m - 1
-#pragma unroll
-                    for (int m = 1; m <= 2 * H; ++m) {
-                        Cm[m - 1][k] = __builtin_fma(w, cm, Cm[m - 1][k]);
-                        Sm[m - 1][k] = __builtin_fma(w, sm, Sm[m - 1][k]);
-                        if (m <= H) {
-                            YC[m - 1][k] = __builtin_fma(wy, cm, YC[m - 1][k]);
-                            YS[m - 1][k] = __builtin_fma(wy, sm, YS[m - 1][k]);
-                        }
-                        if (m < 2 * H) {
-                            const double cn = __builtin_fma(c2, cm, -cl), sn = __builtin_fma(c2, sm, -sl);
-                            cl = cm;
-                            sl = sm;
-                            cm = cn;
-                            sm = sn;
-                        }
-                    }
-                });
-            });
-    }
+    scan_stretch<kChunk, K>(
+        tab, a.rec, n, 0, n, tid, slot_a, slot_b,
+        [&](double2 *row, const int64_t i, const bool real) {   // (sin, cos) unscaled
+            fill_rotation_tables<COLS>(row, tid & 1, real ? a.rec[i * 6 + 5] : 0.0, kdelta, f_tile, 1.0);
+        },
+        [&](const Ahead &h, const int k, const double s, const double c) {
+            add_fourier_sums<H, K>(Cm, Sm, YC, YS, k, h.r[1], h.r[0], s, c);
+        });
 
     const double YY = a.scal[0], Wsum = a.scal[1], Werr = a.scal[2], Y1 = a.scal[3];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const int64_t j = jl + k;
         if (j < a.nf) {
-            double Cs[2 * H + 1], Ss[2 * H + 1], b[2 * H + 1];
-            Cs[0] = Wsum;
-            Ss[0] = 0.0;
-#pragma unroll
-            for (int m = 1; m <= 2 * H; ++m) {
-                Cs[m] = Cm[m - 1][k];
-                Ss[m] = Sm[m - 1][k];
-            }
-#pragma unroll
-            for (int h = 0; h < H; ++h) {
-                b[2 * h] = YC[h][k];
-                b[2 * h + 1] = YS[h][k];
-            }
+            constexpr int D = 2 * H + 1;
+            double Cs[D], Ss[D], b[D];
+            gather_fourier_sums<H, K>(Cm, Sm, YC, YS, k, Wsum, Cs, Ss, b);
             b[2 * H] = Y1;
-            double p = mh_quadratic<H>(Cs, Ss, b, a.fit_mean);
-            // the two normalisations of GLS (gls_epilogue.h)
-            if (a.psd) p *= 0.5 * Werr;
-            else p /= YY;
-            a.power[j] = p;
+            const double quad = cholesky_quadratic<D>(
+                [&](const int r, const int c) {   // the constant's row: sum w cos / sin (h th), then sum w
+                    if (r < 2 * H) return fourier_entry<H>(Cs, Ss, r, c);
+                    return c == 2 * H ? Cs[0] : ((c & 1) ? Ss[c / 2 + 1] : Cs[c / 2 + 1]);
+                },
+                b, a.fit_mean ? D : D - 1);
+            a.power[j] = normalised_power(quad, a.psd, Werr, YY);
         }
     }
 }
