@@ -1,8 +1,8 @@
 // The sample loop of pdm_scan_kernel - included, textually, in its body and in pdm_ragged_scan_kernel's so that
 // both bin the samples with the SAME code: stage [s_begin, s_end) of a.t / a.x through LDS, add every sample to
 // this thread's private histogram of its trial period, then (SPLIT > 1) fold the parts into part 0 in a fixed
-// order.  Names expected in scope: a (.t, .x), s_begin, s_end, mean, period, rp, dm0, thr, m0, mag, nbins, ncw,
-// stage, hsum, hcnt, edge, tid, part, q_over, q_nan and the template parameters BLOCK, SPLIT, KIND, CE, GL.
+// order.  Names it reads from the including body: a (.t, .x), s_begin, s_end, mean, period, rp, dm0, thr, m0, mag,
+// nbins, ncw, stage, hsum, hcnt, edge, tid, part, q_over, q_nan and the template parameters BLOCK, SPLIT, KIND, CE, GL.
     for (int64_t base = s_begin; base < s_end; base += kChunk) {
         __syncthreads();
         for (int i = tid; i < kChunk; i += BLOCK) {

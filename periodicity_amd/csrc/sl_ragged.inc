@@ -1,6 +1,7 @@
 // StringLength over a batch of light curves that each keep their OWN period grid ("ragged" grids):
-// StringLength.batch.  Included at the end of stringlength.hip: it needs the fast:: / duo:: / onecycle:: helpers,
-// sl_ranges.inc, sl_duo_body.inc and the single call's host ladder (stringlength_scan_impl, launch_fast_for).
+// StringLength.batch.  Included at the end of stringlength.hip: it needs sl_period.h (duo_period, is_one_cycle,
+// onecycle_sum, prep_sample: the functions the single call's kernels call), sl_p1.inc, the duo:: layout and the
+// single call's host ladder (stringlength_scan_impl, launch_fast_for).
 //
 // Every curve's trial periods are 1 / np.linspace(count * s, s, count), s = dphi / baseline_b (phase.py:
 // _string_periods): curve b owns samples [offsets[b], offsets[b+1]) and the periods 1 / linspace(start[b], stop[b],
@@ -11,17 +12,19 @@
 //   sl_ragged_periods_kernel  one thread per (curve, period): 1.0 / (j * step + start), exactly 1.0 / stop at the
 //                             last index - numpy's linspace rule (the unit is built with -ffp-contract=off), then an
 //                             IEEE division, as 1 / np.linspace(...) computes the single call's periods.
-//   sl_ragged_prep_kernel     one workgroup per curve: the AoS (t, m) records and the |t| flag of sl_prep_kernel and the
-//                             bad[0..1] words of sl_tame_kernel (OR reductions: any order gives the same words).
-//   sl_ragged_mark_kernel     one thread per (curve, period): sl_onecycle_mark_kernel's test with that curve's words.
-//   sl_ragged_onecycle_kernel one 1024-thread workgroup per listed (curve, period): sl_onecycle_kernel's sum, the same
-//                             reduction shape (so the same bits).
+//   sl_ragged_prep_kernel     one workgroup per curve: prep_sample, as sl_prep_kernel and sl_tame_kernel call it - the AoS
+//                             (t, m) records, the |t| flag and the bad[0..1] words (OR reductions: any order gives the
+//                             same words).
+//   sl_ragged_mark_kernel     one thread per (curve, period): is_one_cycle, as sl_onecycle_mark_kernel calls it, with
+//                             that curve's words.
+//   sl_ragged_onecycle_kernel one 1024-thread workgroup per listed (curve, period): onecycle_sum<1024>, as
+//                             sl_onecycle_kernel calls it (one reduction shape, so the same bits).
 //   sl_duo_ragged_kernel      persistent; the ticket counts (curve, period) items in a dispatch-order prefix table,
 //                             costliest curve first (ragged_order); a workgroup finds its curve by a scalar binary
-//                             search and runs sl_duo_body.inc - the text of sl_duo_kernel's period - on that curve's
-//                             slices.  One launch per instance the single call would pick (<16, 256, 512>, <16>,
-//                             <36>, <52>): P3c adds range lengths r = tid, tid + kB, ..., so the block size decides the
-//                             summation order.  A marked period increments its curve's counter.
+//                             search and runs sl_duo_kernel's period - sl_p1.inc, then duo_period - on a DuoCurve of
+//                             that curve's slices.  One launch per instance the single call would pick (<16, 256, 512>,
+//                             <16>, <36>, <52>): P3c adds range lengths r = tid, tid + kB, ..., so the block size decides
+//                             the summation order.  A marked period increments its curve's counter.
 // Then the host reads the B counters and runs launch_fast_for<false> on the slices of every curve with marks; curves
 // the duo kernel does not take (N > kCapD, N = 0, or knobs that move the single call off it) run
 // stringlength_scan_impl on their slices, with the hints the host entry would compute.  Every value is therefore the
@@ -87,19 +90,10 @@ __global__ __launch_bounds__(kPrepBlock) void sl_ragged_prep_kernel(Args a) {
     __syncthreads();
     const int64_t off = a.offsets[b], n = a.offsets[b + 1] - off;
     const double *t = a.t + off, *m = a.m + off;
-    bool mine = false, unsorted = false;
-    for (int64_t i = threadIdx.x; i < n; i += kPrepBlock) {
-        const double tv = t[i];
-        fast::rec_t v;
-        v.x = tv;
-        v.y = m[i];
-        a.rec[off + i] = v;
-        const double at = __builtin_fabs(tv);
-        mine = mine || !(at == 0.0 || (at >= 1e-150 && at <= 1e150));
-        unsorted = unsorted || (i > 0 && !(t[i - 1] <= tv));   // (NaN counts as unsorted)
-    }
-    if (mine) atomicOr(&words[0], 1u);
-    if (unsorted) atomicOr(&words[1], 1u);
+    fast::PrepFlags f;
+    for (int64_t i = threadIdx.x; i < n; i += kPrepBlock) fast::prep_sample(t, m, i, a.rec + off, f);
+    if (f.wild) atomicOr(&words[0], 1u);
+    if (f.unsorted) atomicOr(&words[1], 1u);
     __syncthreads();
     if (threadIdx.x == 0) {
         a.flags[b] = words[0] ? 0u : 1u;
@@ -116,15 +110,7 @@ __global__ __launch_bounds__(256) void sl_ragged_mark_kernel(Args a) {
     bool one = false;
     if (a.route[b] < kLong) {
         const int64_t off = a.offsets[b], n = a.offsets[b + 1] - off;
-        const unsigned *bad = a.bad + 2 * b;
-        if (bad[1] == 0u && n >= 2) {   // (sl_onecycle_mark_kernel, statement for statement)
-            const double period = a.periods[q];
-            const double y = 1.0 / period;
-            const bool safe = period_is_safe(period, bad[0] == 0u);
-            const double q0 = exact_quotient(a.t[off], period, y, safe), q1 = exact_quotient(a.t[off + n - 1], period, y, safe);
-            const double c0 = __builtin_floor(q0), c1 = __builtin_floor(q1);
-            one = period > 0.0 && (c1 - c0 == 0.0 || (c1 - c0 == 1.0 && q1 - c1 < q0 - c0));
-        }
+        one = is_one_cycle(a.t + off, n, a.periods[q], a.bad[2 * b], a.bad[2 * b + 1]);
     }
     a.skip[q] = one ? 1 : 0;
     if (one) a.list[atomicAdd(a.count, 1u)] = (unsigned)q;
@@ -133,30 +119,15 @@ __global__ __launch_bounds__(256) void sl_ragged_mark_kernel(Args a) {
 __global__ __launch_bounds__(kBlock) void sl_ragged_onecycle_kernel(Args a) {
     using namespace fast;
     __shared__ double red[kBlock / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned count = *a.count;
     for (unsigned k = blockIdx.x; k < count; k += gridDim.x) {   // (workgroup-uniform)
         const int64_t q = a.list[k];
         const int64_t b = curve_of(a.poff, a.n_curves, q);
         const int64_t off = a.offsets[b], n = a.offsets[b + 1] - off;
-        const double *t = a.t + off, *m = a.m + off;
         const double period = a.periods[q];
-        const double y = 1.0 / period;
         const bool safe = period_is_safe(period, a.bad[2 * b] == 0u);
-        double acc = 0.0;
-        for (int64_t i = tid + 1; i < n; i += kBlock) {          // segment (i - 1, i)
-            const double p1 = fast_phase(t[i], period, y, safe), p0 = fast_phase(t[i - 1], period, y, safe);
-            acc += short_hypot(m[i] - m[i - 1], p1 - p0);
-        }
-        acc = wave_sum_fixed(acc);
-        if (lane == 0) red[wave] = acc;
-        __syncthreads();
-        if (tid == 0) {
-            double total = 0.0;
-            for (int x = 0; x < kBlock / 64; ++x) total += red[x];
-            total += hypot(m[0] - m[n - 1], fast_phase(t[0], period, y, safe) - fast_phase(t[n - 1], period, y, safe));
-            a.ell[q] = total;
-        }
+        const double total = onecycle_sum<kBlock>(a.t + off, a.m + off, n, period, safe, red);
+        if (threadIdx.x == 0) a.ell[q] = total;
         __syncthreads();
     }
 }
@@ -192,34 +163,20 @@ struct RaggedDuoArgs {
     int64_t nr_pad;
 };
 
-// sl_duo_kernel over the (curve, period) items of every curve of one instance; the period body is the same text
+// sl_duo_kernel over the (curve, period) items of every curve of one instance: the same duo_period, on the curve of
+// the ticket
 template <int KMAX, int BLK = duo::kB, int NBL = kNB>
 __global__ __launch_bounds__(BLK, 4) void sl_duo_ragged_kernel(RaggedDuoArgs ra) {
-    constexpr int kB = BLK, kW = BLK / 64;
-    constexpr int kDCap = BLK >= 512 ? ::kDCap : 1024;
-    static_assert(kW * kWaveB >= (NBL + 64) * 4 && kW * kWaveB >= kDCap * 10, "aliases must fit");
-    typedef unsigned short IdxT;
+    using L = View<BLK>;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    unsigned char *wbuf = lds_raw;
-    unsigned *hist = reinterpret_cast<unsigned *>(lds_raw);
-    unsigned long long *bkeys = reinterpret_cast<unsigned long long *>(lds_raw);
-    IdxT *bidx = reinterpret_cast<IdxT *>(bkeys + kDCap);
-    unsigned short *bndb = reinterpret_cast<unsigned short *>(lds_raw + kW * kWaveB);
-    unsigned short *bnds = bndb + kRangesD + 8;
-    unsigned *defer = reinterpret_cast<unsigned *>(bnds + kRangesD + 8);
-    IdxT *order = reinterpret_cast<IdxT *>(defer + 16);
-    __shared__ unsigned wave_tot[kW];
-    __shared__ double red[kW];
+    __shared__ unsigned wave_tot[BLK / 64];
+    __shared__ double red[BLK / 64];
     __shared__ unsigned s_item, s_bad;
     const int tid0 = threadIdx.x, lane = tid0 & 63, wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
-    double *rsum = ra.rsum + (int64_t)blockIdx.x * ra.nr_pad * 4;
-    int *rcnt = ra.rcnt + (int64_t)blockIdx.x * ra.nr_pad;
-    double *rlen = ra.rlen + (int64_t)blockIdx.x * ra.nr_pad;
+    const L v = L::carve(lds_raw, wave);
+    const RangeScratch rs = {ra.rsum + (int64_t)blockIdx.x * ra.nr_pad * 4, ra.rcnt + (int64_t)blockIdx.x * ra.nr_pad,
+                             ra.rlen + (int64_t)blockIdx.x * ra.nr_pad};
     const unsigned n_items = (unsigned)ra.opre[ra.mc];
-
-    unsigned long long *keys_w = reinterpret_cast<unsigned long long *>(wbuf + wave * kWaveB);
-    unsigned *fine_w = reinterpret_cast<unsigned *>(wbuf + wave * kWaveB + kRCap * 8);
-    IdxT *idx_w = reinterpret_cast<IdxT *>(wbuf + wave * kWaveB + kRCap * 8 + (kWFine + 4) * 4);
 
     for (;;) {
         __syncthreads();   // the previous item is done with LDS
@@ -241,17 +198,21 @@ __global__ __launch_bounds__(BLK, 4) void sl_duo_ragged_kernel(RaggedDuoArgs ra)
         const int64_t p = (int64_t)item - ra.opre[lo];
         const int64_t off = ra.offsets[curve], po = ra.poff[curve];
         if (ra.skip[po + p]) continue;   // (workgroup-uniform)
-        const int n = (int)(ra.offsets[curve + 1] - off);
-        const bool t_safe = ra.flags[curve] != 0u;
-        unsigned *const marked = ra.marked + curve;
-        const struct {
-            const double *t, *m, *periods;
-            const rec_t *rec;
-            double *ell;
-            unsigned char *todo;
-            int64_t n;
-        } a{ra.t + off, ra.m + off, ra.periods + po, ra.rec + off, ra.ell + po, ra.todo + po, n};   // (the names the body reads)
-#include "sl_duo_body.inc"
+        const DuoCurve c = {ra.t + off, ra.m + off, ra.rec + off, ra.periods + po, ra.ell + po, ra.todo + po,
+                            (int)(ra.offsets[curve + 1] - off), ra.flags[curve] != 0u, ra.marked + curve};
+        const int n = c.n;
+        const double period = c.periods[p];
+        const double y = 1.0 / period;
+        const bool safe = period_is_safe(period, c.t_safe);
+        int tid = tid0;   // (opaque copy, once per period: addresses built from it are not hoisted out of the ticket loop and spilled)
+        asm volatile("" : "+v"(tid));
+        unsigned pk[(KMAX + 1) / 2];
+        {   // (P1 is text in the kernel body: sl_p1.inc says why)
+            constexpr int P1_BLK = BLK, P1_NB = NBL;
+            const double *const p1_t = c.t;
+#include "sl_p1.inc"
+        }
+        duo_period<KMAX, BLK, NBL>(c, p, period, y, safe, tid, pk, v, rs, red, &s_bad, lane, wave);
     }
 }
 
@@ -305,8 +266,7 @@ SlRaggedLayout slr_layout(int64_t B, int64_t n_total, int64_t p_total, int64_t n
 
 template <int KMAX, int BLK = duo::kB, int NBL = fast::kNB>
 int launch_duo_ragged(const duo::RaggedDuoArgs &a, int n_max, int64_t grid, hipStream_t st) {
-    const size_t fixed = (size_t)(BLK / 64) * duo::kWaveB + 2 * (duo::kRangesD + 8) * 2 + 64;
-    const size_t lds = fixed + (size_t)((n_max + 64 + 7) & ~7) * 2;
+    const size_t lds = duo::View<BLK>::bytes(n_max);
     PDC_TRY(allow_dynamic_lds((const void *)duo::sl_duo_ragged_kernel<KMAX, BLK, NBL>, duo::kLdsWg - duo::kStaticD));
     hipLaunchKernelGGL((duo::sl_duo_ragged_kernel<KMAX, BLK, NBL>), dim3((unsigned)grid), dim3(BLK), lds, st, a);
     return PDC_OK;

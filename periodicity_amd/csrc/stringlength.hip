@@ -36,6 +36,12 @@
 //        larger than a whole slice is gathered straight into the global scratch.
 //   P3c  links between consecutive ranges and the closing segment, from the summaries.
 // Nothing but t[], m[] (read) and ell[p] (written) touches global memory on the common path.
+//
+// Files: sl_period.h - the phases of a period as functions (LDS view, P2, range table, P3a, the LDS sort of P3b,
+// P3c, duo_period, the one-cycle and prep bodies), called by the kernels here and in sl_ragged.inc; sl_p1.inc and
+// sl_p3a.inc - P1 and P3a's lambdas as text, for the kernel bodies that lose time when they call them; this file - the
+// kernels (sl_scan_kernel, fast::, duo::, stream::, onecycle::), the switches and the host ladder; timesort.inc,
+// supersmoother.inc, sl_ragged.inc - included below.
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -47,32 +53,7 @@ using namespace pdc;
 
 namespace {
 
-constexpr int kBuckets = 2048;       // coarse buckets over [0, 1]
-constexpr int kBucketsLarge = 8192;  // ... for N >= 65536, so that a bucket still fits a wave's range
-constexpr int kBlock = 1024;
-constexpr int kWaves = kBlock / 64;
-constexpr int kWin = 192;        // sorted positions per range window
-constexpr int kRCap = 256;       // samples a wave sorts by itself (4 per lane)
-constexpr int kRPer = kRCap / 64;
-constexpr int kWFine = 256;      // fine buckets per wave range
-constexpr int kCPL = kWFine / 64; // fine counters per lane (multiple of 4)
-constexpr int kWInsertMax = 16;  // fullest fine bucket the predecessor-counting finish accepts
-constexpr int kDCap = 2048;      // workgroup-level (deferred) LDS sort capacity
-constexpr int kMaxRanges = 1024; // ranges per slice
-constexpr int kMaxGrid = 1024;
-constexpr int kLdsTotal = 163840;
-
-template <typename IdxT>
-struct Lds {
-    // per wave: keys u64[kRCap] | fine u32[kWFine + 4] | idx IdxT[kRCap]
-    static constexpr int wave_bytes = ((kRCap * 8 + (kWFine + 4) * 4 + kRCap * (int)sizeof(IdxT)) + 15) & ~15;
-    // the coarse histogram is only alive in P1/P2 and the wave scratch only in P3: they share LDS
-    static constexpr int fixed = kWaves * wave_bytes + (kMaxRanges + 8) * 4 + 128;
-    static constexpr int capacity = (kLdsTotal - fixed - 1024) / (int)sizeof(IdxT);  // slice size
-    static_assert(kWaves * wave_bytes >= kDCap * (8 + (int)sizeof(IdxT)), "deferred sort must fit");
-    static_assert(capacity / kWin + 1 <= kMaxRanges, "range table too small");
-    static_assert(capacity < 65536, "slice positions are stored as 16-bit offsets");
-};
+#include "sl_period.h"
 
 struct SlArgs {
     const double *t, *m, *periods;
@@ -110,102 +91,6 @@ __device__ __forceinline__ int coarse_bucket(double t, double period, double rp,
     const int b = (int)u;
     if (__builtin_fabs((u - (double)b) - 0.5) < thr) return b;
     return scaled_index(fold_phase(t, period), (double)NB, NB - 1);
-}
-
-// LDS traffic between lanes of ONE wave: order the accesses without a workgroup barrier.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Exclusive prefix sum of a[0..NB) in place (NB / BLOCK entries per thread); returns the total.
-template <int NB, int BLOCK = kBlock>
-__device__ __forceinline__ unsigned scan_buckets(unsigned *a, unsigned *wave_tot) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int per = NB / BLOCK;
-    static_assert(per * BLOCK == NB, "bucket count must be a multiple of the block size");
-    unsigned local[per], sum = 0;
-#pragma unroll
-    for (int e = 0; e < per; ++e) {
-        local[e] = a[tid * per + e];
-        sum += local[e];
-    }
-    unsigned incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += up;
-    }
-    __syncthreads();
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    unsigned run = incl - sum, all = 0u;
-#pragma unroll
-    for (int w = 0; w < BLOCK / 64; ++w) {
-        if (w < wave) run += wave_tot[w];
-        all += wave_tot[w];
-    }
-#pragma unroll
-    for (int e = 0; e < per; ++e) {
-        a[tid * per + e] = run;
-        run += local[e];
-    }
-    __syncthreads();
-    return all;
-}
-
-// Ascending bitonic sort of P (power of two) (key, index) pairs by (key, index), whole workgroup.
-template <typename IdxT, typename KeyPtr, typename IdxPtr>
-__device__ __forceinline__ void bitonic_sort(KeyPtr K, IdxPtr I, int P) {
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int c = threadIdx.x; c < (P >> 1); c += (int)blockDim.x) {
-                const int i = ((c & ~(j - 1)) << 1) | (c & (j - 1));
-                const int l = i | j;
-                const unsigned long long ka = K[i], kb = K[l];
-                const IdxT ia = I[i], ib = I[l];
-                const bool up = (i & k) == 0;
-                const bool a_gt_b = ka > kb || (ka == kb && ia > ib);
-                if (a_gt_b == up) {
-                    K[i] = kb;
-                    K[l] = ka;
-                    I[i] = ib;
-                    I[l] = ia;
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// Sum of hypot(dm, dphi) over consecutive sorted points j-1 -> j, j in [1, cnt), whole workgroup.
-template <typename KeyPtr, typename IdxPtr>
-__device__ __forceinline__ double segment_sum(KeyPtr K, IdxPtr I, int cnt, const double *m) {
-    const int lane = threadIdx.x & 63;
-    double total = 0.0;
-    for (int j0 = 0; j0 < cnt; j0 += (int)blockDim.x) {
-        const int j = j0 + threadIdx.x;
-        const bool live = j < cnt;
-        double phi = 0.0, mm = 0.0;
-        if (live) {
-            phi = __longlong_as_double((long long)K[j]);
-            mm = m[I[j]];
-        }
-        double pphi = __shfl_up(phi, 1, 64);
-        double pm = __shfl_up(mm, 1, 64);
-        bool ok = live;
-        if (lane == 0 && live) {
-            if (j > 0) {
-                pphi = __longlong_as_double((long long)K[j - 1]);
-                pm = m[I[j - 1]];
-            } else {
-                ok = false;
-            }
-        }
-        if (ok) total += hypot(mm - pm, phi - pphi);
-    }
-    return total;
 }
 
 template <typename IdxT, int NB>
@@ -615,34 +500,20 @@ __global__ __launch_bounds__(kBlock) void sl_scan_kernel(SlArgs a) {
             __syncthreads();
 
             // ---- P3b: deferred ranges, whole workgroup ---------------------------------------------
+            auto key_of = [&](double tv) { return (unsigned long long)__double_as_longlong(fold_phase(tv, period)); };
             for (int w32 = 0; w32 < (nranges + 31) / 32; ++w32) {
                 unsigned bits = defer[w32];
                 while (bits) {
                     const int r = w32 * 32 + __builtin_ctz(bits);
                     bits &= bits - 1;
                     const int s_lo = bnds[r], cnt = (int)bnds[r + 1] - s_lo;
-                    int P = 2;
-                    while (P < cnt) P <<= 1;
-                    double p0, m0, p1, m1;
+                    double ends[4];
                     if (cnt <= kDCap) {
-                        for (int s = tid; s < P; s += kBlock) {
-                            if (s < cnt) {
-                                const IdxT id = order[s_lo + s];
-                                bkeys[s] = (unsigned long long)__double_as_longlong(fold_phase(a.t[id], period));
-                                bidx[s] = id;
-                            } else {
-                                bkeys[s] = ~0ull;
-                                bidx[s] = (IdxT)~0u;
-                            }
-                        }
-                        __syncthreads();
-                        bitonic_sort<IdxT>(bkeys, bidx, P);
-                        total += segment_sum(bkeys, bidx, cnt, a.m);
-                        p0 = __longlong_as_double((long long)bkeys[0]);
-                        m0 = a.m[bidx[0]];
-                        p1 = __longlong_as_double((long long)bkeys[cnt - 1]);
-                        m1 = a.m[bidx[cnt - 1]];
+                        total += fast::sort_deferred_lds<kBlock, false>(bkeys, bidx, fast::OrderPlain<IdxT>{order}, s_lo, cnt,
+                                                                        a.t, a.m, key_of, tid, nullptr, ends);
                     } else {
+                        int P = 2;
+                        while (P < cnt) P <<= 1;
                         for (int s = tid; s < P; s += kBlock) {
                             if (s < cnt) {
                                 const unsigned id = order[s_lo + s];
@@ -656,12 +527,12 @@ __global__ __launch_bounds__(kBlock) void sl_scan_kernel(SlArgs a) {
                         __syncthreads();
                         bitonic_sort<unsigned>(gk, gi, P);
                         total += segment_sum(gk, gi, cnt, a.m);
-                        p0 = __longlong_as_double((long long)gk[0]);
-                        m0 = a.m[gi[0]];
-                        p1 = __longlong_as_double((long long)gk[cnt - 1]);
-                        m1 = a.m[gi[cnt - 1]];
+                        ends[0] = __longlong_as_double((long long)gk[0]);
+                        ends[1] = a.m[gi[0]];
+                        ends[2] = __longlong_as_double((long long)gk[cnt - 1]);
+                        ends[3] = a.m[gi[cnt - 1]];
                     }
-                    if (tid == 0) write_summary(r_base + r, p0, m0, p1, m1, cnt);
+                    if (tid == 0) write_summary(r_base + r, ends[0], ends[1], ends[2], ends[3], cnt);
                     __syncthreads();
                 }
             }
@@ -672,32 +543,9 @@ __global__ __launch_bounds__(kBlock) void sl_scan_kernel(SlArgs a) {
         __syncthreads();  // every summary of this period (global, this workgroup's) is visible
 
         // ---- P3c: links between consecutive non-empty ranges + the closing segment ----------------
-        for (int r = tid; r < r_base; r += kBlock) {
-            if (rcnt[r] > 0) {
-                int q = r - 1;
-                while (q >= 0 && rcnt[q] == 0) --q;
-                if (q >= 0)
-                    total += hypot(rsum[(int64_t)r * 4 + 1] - rsum[(int64_t)q * 4 + 3],
-                                   rsum[(int64_t)r * 4 + 0] - rsum[(int64_t)q * 4 + 2]);
-            }
-        }
-        if (tid == 0 && r_base > 0) {
-            int f0 = 0, l0 = r_base - 1;
-            while (f0 < r_base && rcnt[f0] == 0) ++f0;
-            while (l0 >= 0 && rcnt[l0] == 0) --l0;
-            // closing segment of np.roll(-1): first minus last, no phase wrap (phase.py:50)
-            if (f0 < r_base && l0 >= 0)
-                total += hypot(rsum[(int64_t)f0 * 4 + 1] - rsum[(int64_t)l0 * 4 + 3],
-                               rsum[(int64_t)f0 * 4 + 0] - rsum[(int64_t)l0 * 4 + 2]);
-        }
-        total = wave_sum(total);
-        if (lane == 0) red[wave] = total;
-        __syncthreads();
-        if (tid == 0) {
-            double sum = 0.0;
-            for (int w = 0; w < kWaves; ++w) sum += red[w];
-            a.ell[p] = sum;
-        }
+        // (the lengths inside the ranges are in `total` already: no rlen[])
+        const double sum = fast::links_and_total<kBlock, false>(total, rsum, rcnt, nullptr, r_base, tid, lane, wave, red);
+        if (tid == 0) a.ell[p] = sum;
         __syncthreads();
     }
 }
@@ -736,10 +584,6 @@ namespace fast {
 #ifndef PDC_SL_G2
 #define PDC_SL_G2 4
 #endif
-constexpr int kNB = kBuckets;
-constexpr int kFWin = 216;             // sorted positions per range window (a range = window + < one bucket)
-constexpr int kFCap = 255;             // samples a wave ranks by itself: counts and starts fit in bytes
-constexpr int kFine = 1024;            // fine buckets per range, 8-bit counters packed four to a word
 constexpr int kRanges = 320;           // >= capacity / kFWin + 2
 constexpr int kKMax = 52;              // samples per thread in P1/P2 (capacity <= kKMax * kBlock)
 constexpr int kNBLarge = kBucketsLarge; // coarse buckets of the several-slice instance (N above one slice)
@@ -749,7 +593,8 @@ constexpr int kLdsTotalDyn = kLdsTotal - kStatic;
 template <typename IdxT>
 struct FL {
     static constexpr int wave_bytes = Lds<IdxT>::wave_bytes;
-    static constexpr int fixed = kWaves * wave_bytes + 2 * (kRanges + 8) * 2 + 64;
+    using View = PeriodLds<IdxT, kWaves, wave_bytes, kRanges, kDCap>;
+    static constexpr int fixed = View::fixed;
     static constexpr int capacity = ((((kLdsTotal - fixed - kStatic) / (int)sizeof(IdxT)) & ~7) - 64);   // (+ 64 dummy slots)
 };
 constexpr int kCapacity = FL<unsigned short>::capacity;   // samples the one-slice instances take
@@ -758,15 +603,10 @@ constexpr int kCapacity17 = ((((kLdsTotal - FL<unsigned>::fixed - kStatic) * 8 /
 constexpr int kCapacity18 = ((((kLdsTotal - FL<unsigned>::fixed - kStatic) * 8 / 18) & ~31) - 64 - 32);
 static_assert(kCapacity17 < 65536 && kCapacity18 > 40000, "slice positions are 16-bit");
 static_assert(kCapacity / kFWin + 2 <= kRanges, "range table too small");
-static_assert(kFine + 16 <= (kWFine + 4) * 4, "byte counters live in the general kernel's counter area");
 static_assert(kCapacity <= kKMax * kBlock, "P1 keeps one bucket id per sample in registers");
 static_assert(kCapacity < 65536 && FL<unsigned>::capacity < 65536, "slice positions are 16-bit");
-static_assert(kWaves * FL<unsigned short>::wave_bytes >= (kNB + 64) * 4 && kWaves * FL<unsigned short>::wave_bytes >= kDCap * 10,
-              "aliases must fit");
-static_assert(kWaves * FL<unsigned>::wave_bytes >= kNBLarge * 4 && kWaves * FL<unsigned>::wave_bytes >= kDCap * 12,
-              "aliases must fit");
-
-typedef double rec_t __attribute__((ext_vector_type(2)));   // (t, m)
+// (the aliases of the wave scratch: PeriodLds checks the deferred sort, sl_p1.inc the one-slice histogram)
+static_assert(kWaves * FL<unsigned short>::wave_bytes >= kNBLarge * 4, "aliases must fit: the several-slice histogram");
 
 struct FastArgs {
     const double *t, *m, *periods;
@@ -789,136 +629,6 @@ struct FastArgs {
     rec_t *sorted;              // (EMIT instances) [n_periods][n]: every period's (phase, m) in sorted order
 };
 
-// RN(t / period) without the division: y = RN(1 / period); q0 = RN(t y) is within 1.5 ulp of the
-// quotient, one fma correction makes it faithful, and for a faithful q and a correctly rounded
-// reciprocal Markstein's theorem (IBM J. Res. Dev. 34, 1990; Muller et al., Handbook of
-// Floating-Point Arithmetic, "division with an FMA") says the second correction IS the correctly
-// rounded quotient.  The theorem needs no over/underflow and a divisor whose significand is not all
-// ones: `safe` (wave-uniform) says so, otherwise the IEEE division runs.
-__device__ __forceinline__ double exact_quotient(double t, double period, double y, bool safe) {
-    if (!safe) return t / period;
-    const double q0 = t * y;
-    const double r0 = __builtin_fma(-period, q0, t);
-    const double q1 = __builtin_fma(r0, y, q0);
-    const double r1 = __builtin_fma(-period, q1, t);
-    return __builtin_fma(r1, y, q1);
-}
-
-__device__ __forceinline__ bool period_is_safe(double period, bool t_safe) {
-    const double ap = __builtin_fabs(period);
-    const unsigned long long frac = (unsigned long long)__double_as_longlong(period) & 0xFFFFFFFFFFFFFull;
-    return t_safe && ap >= 1e-150 && ap <= 1e150 && frac != 0xFFFFFFFFFFFFFull;
-}
-
-// ((t - 0) / period) % 1 as numpy computes it (core.py:544); NaN when the quotient is not finite.
-__device__ __forceinline__ double fast_phase(double t, double period, double y, bool safe) {
-    const double q = exact_quotient(t, period, y, safe);
-    return q - __builtin_floor(q);
-}
-
-__device__ __forceinline__ unsigned long long phase_key(double phi) {
-    // monotone for phi in [0, 1]; every NaN gets one pattern, above all numbers, so that NaN phases
-    // keep their time order (stable sort)
-    return phi == phi ? (unsigned long long)__double_as_longlong(phi) : 0x7FF8000000000000ull;
-}
-
-template <int NB = kNB>
-__device__ __forceinline__ int coarse_of(double phi) {
-    const unsigned b = (unsigned)(phi * (double)NB);            // exact product; v_cvt_u32 saturates
-    const unsigned c = b < (unsigned)(NB - 1) ? b : (unsigned)(NB - 1);
-    return phi == phi ? (int)c : NB - 1;
-}
-
-// Wave-wide inclusive scan / maximum by DPP row shifts and row broadcasts (gfx9 encodings: row_shr:n =
-// 0x110 + n, row_bcast15 = 0x142, row_bcast31 = 0x143); no LDS permutes.  The maximum ends in lane 63.
-#define PDC_DPP(old, src, ctrl, rmask) \
-    (unsigned)__builtin_amdgcn_update_dpp((int)(old), (int)(src), (ctrl), (rmask), 0xf, false)
-__device__ __forceinline__ unsigned wave_scan_add(unsigned v) {
-    v += PDC_DPP(0u, v, 0x111, 0xf);
-    v += PDC_DPP(0u, v, 0x112, 0xf);
-    v += PDC_DPP(0u, v, 0x114, 0xf);
-    v += PDC_DPP(0u, v, 0x118, 0xf);
-    v += PDC_DPP(0u, v, 0x142, 0xa);
-    v += PDC_DPP(0u, v, 0x143, 0xc);
-    return v;
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {   // valid in lane 63 -> broadcast
-    unsigned u;
-    u = PDC_DPP(0u, v, 0x111, 0xf); v = u > v ? u : v;
-    u = PDC_DPP(0u, v, 0x112, 0xf); v = u > v ? u : v;
-    u = PDC_DPP(0u, v, 0x114, 0xf); v = u > v ? u : v;
-    u = PDC_DPP(0u, v, 0x118, 0xf); v = u > v ? u : v;
-    u = PDC_DPP(0u, v, 0x142, 0xa); v = u > v ? u : v;
-    u = PDC_DPP(0u, v, 0x143, 0xc); v = u > v ? u : v;
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-
-// Wave-wide sum of doubles in a FIXED order (the scan pattern above on both halves of the double; the
-// total ends in lane 63 and is broadcast): no LDS permutes on the critical path of a range.
-#define PDC_DPP_F64(v, ctrl, rmask)                                                                          \
-    __longlong_as_double(((long long)PDC_DPP(0u, (unsigned)(__double_as_longlong(v) >> 32), ctrl, rmask) << 32) | \
-                         (long long)PDC_DPP(0u, (unsigned)__double_as_longlong(v), ctrl, rmask))
-__device__ __forceinline__ double wave_sum_fixed(double v) {
-    v += PDC_DPP_F64(v, 0x111, 0xf);
-    v += PDC_DPP_F64(v, 0x112, 0xf);
-    v += PDC_DPP_F64(v, 0x114, 0xf);
-    v += PDC_DPP_F64(v, 0x118, 0xf);
-    v += PDC_DPP_F64(v, 0x142, 0xa);
-    v += PDC_DPP_F64(v, 0x143, 0xc);
-    const long long b = __double_as_longlong(v);
-    return __longlong_as_double(((long long)__builtin_amdgcn_readlane((int)(b >> 32), 63) << 32) |
-                                (unsigned)__builtin_amdgcn_readlane((int)b, 63));
-}
-
-// x of the lane below (lane 0: `first`), by DPP wave_shr:1 on both halves - no LDS permute
-__device__ __forceinline__ double lane_below(double x, double first) {
-    const long long xb = __double_as_longlong(x), fb = __double_as_longlong(first);
-    const int lo = __builtin_amdgcn_update_dpp((int)fb, (int)xb, 0x138, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(fb >> 32), (int)(xb >> 32), 0x138, 0xf, 0xf, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-
-__device__ __forceinline__ double read_lane(double x, int l) {   // l wave-uniform
-    const long long xb = __double_as_longlong(x);
-    const int lo = __builtin_amdgcn_readlane((int)xb, l), hi = __builtin_amdgcn_readlane((int)(xb >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-
-// sqrt(x^2 + y^2) for |x|, |y| <= ~1e150 whose squares do not underflow to a subnormal that matters:
-// here |dm| <= 0.5 and |dphi| <= 1.  rsq seed, one coupled Goldschmidt step, one Newton step.
-__device__ __forceinline__ double short_hypot(double x, double y) {
-    const double s = __builtin_fma(x, x, y * y);
-    const double r = __builtin_amdgcn_rsq(s);
-    const double g0 = s * r, h0 = 0.5 * r;
-    const double e0 = __builtin_fma(-h0, g0, 0.5);
-    const double g1 = __builtin_fma(g0, e0, g0), h1 = __builtin_fma(h0, e0, h0);
-    const double d1 = __builtin_fma(-g1, g1, s);
-    const double g2 = __builtin_fma(d1, h1, g1);
-    return (s > 0.0 && s < __builtin_inf()) ? g2 : s;        // 0, +inf and NaN pass through
-}
-
-// Four phases at once: ONE wave-uniform branch on `safe` per group, so that the four dependent fma
-// chains sit in one basic block and overlap.
-__device__ __forceinline__ void phases4(const double (&t)[4], double period, double y, bool safe,
-                                        double (&phi)[4]) {
-    double q[4];
-    if (safe) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const double q0 = t[u] * y;
-            const double r0 = __builtin_fma(-period, q0, t[u]);
-            const double q1 = __builtin_fma(r0, y, q0);
-            const double r1 = __builtin_fma(-period, q1, t[u]);
-            q[u] = __builtin_fma(r1, y, q1);
-        }
-    } else {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) q[u] = t[u] / period;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) phi[u] = q[u] - __builtin_floor(q[u]);
-}
-
 // MULTI = false: all samples fit one LDS slice (KMAX = samples per thread kept in registers between P1
 // and P2, 16-bit indices, NB = 2048).  MULTI = true (kCapacity < N <= 16 slices): one histogram pass over
 // all samples (rolled loop) gives the bucket starts and leaves every sample's bucket id in global scratch,
@@ -936,44 +646,32 @@ template <int KMAX, typename IdxT = unsigned short, int NB = kNB, bool MULTI = f
 __global__ __launch_bounds__(kBlock) void sl_fast_kernel(FastArgs a) {
     constexpr bool P17 = PL > 0;
     static_assert(PL >= 0 && PL <= 2 && (!P17 || (MULTI && sizeof(IdxT) == 4)), "the bit planes belong to the several-slice instance");
-    constexpr int kWaveBytes = FL<IdxT>::wave_bytes;
+    using L = typename FL<IdxT>::View;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    unsigned char *wbuf = lds_raw;                                                  // P3a: per-wave scratch
-    unsigned *hist = reinterpret_cast<unsigned *>(lds_raw);                         // P1/P2 alias [NB + 64]
-    unsigned long long *bkeys = reinterpret_cast<unsigned long long *>(lds_raw);    // P3b alias [kDCap]
-    IdxT *bidx = reinterpret_cast<IdxT *>(bkeys + kDCap);                           // P3b alias [kDCap]
-    unsigned short *bndb = reinterpret_cast<unsigned short *>(lds_raw + kWaves * kWaveBytes);
-    unsigned short *bnds = bndb + kRanges + 8;
-    unsigned *defer = reinterpret_cast<unsigned *>(bnds + kRanges + 8);             // [16]
-    IdxT *order = reinterpret_cast<IdxT *>(defer + 16);                             // [slice + 64]
-    unsigned short *order16 = reinterpret_cast<unsigned short *>(defer + 16);       // P17: low 16 bits per entry ...
-    const int plane_words = P17 ? (a.slice_cap + 64 + 31) / 32 : 0;                 // per plane
-    unsigned *plane = reinterpret_cast<unsigned *>(order16 + ((a.slice_cap + 64 + 7) & ~7));   // ... + bits 16 (, 17)
-    auto order_get = [&](int pos) -> unsigned {
-        if constexpr (P17) {
-            unsigned v = (unsigned)order16[pos] | (((plane[pos >> 5] >> (pos & 31)) & 1u) << 16);
-            if constexpr (PL > 1) v |= ((plane[plane_words + (pos >> 5)] >> (pos & 31)) & 1u) << 17;
-            return v;
-        } else {
-            return (unsigned)order[pos];
-        }
-    };
-#define PDC_ORDER_GET(pos) order_get(pos)
     __shared__ unsigned wave_tot[kWaves];
     __shared__ double red[kWaves];
     __shared__ unsigned s_fill;
     const int tid0 = threadIdx.x, lane = tid0 & 63, wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
+    const L v = L::carve(lds_raw, wave);
+    unsigned short *order16 = reinterpret_cast<unsigned short *>(v.order);          // P17: low 16 bits per entry ...
+    const int plane_words = P17 ? (a.slice_cap + 64 + 31) / 32 : 0;                 // per plane
+    unsigned *plane = reinterpret_cast<unsigned *>(order16 + ((a.slice_cap + 64 + 7) & ~7));   // ... + bits 16 (, 17)
+    auto order_get = [&](int pos) -> unsigned {
+        if constexpr (P17) {
+            unsigned x = (unsigned)order16[pos] | (((plane[pos >> 5] >> (pos & 31)) & 1u) << 16);
+            if constexpr (PL > 1) x |= ((plane[plane_words + (pos >> 5)] >> (pos & 31)) & 1u) << 17;
+            return x;
+        } else {
+            return (unsigned)v.order[pos];
+        }
+    };
     const int n = (int)a.n;
     unsigned long long *gk = a.gkeys + (int64_t)blockIdx.x * a.n_pad;
     unsigned *gi = a.gidx + (int64_t)blockIdx.x * a.n_pad;
-    double *rsum = a.rsum + (int64_t)blockIdx.x * a.nr_pad * 4;
-    int *rcnt = a.rcnt + (int64_t)blockIdx.x * a.nr_pad;
-    double *rlen = a.rlen + (int64_t)blockIdx.x * a.nr_pad;
+    const RangeScratch rs = {a.rsum + (int64_t)blockIdx.x * a.nr_pad * 4, a.rcnt + (int64_t)blockIdx.x * a.nr_pad,
+                             a.rlen + (int64_t)blockIdx.x * a.nr_pad};
     const bool t_safe = a.flags[0] != 0u;
 
-    unsigned long long *keys_w = reinterpret_cast<unsigned long long *>(wbuf + wave * kWaveBytes);
-    unsigned *fine_w = reinterpret_cast<unsigned *>(wbuf + wave * kWaveBytes + kRCap * 8);
-    IdxT *idx_w = reinterpret_cast<IdxT *>(wbuf + wave * kWaveBytes + kRCap * 8 + (kWFine + 4) * 4);
     unsigned *ghist = MULTI ? a.ghist + (int64_t)blockIdx.x * NB : nullptr;
     unsigned short *gb = MULTI ? a.gbucket + (int64_t)blockIdx.x * a.n_pad * 2 : nullptr;
     static_assert(!MULTI || NB <= 65536, "bucket ids are kept as 16-bit numbers");
@@ -995,63 +693,19 @@ __global__ __launch_bounds__(kBlock) void sl_fast_kernel(FastArgs a) {
         // bounds masks are loop-invariant, and hoisted out of the period loop they would all be spilled)
         int tid = tid0;
         asm volatile("" : "+v"(tid));
-        for (int b = tid; b < NB + 64; b += kBlock) hist[b] = 0u;
-        if (tid < 16) defer[tid] = tid == 15 ? (unsigned)kWaves : 0u;   // [15]: next range to hand out (P3a)
-        __syncthreads();
-        // Samples past the end (the last trip of a thread) go to one of 64 dummy buckets behind the
-        // histogram instead of being branched around: everything below is straight-line code.
         unsigned pk[(KMAX + 1) / 2];
-#pragma unroll
-        for (int k = 0; k < (KMAX + 1) / 2; ++k) pk[k] = 0u;
-        // (groups of G1 coalesced loads, the next group requested before the current one is folded;
-        // the scheduling barrier keeps the compiler from hoisting all <= 52 loads to the top)
-        constexpr int G1 = PDC_SL_G1, G2 = PDC_SL_G2;
-        static_assert(G1 % 4 == 0, "phases are computed four at a time");
-        double tv[G1], tn[G1];
-#pragma unroll
-        for (int u = 0; u < G1; ++u) {
-            const int i = u * kBlock + tid;
-            tn[u] = a.t[i < n ? i : n - 1];
+        {   // (P1 is text in the kernel body: sl_p1.inc says why)
+            constexpr int P1_BLK = kBlock, P1_NB = NB;
+            const double *const p1_t = a.t;
+#include "sl_p1.inc"
         }
-#pragma unroll
-        for (int k0 = 0; k0 < KMAX; k0 += G1) {
-            if (k0 * kBlock < n) {   // workgroup-uniform
-#pragma unroll
-                for (int u = 0; u < G1; ++u) tv[u] = tn[u];
-                if (k0 + G1 < KMAX && (k0 + G1) * kBlock < n) {
-#pragma unroll
-                    for (int u = 0; u < G1; ++u) {
-                        const int i = (k0 + G1 + u) * kBlock + tid;
-                        if (k0 + G1 + u < KMAX) tn[u] = a.t[i < n ? i : n - 1];
-                    }
-                }
-                double phi[G1];
-#pragma unroll
-                for (int q = 0; q < G1; q += 4) {
-                    double t4[4] = {tv[q], tv[q + 1], tv[q + 2], tv[q + 3]}, p4[4];
-                    phases4(t4, period, y, safe, p4);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) phi[q + u] = p4[u];
-                }
-#pragma unroll
-                for (int u = 0; u < G1; ++u) {
-                    if (k0 + u < KMAX) {
-                        const int i = (k0 + u) * kBlock + tid;
-                        const int b = i < n ? coarse_of<NB>(phi[u]) : NB + lane;
-                        atomicAdd(&hist[b], 1u);
-                        pk[(k0 + u) >> 1] |= (unsigned)b << (((k0 + u) & 1) * 16);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        __syncthreads();
-        scan_buckets<NB>(hist, wave_tot);   // hist[b] = first sorted position of bucket b
 #if PDC_SL_STOP == 1
         continue;
 #endif
-
         // ---- P2: the permutation, grouped by coarse bucket ----------------------------------------
+        // (written out here, where the duo kernels call permute<KMAX, BLK, G>: with P1 and P3a as text in this body,
+        // the call cost the <20 | 36 | 52, ..., false> instances one or two VGPRs - DESIGN.md 4.3c)
+        constexpr int G2 = PDC_SL_G2;
 #pragma unroll
         for (int k0 = 0; k0 < KMAX; k0 += G2) {
             if (k0 * kBlock < n) {   // workgroup-uniform
@@ -1060,14 +714,14 @@ __global__ __launch_bounds__(kBlock) void sl_fast_kernel(FastArgs a) {
                 for (int u = 0; u < G2; ++u) {
                     if (k0 + u < KMAX) {
                         const unsigned b = (pk[(k0 + u) >> 1] >> (((k0 + u) & 1) * 16)) & 0xFFFFu;
-                        pos[u] = atomicAdd(&hist[b], 1u);
+                        pos[u] = atomicAdd(&v.hist[b], 1u);
                     }
                 }
 #pragma unroll
                 for (int u = 0; u < G2; ++u) {
                     if (k0 + u < KMAX) {
                         const int i = (k0 + u) * kBlock + tid;
-                        order[i < n ? pos[u] : (unsigned)(n + lane)] = (IdxT)i;
+                        v.order[i < n ? pos[u] : (unsigned)(n + lane)] = (IdxT)i;
                     }
                 }
             }
@@ -1077,7 +731,7 @@ __global__ __launch_bounds__(kBlock) void sl_fast_kernel(FastArgs a) {
         // scratch, once per period -------------------------------------------------------------------------
         int tid = tid0;   // (opaque copy, as above: addresses built from the thread id are not hoisted out of the period loop and spilled)
         asm volatile("" : "+v"(tid));
-        for (int b = tid; b < NB; b += kBlock) hist[b] = 0u;
+        for (int b = tid; b < NB; b += kBlock) v.hist[b] = 0u;
         __syncthreads();
         // (eight coalesced loads per trip, the next trip's requested before this one is folded)
         auto load8 = [&](int i0, double (&v)[8]) {
@@ -1111,14 +765,14 @@ __global__ __launch_bounds__(kBlock) void sl_fast_kernel(FastArgs a) {
                 for (int u = 0; u < 8; ++u)
                     if (i0 + u * kBlock < n) {
                         const int b = coarse_of<NB>(phi[u]);
-                        atomicAdd(&hist[b], 1u);
+                        atomicAdd(&v.hist[b], 1u);
                         gb[i0 + u * kBlock] = (unsigned short)b;   // (read back once per slice: no second fold)
                     }
             }
         }
         __syncthreads();
-        scan_buckets<NB>(hist, wave_tot);   // hist[b] = first sorted position of bucket b
-        for (int b = tid; b < NB; b += kBlock) ghist[b] = hist[b];
+        scan_buckets<NB>(v.hist, wave_tot);   // v.hist[b] = first sorted position of bucket b
+        for (int b = tid; b < NB; b += kBlock) ghist[b] = v.hist[b];
         __syncthreads();
         }
         int tid = tid0;   // (opaque copy, as above: addresses built from the thread id are not hoisted out of the period loop and spilled)
@@ -1127,9 +781,9 @@ __global__ __launch_bounds__(kBlock) void sl_fast_kernel(FastArgs a) {
         asm volatile("" : "+v"(tid));   // (... nor out of the slice loop)
         if constexpr (MULTI) {
             __syncthreads();
-            for (int b = tid; b < NB; b += kBlock) hist[b] = ghist[b];
+            for (int b = tid; b < NB; b += kBlock) v.hist[b] = ghist[b];
             __syncthreads();
-            auto end_of = [&](int b) -> int { return b + 1 < NB ? (int)hist[b + 1] : n; };
+            auto end_of = [&](int b) -> int { return b + 1 < NB ? (int)v.hist[b + 1] : n; };
             {   // first bucket that still has unconsumed samples
                 int l = 0, h = NB - 1;
                 while (l < h) {
@@ -1173,12 +827,12 @@ __global__ __launch_bounds__(kBlock) void sl_fast_kernel(FastArgs a) {
                     }
                 }
                 if (tid == 0) {
-                    rsum[(int64_t)r_base * 4 + 0] = __longlong_as_double((long long)gk[0]);
-                    rsum[(int64_t)r_base * 4 + 1] = a.m[gi[0]];
-                    rsum[(int64_t)r_base * 4 + 2] = __longlong_as_double((long long)gk[cnt - 1]);
-                    rsum[(int64_t)r_base * 4 + 3] = a.m[gi[cnt - 1]];
-                    rcnt[r_base] = cnt;
-                    rlen[r_base] = 0.0;
+                    rs.rsum[(int64_t)r_base * 4 + 0] = __longlong_as_double((long long)gk[0]);
+                    rs.rsum[(int64_t)r_base * 4 + 1] = a.m[gi[0]];
+                    rs.rsum[(int64_t)r_base * 4 + 2] = __longlong_as_double((long long)gk[cnt - 1]);
+                    rs.rsum[(int64_t)r_base * 4 + 3] = a.m[gi[cnt - 1]];
+                    rs.rcnt[r_base] = cnt;
+                    rs.rlen[r_base] = 0.0;
                 }
                 __syncthreads();
                 r_base += 1;
@@ -1195,14 +849,14 @@ __global__ __launch_bounds__(kBlock) void sl_fast_kernel(FastArgs a) {
             }
             slice_n = end_of(b1 - 1) - consumed;
             __syncthreads();   // every thread has read what it needs from the start offsets
-            if (tid < 16) defer[tid] = tid == 15 ? (unsigned)kWaves : 0u;
+            if (tid < 16) v.defer[tid] = tid == 15 ? (unsigned)kWaves : 0u;
             if constexpr (P17) {
                 for (int x = tid; x < PL * plane_words; x += kBlock) plane[x] = 0u;
                 __syncthreads();
             }
             {
-                // hist[b] still holds the START of every bucket: every sample's bucket id is read back (2
-                // bytes, coalesced) and this slice's samples go to order[].  (Grouping all samples once in
+                // v.hist[b] still holds the START of every bucket: every sample's bucket id is read back (2
+                // bytes, coalesced) and this slice's samples go to v.order[].  (Grouping all samples once in
                 // global scratch instead costs a random 4-byte store per sample and period - 1.05e11/s, 2.6x
                 // slower than a random load; folding every sample again per slice - the first version of this
                 // path - cost as much as the ranges from five slices on.)
@@ -1218,14 +872,14 @@ __global__ __launch_bounds__(kBlock) void sl_fast_kernel(FastArgs a) {
                         const int i = i0 + u * kBlock;
                         const int b = (int)bk[u];
                         if (i < n && b >= b0 && b < b1) {
-                            const unsigned pos = atomicAdd(&hist[b], 1u) - (unsigned)consumed;
+                            const unsigned pos = atomicAdd(&v.hist[b], 1u) - (unsigned)consumed;
                             if constexpr (P17) {
                                 order16[pos] = (unsigned short)i;
                                 if ((i >> 16) & 1) atomicOr(&plane[pos >> 5], 1u << (pos & 31));
                                 if constexpr (PL > 1)
                                     if ((i >> 17) & 1) atomicOr(&plane[plane_words + (pos >> 5)], 1u << (pos & 31));
                             } else {
-                                order[pos] = (IdxT)i;
+                                v.order[pos] = (IdxT)i;
                             }
                         }
                     }
@@ -1233,33 +887,21 @@ __global__ __launch_bounds__(kBlock) void sl_fast_kernel(FastArgs a) {
             }
         }
         nranges = (slice_n + kFWin - 1) / kFWin;
-        __syncthreads();   // hist[b] = END position of bucket b
-        // range r starts at the first bucket whose start position is >= r * kWin
-        for (int r = tid; r <= nranges; r += kBlock) {
-            int b = b0, s0 = 0;
-            if (r > 0) {
-                const unsigned x = (unsigned)consumed + (unsigned)r * kFWin;
-                int l = b0, h = b1;   // smallest j in [b0, b1) with end(j) >= x, b1 if none
-                while (l < h) {
-                    const int mid = (l + h) >> 1;
-                    if (hist[mid] >= x) h = mid; else l = mid + 1;
-                }
-                b = l < b1 ? l + 1 : b1;
-                s0 = l < b1 ? (int)hist[l] - consumed : slice_n;
-            }
-            bndb[r] = (unsigned short)b;
-            bnds[r] = (unsigned short)s0;
-        }
-        __syncthreads();   // (the histogram is dead from here on: its LDS becomes wave scratch)
+        range_table<kBlock>(v, b0, b1, consumed, slice_n, nranges, tid);
 
 #if PDC_SL_STOP == 2
         continue;
 #endif
         // ---- P3a: wave-autonomous ranges -------------------------------------------------------------
-        constexpr bool kEmitSorted = EMIT;
         rec_t *const emit_row = EMIT ? a.sorted + p * a.n : nullptr;
+        // (text in the kernel body, not a call of walk_ranges: sl_p3a.inc says why; these are the names it reads)
+        const unsigned short *const bndb = v.bndb, *const bnds = v.bnds;
+        unsigned *const defer = v.defer, *const fine_w = v.fine_w;
+        unsigned long long *const keys_w = v.keys_w;
+        IdxT *const idx_w = v.idx_w;
+        const rec_t *const rec = a.rec;
         const int emit_at = consumed;
-#include "sl_ranges.inc"
+#include "sl_p3a.inc"
         if (wave < nranges) request(wave);
         for (int r = wave; r < nranges; r = r_next) {
             if (n_cnt > 192) process(r, std::true_type{});
@@ -1268,45 +910,24 @@ __global__ __launch_bounds__(kBlock) void sl_fast_kernel(FastArgs a) {
         __syncthreads();
 
         // ---- P3b: deferred ranges, whole workgroup ---------------------------------------------------
+        auto key_of = [&](double tv) { return phase_key(fast_phase(tv, period, y, safe)); };
         for (int w32 = 0; w32 < (nranges + 31) / 32; ++w32) {
-            unsigned bits = defer[w32];
+            unsigned bits = v.defer[w32];
             while (bits) {
                 const int r = w32 * 32 + __builtin_ctz(bits);
                 bits &= bits - 1;
-                const int s_lo = bnds[r], cnt = (int)bnds[r + 1] - s_lo;
-                int P = 2;
-                while (P < cnt) P <<= 1;
-                double p0, m0, p1, m1;
+                const int s_lo = v.bnds[r], cnt = (int)v.bnds[r + 1] - s_lo;
+                double ends[4];
                 if (cnt <= kDCap) {
+                    total += sort_deferred_lds<kBlock, EMIT>(v.bkeys, v.bidx, order_get, s_lo, cnt, a.t, a.m, key_of, tid,
+                                                             EMIT ? emit_row + consumed + s_lo : nullptr, ends);
+                } else {   // beyond the LDS sort: in global scratch
+                    int P = 2;
+                    while (P < cnt) P <<= 1;
                     for (int s = tid; s < P; s += kBlock) {
                         if (s < cnt) {
-                            const IdxT id = (IdxT)PDC_ORDER_GET(s_lo + s);
-                            bkeys[s] = phase_key(fast_phase(a.t[id], period, y, safe));
-                            bidx[s] = id;
-                        } else {
-                            bkeys[s] = ~0ull;
-                            bidx[s] = (IdxT)~0u;
-                        }
-                    }
-                    __syncthreads();
-                    bitonic_sort<IdxT>(bkeys, bidx, P);
-                    total += segment_sum(bkeys, bidx, cnt, a.m);
-                    if (EMIT)
-                        for (int s = tid; s < cnt; s += kBlock) {
-                            rec_t o;
-                            o.x = __longlong_as_double((long long)bkeys[s]);
-                            o.y = a.m[bidx[s]];
-                            emit_row[consumed + s_lo + s] = o;
-                        }
-                    p0 = __longlong_as_double((long long)bkeys[0]);
-                    m0 = a.m[bidx[0]];
-                    p1 = __longlong_as_double((long long)bkeys[cnt - 1]);
-                    m1 = a.m[bidx[cnt - 1]];
-                } else {
-                    for (int s = tid; s < P; s += kBlock) {
-                        if (s < cnt) {
-                            const unsigned id = PDC_ORDER_GET(s_lo + s);
-                            gk[s] = phase_key(fast_phase(a.t[id], period, y, safe));
+                            const unsigned id = order_get(s_lo + s);
+                            gk[s] = key_of(a.t[id]);
                             gi[s] = id;
                         } else {
                             gk[s] = ~0ull;
@@ -1323,19 +944,17 @@ __global__ __launch_bounds__(kBlock) void sl_fast_kernel(FastArgs a) {
                             o.y = a.m[gi[s]];
                             emit_row[consumed + s_lo + s] = o;
                         }
-                    p0 = __longlong_as_double((long long)gk[0]);
-                    m0 = a.m[gi[0]];
-                    p1 = __longlong_as_double((long long)gk[cnt - 1]);
-                    m1 = a.m[gi[cnt - 1]];
+                    ends[0] = __longlong_as_double((long long)gk[0]);
+                    ends[1] = a.m[gi[0]];
+                    ends[2] = __longlong_as_double((long long)gk[cnt - 1]);
+                    ends[3] = a.m[gi[cnt - 1]];
                 }
                 if (tid == 0) {
                     const int64_t g = r_base + r;
-                    rsum[g * 4 + 0] = p0;
-                    rsum[g * 4 + 1] = m0;
-                    rsum[g * 4 + 2] = p1;
-                    rsum[g * 4 + 3] = m1;
-                    rcnt[g] = cnt;
-                    rlen[g] = 0.0;   // (its segments were added to `total` by the whole workgroup, in a fixed order)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) rs.rsum[g * 4 + k] = ends[k];
+                    rs.rcnt[g] = cnt;
+                    rs.rlen[g] = 0.0;   // (its segments were added to `total` by the whole workgroup, in a fixed order)
                 }
                 __syncthreads();
             }
@@ -1343,42 +962,14 @@ __global__ __launch_bounds__(kBlock) void sl_fast_kernel(FastArgs a) {
         r_base += nranges;
         consumed += slice_n;
         } while (MULTI && consumed < n);
-        const int nr_all = r_base;
         __syncthreads();  // every summary of this period (global, this workgroup's) is visible
 
         // ---- P3c: links between consecutive non-empty ranges + the closing segment ----------------
-        for (int r = tid; r < nr_all; r += kBlock) {
-            if (rcnt[r] > 0) {
-                total += rlen[r];
-                int q = r - 1;
-                while (q >= 0 && rcnt[q] == 0) --q;
-                if (q >= 0)
-                    total += hypot(rsum[(int64_t)r * 4 + 1] - rsum[(int64_t)q * 4 + 3],
-                                   rsum[(int64_t)r * 4 + 0] - rsum[(int64_t)q * 4 + 2]);
-            }
-        }
-        if (tid == 0 && nr_all > 0) {
-            int f0 = 0, l0 = nr_all - 1;
-            while (f0 < nr_all && rcnt[f0] == 0) ++f0;
-            while (l0 >= 0 && rcnt[l0] == 0) --l0;
-            // closing segment of np.roll(-1): first minus last, no phase wrap (phase.py:50)
-            if (f0 < nr_all && l0 >= 0)
-                total += hypot(rsum[(int64_t)f0 * 4 + 1] - rsum[(int64_t)l0 * 4 + 3],
-                               rsum[(int64_t)f0 * 4 + 0] - rsum[(int64_t)l0 * 4 + 2]);
-        }
-        total = wave_sum(total);
-        if (lane == 0) red[wave] = total;
-        __syncthreads();
-        if (tid == 0) {
-            double sum = 0.0;
-            for (int w = 0; w < kWaves; ++w) sum += red[w];
-            a.ell[p] = sum;
-        }
+        const double sum = links_and_total<kBlock, true>(total, rs.rsum, rs.rcnt, rs.rlen, r_base, tid, lane, wave, red);
+        if (tid == 0) a.ell[p] = sum;
         __syncthreads();
     }
 }
-
-#undef PDC_ORDER_GET
 
 // AoS (t, m) table + the "every t is tame" flag (one workgroup; N <= 52k)
 __global__ __launch_bounds__(kBlock) void sl_prep_kernel(const double *t, const double *m, int n,
@@ -1386,17 +977,9 @@ __global__ __launch_bounds__(kBlock) void sl_prep_kernel(const double *t, const 
     __shared__ int bad;
     if (threadIdx.x == 0) bad = 0;
     __syncthreads();
-    int mine = 0;
-    for (int i = threadIdx.x; i < n; i += kBlock) {
-        const double tv = t[i];
-        rec_t v;
-        v.x = tv;
-        v.y = m[i];
-        rec[i] = v;
-        const double at = __builtin_fabs(tv);
-        if (!(at == 0.0 || (at >= 1e-150 && at <= 1e150))) mine = 1;
-    }
-    if (mine) atomicOr(&bad, 1);
+    PrepFlags mine;
+    for (int i = threadIdx.x; i < n; i += kBlock) prep_sample(t, m, i, rec, mine);
+    if (mine.wild) atomicOr(&bad, 1);
     __syncthreads();
     if (threadIdx.x == 0) flags[0] = bad ? 0u : 1u;
 }
@@ -1422,16 +1005,16 @@ namespace duo {
 using namespace fast;
 
 constexpr int kB = 512;
-constexpr int kW = kB / 64;
 constexpr int kLdsWg = kLdsTotal / 2;   // two workgroups per CU
 constexpr int kWaveB = Lds<unsigned short>::wave_bytes;
 constexpr int kRangesD = 136;           // >= kCapD / kFWin + 2
 constexpr int kStaticD = 256;           // static __shared__ below, rounded up
-constexpr int kFixedD = kW * kWaveB + 2 * (kRangesD + 8) * 2 + 64;
-constexpr int kCapD = ((((kLdsWg - kFixedD - kStaticD) / 2) & ~7) - 64);   // samples per period (+ 64 dummy slots)
+// the LDS block of a BLK-thread workgroup; its deferred LDS sort (keys + indices alias the wave scratch) takes 2048
+// samples with eight waves, 1024 with four
+template <int BLK>
+using View = PeriodLds<unsigned short, BLK / 64, kWaveB, kRangesD, (BLK >= 512 ? kDCap : 1024)>;
+constexpr int kCapD = ((((kLdsWg - View<kB>::fixed - kStaticD) / 2) & ~7) - 64);   // samples per period (+ 64 dummy slots)
 static_assert(kCapD / kFWin + 2 <= kRangesD, "range table too small");
-static_assert(kW * kWaveB >= (kNB + 64) * 4 && kW * kWaveB >= kDCap * 10, "aliases must fit");
-static_assert(kRangesD <= 15 * 32, "deferred-range bits live in defer[0..14]");
 constexpr int kCapQ = 4096;             // samples per period of the 256-thread instance (four workgroups per CU)
 
 struct DuoArgs {
@@ -1456,34 +1039,17 @@ struct DuoArgs {
 // binary searches are fixed work per period)
 template <int KMAX, int BLK = duo::kB, int NBL = kNB>
 __global__ __launch_bounds__(BLK, 4) void sl_duo_kernel(DuoArgs a) {
-    constexpr int kB = BLK, kW = BLK / 64;                 // (shadow the namespace's 512-thread values)
-    constexpr int kDCap = BLK >= 512 ? ::kDCap : 1024;     // deferred LDS sort: keys + indices alias the wave scratch
-    static_assert(kW * kWaveB >= (NBL + 64) * 4 && kW * kWaveB >= kDCap * 10, "aliases must fit");
-    typedef unsigned short IdxT;
+    using L = View<BLK>;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    unsigned char *wbuf = lds_raw;                                                  // P3a: per-wave scratch
-    unsigned *hist = reinterpret_cast<unsigned *>(lds_raw);                         // P1/P2 alias [NBL + 64]
-    unsigned long long *bkeys = reinterpret_cast<unsigned long long *>(lds_raw);    // P3b alias [kDCap]
-    IdxT *bidx = reinterpret_cast<IdxT *>(bkeys + kDCap);                           // P3b alias [kDCap]
-    unsigned short *bndb = reinterpret_cast<unsigned short *>(lds_raw + kW * kWaveB);
-    unsigned short *bnds = bndb + kRangesD + 8;
-    unsigned *defer = reinterpret_cast<unsigned *>(bnds + kRangesD + 8);            // [16]
-    IdxT *order = reinterpret_cast<IdxT *>(defer + 16);                             // [cap + 64]
-    __shared__ unsigned wave_tot[kW];
-    __shared__ double red[kW];
+    __shared__ unsigned wave_tot[BLK / 64];
+    __shared__ double red[BLK / 64];
     __shared__ unsigned s_item, s_bad;
     const int tid0 = threadIdx.x, lane = tid0 & 63, wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
-    const int n = a.n;
-    double *rsum = a.rsum + (int64_t)blockIdx.x * a.nr_pad * 4;
-    int *rcnt = a.rcnt + (int64_t)blockIdx.x * a.nr_pad;
-    double *rlen = a.rlen + (int64_t)blockIdx.x * a.nr_pad;
-    const bool t_safe = a.flags[0] != 0u;
+    const L v = L::carve(lds_raw, wave);
+    const RangeScratch rs = {a.rsum + (int64_t)blockIdx.x * a.nr_pad * 4, a.rcnt + (int64_t)blockIdx.x * a.nr_pad,
+                             a.rlen + (int64_t)blockIdx.x * a.nr_pad};
+    const DuoCurve curve = {a.t, a.m, a.rec, a.periods, a.ell, a.todo, a.n, a.flags[0] != 0u, a.ticket + 1};
     const unsigned n_items = (unsigned)a.n_periods;
-    unsigned *const marked = a.ticket + 1;
-
-    unsigned long long *keys_w = reinterpret_cast<unsigned long long *>(wbuf + wave * kWaveB);
-    unsigned *fine_w = reinterpret_cast<unsigned *>(wbuf + wave * kWaveB + kRCap * 8);
-    IdxT *idx_w = reinterpret_cast<IdxT *>(wbuf + wave * kWaveB + kRCap * 8 + (kWFine + 4) * 4);
 
     for (;;) {
         __syncthreads();   // the previous item is done with LDS
@@ -1496,7 +1062,19 @@ __global__ __launch_bounds__(BLK, 4) void sl_duo_kernel(DuoArgs a) {
         if (item >= n_items) break;
         const int64_t p = (int64_t)item;
         if (a.skip && a.skip[p]) continue;   // (workgroup-uniform)
-#include "sl_duo_body.inc"
+        const int n = curve.n;
+        const double period = curve.periods[p];
+        const double y = 1.0 / period;
+        const bool safe = period_is_safe(period, curve.t_safe);
+        int tid = tid0;   // (opaque copy, once per period: addresses built from it are not hoisted out of the ticket loop and spilled)
+        asm volatile("" : "+v"(tid));
+        unsigned pk[(KMAX + 1) / 2];
+        {   // (P1 is text in the kernel body: sl_p1.inc says why)
+            constexpr int P1_BLK = BLK, P1_NB = NBL;
+            const double *const p1_t = curve.t;
+#include "sl_p1.inc"
+        }
+        duo_period<KMAX, BLK, NBL>(curve, p, period, y, safe, tid, pk, v, rs, red, &s_bad, lane, wave);
     }
 }
 
@@ -1614,24 +1192,16 @@ struct StreamArgs {
 
 __global__ __launch_bounds__(256) void sl_tame_kernel(const double *t, const double *m, rec_t *tm, double *t_copy, double *m_copy,
                                                       int64_t n, unsigned *bad) {
-    bool mine = false, unsorted = false;
+    PrepFlags f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        if (tm) {
-            rec_t r;
-            r.x = t[i];
-            r.y = m[i];
-            tm[i] = r;
-        }
+        const rec_t r = prep_sample(t, m, i, tm, f);
         if (t_copy) {   // (samples that may be in any order: the time sort works on copies)
-            t_copy[i] = t[i];
-            m_copy[i] = m[i];
+            t_copy[i] = r.x;
+            m_copy[i] = r.y;
         }
-        const double at = __builtin_fabs(t[i]);
-        mine = mine || !(at == 0.0 || (at >= 1e-150 && at <= 1e150));
-        unsorted = unsorted || (i > 0 && !(t[i - 1] <= t[i]));   // (NaN counts as unsorted)
     }
-    if (__any(mine) && (threadIdx.x & 63) == 0) atomicOr(bad, 1u);
-    if (__any(unsorted) && (threadIdx.x & 63) == 0) atomicOr(bad + 1, 1u);
+    if (__any(f.wild) && (threadIdx.x & 63) == 0) atomicOr(bad, 1u);
+    if (__any(f.unsorted) && (threadIdx.x & 63) == 0) atomicOr(bad + 1, 1u);
 }
 
 // sample index of local position l of tile kappa of group w: every group owns a contiguous run of tiles_w tiles
@@ -2081,7 +1651,7 @@ __global__ __launch_bounds__(kBA) void sl_bound_kernel(StreamArgs a) {
 //    round trips one after the other), and the sum depends on the arrival order of the partition's atomics;
 //  - alternating counter halves + the bin's sum written one barrier later (two barriers fewer): no change - kept;
 //  - the workgroup only groups the bin by 2048 mid buckets and every WAVE ranks and sums ranges of <= 255 records by
-//    itself (the several-slice kernels' sl_ranges.inc on records already in LDS, no barrier in the data-dependent
+//    itself (the several-slice kernels' walk_ranges on records already in LDS, no barrier in the data-dependent
 //    part): 1055 us, 921 us with a parallel link step and a range table built by the counters' owners - the byte
 //    counters' scan per range and rows filled to two thirds cost ~900 instructions per 170 records, and without a
 //    second register set for the next bin's records every wave waits 6.6 k cycles for them.
@@ -2632,47 +2202,19 @@ struct OneArgs {
 __global__ __launch_bounds__(256) void sl_onecycle_mark_kernel(OneArgs a) {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= a.n_periods) return;
-    bool one = false;
-    if (a.bad[1] == 0u && a.n >= 2) {
-        const double period = a.periods[p];
-        const double y = 1.0 / period;
-        const bool safe = period_is_safe(period, a.bad[0] == 0u);
-        const double q0 = exact_quotient(a.t[0], period, y, safe), q1 = exact_quotient(a.t[a.n - 1], period, y, safe);
-        const double c0 = __builtin_floor(q0), c1 = __builtin_floor(q1);
-        // (the samples span less than one cycle: all in one, or the later ones in the next with phases BELOW the first
-        // sample's - sorted order = those, then the earlier ones, each as they stand: the same segments, the pair across
-        // the cycle boundary being the closing one.  NaN: no)
-        one = period > 0.0 && (c1 - c0 == 0.0 || (c1 - c0 == 1.0 && q1 - c1 < q0 - c0));
-    }
+    const bool one = is_one_cycle(a.t, a.n, a.periods[p], a.bad[0], a.bad[1]);
     a.skip[p] = one ? 1 : 0;
     if (one) a.list[atomicAdd(a.count, 1u)] = (unsigned)p;
 }
 
 __global__ __launch_bounds__(kBlock) void sl_onecycle_kernel(OneArgs a) {
     __shared__ double red[kBlock / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned count = *a.count;
     for (unsigned k = blockIdx.x; k < count; k += gridDim.x) {   // (workgroup-uniform)
         const int64_t p = a.list[k];
         const double period = a.periods[p];
-        const double y = 1.0 / period;
-        const bool safe = period_is_safe(period, a.bad[0] == 0u);
-        double acc = 0.0;
-        for (int64_t i = tid + 1; i < a.n; i += kBlock) {        // segment (i - 1, i)
-            const double p1 = fast_phase(a.t[i], period, y, safe), p0 = fast_phase(a.t[i - 1], period, y, safe);
-            acc += short_hypot(a.m[i] - a.m[i - 1], p1 - p0);
-        }
-        acc = wave_sum_fixed(acc);
-        if (lane == 0) red[wave] = acc;
-        __syncthreads();
-        if (tid == 0) {
-            double total = 0.0;
-            for (int x = 0; x < kBlock / 64; ++x) total += red[x];
-            // closing segment of np.roll(-1): first minus last, no phase wrap (phase.py:50)
-            total += hypot(a.m[0] - a.m[a.n - 1],
-                           fast_phase(a.t[0], period, y, safe) - fast_phase(a.t[a.n - 1], period, y, safe));
-            a.ell[p] = total;
-        }
+        const double total = onecycle_sum<kBlock>(a.t, a.m, a.n, period, period_is_safe(period, a.bad[0] == 0u), red);
+        if (threadIdx.x == 0) a.ell[p] = total;
         __syncthreads();
     }
 }
@@ -2756,8 +2298,7 @@ StreamShape stream_shape(int64_t n, int64_t n_periods, bool lists = true) {
 
 template <int KMAX, int BLK = duo::kB, int NBL = fast::kNB>
 int launch_duo(const duo::DuoArgs &a, int64_t grid, hipStream_t st) {
-    const size_t fixed = (size_t)(BLK / 64) * duo::kWaveB + 2 * (duo::kRangesD + 8) * 2 + 64;
-    const size_t lds = fixed + (size_t)((a.n + 64 + 7) & ~7) * 2;
+    const size_t lds = duo::View<BLK>::bytes(a.n);
     PDC_TRY(allow_dynamic_lds((const void *)duo::sl_duo_kernel<KMAX, BLK, NBL>, duo::kLdsWg - duo::kStaticD));
     hipLaunchKernelGGL((duo::sl_duo_kernel<KMAX, BLK, NBL>), dim3((unsigned)grid), dim3(BLK), lds, st, a);
     return PDC_OK;
@@ -3016,9 +2557,10 @@ template <int KMAX, typename IdxT = unsigned short, int NB = fast::kNB, bool MUL
 int launch_fast(const fast::FastArgs &a, int64_t grid, hipStream_t st) {
     constexpr bool P17 = PL > 0;
     const int64_t slice = MULTI ? a.slice_cap : a.n;
-    const int64_t entries = (slice + 64 + 7) & ~(int64_t)7;
-    const size_t lds = (size_t)fast::FL<IdxT>::fixed +
-                       (P17 ? (size_t)entries * 2 + (size_t)PL * ((slice + 64 + 31) / 32) * 4 + 16 : (size_t)entries * sizeof(IdxT));
+    using L = typename fast::FL<IdxT>::View;
+    // (bit planes: 16 bits per entry of the permutation + PL plane bits, in place of the 32-bit entries)
+    const size_t lds = P17 ? (size_t)L::fixed + (size_t)L::order_entries(slice) * 2 + (size_t)PL * ((slice + 64 + 31) / 32) * 4 + 16
+                           : L::bytes(slice);
     PDC_REQUIRE(lds <= (size_t)fast::kLdsTotalDyn, "stringlength: slice of %lld samples does not fit LDS", (long long)slice);
     PDC_TRY(allow_dynamic_lds((const void *)fast::sl_fast_kernel<KMAX, IdxT, NB, MULTI, PL, EMIT>, fast::kLdsTotalDyn));
     hipLaunchKernelGGL((fast::sl_fast_kernel<KMAX, IdxT, NB, MULTI, PL, EMIT>), dim3((unsigned)grid), dim3(kBlock), lds, st, a);
