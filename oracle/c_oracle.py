@@ -147,6 +147,22 @@ def gls_sums_f64(t, hy, h, frequency):
     return out
 
 
+def gls_sums_reduced(t, hy, h, frequency):
+    """``oracle_gls_sums_reduced``: the six sums ``[nf][6] = (Sh, Ch, S, C, S2, C2)`` in long double over
+    ``t' = t - t[0]``, the phase ``f t'`` reduced in cycles through its exact product before anything is rounded: the
+    checker for error budgets of 1e-14, good at any cycle count.  ``hy`` and ``h`` are taken as long double."""
+    if np.dtype(np.longdouble).itemsize != 16 or np.finfo(np.longdouble).nmant != 63:
+        raise RuntimeError("gls_sums_reduced needs numpy's longdouble to be the C compiler's 80-bit long double")
+    t, f = _f(t), _f(frequency)
+    hy = np.ascontiguousarray(hy, dtype=np.longdouble)
+    h = np.ascontiguousarray(h, dtype=np.longdouble)
+    if hy.size != t.size or h.size != t.size:
+        raise ValueError("Input arrays have incompatible lengths.")
+    out = np.empty((f.size, 6), dtype=np.longdouble)
+    lib().oracle_gls_sums_reduced(_p(t), _p(hy), _p(h), C.c_int64(t.size), _p(f), C.c_int64(f.size), _p(out))
+    return out
+
+
 def gls_power_f64_batch(t, values, err, frequency, fit_mean=True, psd=False):
     """Rows of ``gls_power_f64`` for curves of equal length (2-D ``t``, ``values``, ``err``): one OpenMP region
     over (curve, frequency tile), the reference's prologue / epilogue per row."""

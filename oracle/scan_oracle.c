@@ -29,6 +29,42 @@ void oracle_trig_sums_exact(const double *t, const double *h, int64_t n, const d
     }
 }
 
+/* The six GLS sums with the phase REDUCED IN CYCLES before any rounding that scales with it: the checker for
+ * error budgets of ~1e-14, where oracle_trig_sums_exact's 64-bit product 2 pi f t (2^-64 of the PHASE: 2e-14 rad
+ * at 5e4 cycles) is itself the size of what is measured.  t' = t - t[0] in double, as the device takes it;
+ * p = fl(f t'), e = fma(f, t', -p) is the product's exact remainder, p - rint(p) is exact, and
+ * r = (long double)(p - rint(p)) + (long double)e carries f t' mod 1 with no rounding at all (|e| <= ulp(p) / 2 and
+ * the 64-bit significand holds both terms whenever they are 11 bits apart or less; otherwise the rounding is
+ * 2^-64 of a number below 1/2).  Then sinl / cosl of 2 pi r and long-double sums in sample order.  The weights come
+ * as long double (hy = w y', h = w), so the caller's prologue need not round them to double; out = [nf][6] =
+ * {Sh, Ch, S, C, S2, C2}, S2 and C2 at the doubled phase 2 r (exact).
+ * tests/test_gls_error_budget_host.py pins it to integer arithmetic on lattice inputs, at 4e3 and 4e6 cycles. */
+void oracle_gls_sums_reduced(const double *t, const long double *hy, const long double *h, int64_t n,
+                             const double *freq, int64_t nf, long double *out) {
+    const long double two_pi = 2.0L * acosl(-1.0L);
+    const double t0 = n > 0 ? t[0] : 0.0;
+#pragma omp parallel for schedule(static)
+    for (int64_t j = 0; j < nf; ++j) {
+        const double f = freq[j];
+        long double a[6] = {0.0L, 0.0L, 0.0L, 0.0L, 0.0L, 0.0L};
+        for (int64_t i = 0; i < n; ++i) {
+            const double tp = t[i] - t0;
+            const double p = f * tp;
+            const double e = fma(f, tp, -p);
+            const long double r = (long double)(p - rint(p)) + (long double)e;
+            const long double x = two_pi * r;
+            const long double s = sinl(x), c = cosl(x), s2 = sinl(x + x), c2 = cosl(x + x);
+            a[0] += hy[i] * s;
+            a[1] += hy[i] * c;
+            a[2] += h[i] * s;
+            a[3] += h[i] * c;
+            a[4] += h[i] * s2;
+            a[5] += h[i] * c2;
+        }
+        for (int q = 0; q < 6; ++q) out[j * 6 + q] = a[q];
+    }
+}
+
 /* numpy's float remainder for a positive divisor of 1 (Python modulo, phase.py:131,
  * core.py:544): fmod, then shift negative results up by the divisor. */
 static double mod1(double q) {
