@@ -302,6 +302,50 @@ int pdc_htest_fdot_last_dispatch(int *ht, int *k, int *parts, int *rows_per_laun
  * both planes; a device of 256 CUs is assumed for parts == 0.  -1 for sizes out of range.  No GPU needed. */
 int64_t pdc_htest_fdot_work_bytes(int64_t n, int64_t nf, int64_t nfd, int nharm, int parts, int want_plane);
 
+/* ---- WWZ: the weighted wavelet Z-transform (Foster 1996, AJ 112, 1709) -------------------------------------------------
+ * The reference has no such statistic (its timefrequency.WPS needs an evenly sampled series) - PARITY UNPINNED BY THE
+ * REFERENCE.  Time-frequency analysis of an unevenly sampled curve: at every time shift tau[r], r < ntau, and every trial
+ * frequency f_j = f0 + j delta (numpy's arange fill, f0 >= 0, delta > 0) the weighted least-squares fit of a constant plus
+ * a sinusoid under a Gaussian window whose width scales with the period.  Times t[n] never decrease; s_i = dy_i^-2
+ * (dy == NULL: 1); omega = 2 pi f; decay c > 0 (Foster: 1 / (8 pi^2)):
+ *     w_i = s_i exp(-c omega^2 (t_i - tau)^2),   W = sum w_i,   Neff = W^2 / sum w_i^2,   <a, b> = sum w_i a_i b_i / W,
+ *     phi = (1, cos omega (t - t[0]), sin omega (t - t[0])),   S = <phi phi^T>,   b = <phi y>,   a = S^-1 b,
+ *     Vx = <y, y> - <1, y>^2,   Vy = a^T b - <1, y>^2,
+ *     WWZ = (Neff - 3) Vy / (2 (Vx - Vy)),   WWA = sqrt(a_2^2 + a_3^2)
+ * (neither depends on the phase origin; y is centred on its global weighted mean first, which the constant absorbs).  A
+ * cell with W not > 0, or with a Cholesky pivot of S not > 0 or not finite, is NaN in WWZ and WWA; Neff is 0 where W is
+ * not > 0.  Samples whose exponent c (2 pi f_lo)^2 (t_i - tau)^2 at the LOWEST frequency f_lo of a tile of
+ * pdc_wwz_tile_bins() bins exceeds 746 are skipped for that (tile, tau): their weight is exactly 0 in fp64 at every
+ * frequency of the tile.  Outputs, any of them NULL, not all:
+ *     wwz_out[ntau][nf], amp_out[ntau][nf], neff_out[ntau][nf]   WWZ, WWA and Neff of every cell;
+ *     ridge_bin_out[ntau], ridge_wwz_out[ntau], ridge_amp_out[ntau]   per tau the bin of the largest WWZ among the cells
+ *         with Neff >= min_neff, as np.nanargmax(np.where(neff >= min_neff, wwz, nan), axis=1) finds it (NaN never wins,
+ *         the lowest bin of equal maxima wins), with its WWZ and WWA; bin -1 and NaN where no cell is eligible;
+ *     best_out[1], best_at_out[2] = (row, bin)   the largest ridge value as np.nanargmax finds it in ascending row order;
+ *         NaN and (-1, -1) where no row has a bin;
+ *     visited_out[1]   the samples that were not skipped, summed over all (tile, tau).
+ * min_neff applies to the reductions only, never to the planes.  Checked before any device is looked for: f0 finite and
+ * >= 0, delta finite and > 0, nf >= 1, n >= 4, ntau >= 1, decay finite and > 0, min_neff finite, not every output NULL,
+ * and in the host form finite t that never decrease and finite tau (the `_dev` form cannot look at them: they are its
+ * caller's precondition, and no value of them indexes memory out of bounds).  A launch takes at most 65535 rows; no bit
+ * depends on the rows per launch.  No atomics: the same bits from call to call.  The `_dev` form takes device pointers
+ * (tau too), enqueues on `stream` and keeps its own workspace per (device, stream). */
+int pdc_wwz_scan(const double *t, const double *y, const double *dy, int64_t n, double f0, double delta, int64_t nf,
+                 const double *tau, int64_t ntau, double decay, double min_neff, double *wwz_out, double *amp_out,
+                 double *neff_out, int64_t *ridge_bin_out, double *ridge_wwz_out, double *ridge_amp_out, double *best_out,
+                 int64_t *best_at_out, int64_t *visited_out, int device);
+int pdc_wwz_scan_dev(int device, void *stream, const double *d_t, const double *d_y, const double *d_dy, int64_t n,
+                     double f0, double delta, int64_t nf, const double *d_tau, int64_t ntau, double decay,
+                     double min_neff, double *d_wwz, double *d_amp, double *d_neff, int64_t *d_ridge_bin,
+                     double *d_ridge_wwz, double *d_ridge_amp, double *d_best, int64_t *d_best_at, int64_t *d_visited);
+/* Bins per tile of the scan (the unit of the support cut).  No GPU needed. */
+int64_t pdc_wwz_tile_bins(void);
+/* Workspace bytes of a scan; -1 for sizes out of range (n < 4, nf < 1, ntau < 1, a plane too large).  No GPU needed. */
+int64_t pdc_wwz_work_bytes(int64_t n, int64_t nf, int64_t ntau);
+/* What the CALLING THREAD's last WWZ scan launched (as pdc_htest_last_dispatch; zeros before the first): frequencies per
+ * thread, rows per launch, launches of the scan kernel.  Any pointer may be NULL. */
+int pdc_wwz_last_dispatch(int *k, int *rows_per_launch, int64_t *launches);
+
 /* ---- BLS: box least squares (Kovacs, Zucker & Mazeh 2002, A&A 391, 369) ----------------------------------------------
  * The reference has no such class - PARITY UNPINNED BY THE REFERENCE.  The search for a box-shaped dip (a transit, a
  * detached eclipse): per trial period the best two-level model of the folded curve.  Weights and centring as

@@ -60,6 +60,12 @@ PROTOTYPES = {
                                      _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pdc_htest_fdot_last_dispatch": (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), c_int64_p]),
     "pdc_htest_fdot_work_bytes": (_L, [_L, _L, _L, _I, _I, _I]),
+    "pdc_wwz_scan": (_I, [_VP, _VP, _VP, _L, _D, _D, _L, _VP, _L, _D, _D, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I]),
+    "pdc_wwz_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _D, _D, _L, _VP, _L, _D, _D,
+                              _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pdc_wwz_tile_bins": (_L, []),
+    "pdc_wwz_work_bytes": (_L, [_L, _L, _L]),
+    "pdc_wwz_last_dispatch": (_I, [C.POINTER(_I), C.POINTER(_I), c_int64_p]),
     "pdc_bls_scan": (_I, [_VP, _VP, _VP, _L, _VP, _L, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _I]),
     "pdc_bls_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _VP, _L, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "pdc_bls_scan_ragged": (_I, [_VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I,
@@ -398,6 +404,48 @@ def htest_fdot_last_dispatch():
 def htest_fdot_work_bytes(n, nf, nfd, nharm=20, parts=0, want_plane=True):
     """Workspace bytes of a plane scan under the current ``PDC_WORK_BUDGET_GB`` (-1: sizes out of range); no GPU needed."""
     return int(lib().pdc_htest_fdot_work_bytes(int(n), int(nf), int(nfd), int(nharm), int(parts), int(bool(want_plane))))
+
+
+def wwz_scan(t, y, dy, f0, delta, nf, tau, decay, min_neff=6.0, want_planes=True, device=None):
+    """Weighted wavelet Z-transform over the time shifts ``tau`` times the grid of frequencies (``pdc_wwz_scan``):
+    times ``t`` that never decrease, uncertainties ``dy`` (None: unit).  Returns a dict: ``wwz`` / ``amp`` / ``neff``
+    ``[ntau][nf]`` (None without ``want_planes``), ``ridge_bin`` (int64) / ``ridge_wwz`` / ``ridge_amp`` ``[ntau]`` (per
+    tau the best bin with ``neff >= min_neff``), ``best`` = ``(value, row, bin)`` and ``visited``, the samples inside
+    the support cut summed over all (tile, tau)."""
+    t, y, tau = _f64(t, "t"), _f64(y, "y"), _f64(tau, "tau")
+    dy = None if dy is None else _f64(dy, "dy")
+    if y.size != t.size or (dy is not None and dy.size != t.size):
+        raise ValueError("Input arrays have incompatible lengths.")
+    ntau = tau.size
+    out = {name: np.empty((ntau, nf)) if want_planes else None for name in ("wwz", "amp", "neff")}
+    out["ridge_bin"] = np.empty(ntau, dtype=np.int64)
+    out["ridge_wwz"], out["ridge_amp"] = np.empty(ntau), np.empty(ntau)
+    best, best_at, visited = np.full(1, np.nan), np.full(2, -1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+    dev = default_device() if device is None else device
+    check(lib().pdc_wwz_scan(_ptr(t), _ptr(y), _ptr(dy), t.size, f0, delta, nf, _ptr(tau), ntau, float(decay),
+                             float(min_neff), _ptr(out["wwz"]), _ptr(out["amp"]), _ptr(out["neff"]),
+                             _ptr(out["ridge_bin"]), _ptr(out["ridge_wwz"]), _ptr(out["ridge_amp"]), _ptr(best),
+                             _ptr(best_at), _ptr(visited), dev))
+    out["best"] = (float(best[0]), int(best_at[0]), int(best_at[1]))
+    out["visited"] = int(visited[0])
+    return out
+
+
+def wwz_tile_bins():
+    """Bins per tile of the WWZ scan, the unit of its support cut; no GPU needed."""
+    return int(lib().pdc_wwz_tile_bins())
+
+
+def wwz_work_bytes(n, nf, ntau):
+    """Workspace bytes of a WWZ scan (-1: sizes out of range); no GPU needed."""
+    return int(lib().pdc_wwz_work_bytes(int(n), int(nf), int(ntau)))
+
+
+def wwz_last_dispatch():
+    """``(k, rows_per_launch, launches)`` of this thread's last WWZ scan."""
+    k, rows, launches = C.c_int(0), C.c_int(0), C.c_int64(0)
+    check(lib().pdc_wwz_last_dispatch(C.byref(k), C.byref(rows), C.byref(launches)))
+    return k.value, rows.value, launches.value
 
 
 def bls_scan(t, y, dy, periods, n_bins, len_min, len_max, min_points=5, dips_only=False, slices=0, device=None):
