@@ -1,21 +1,30 @@
 // Generalized Lomb-Scargle by the reference's OWN algorithm on the device (SURVEY.md §8 f1,
-// "Tier F"): Press-Rybicki extirpolation + inverse FFT, exactly as
-// /root/reference/src/periodicity/spectral.py:11-40 (`_trig_sum`) does it on the CPU, followed by
+// "Tier F"): Press-Rybicki extirpolation + inverse FFT, exactly as the reference's
+// src/periodicity/spectral.py:11-40 (`_trig_sum`) does it on the CPU, followed by
 // the same epilogue (spectral.py:113-132).  O(N + nfft log nfft) instead of O(N nf); it inherits
 // the reference's approximation error (median ~1e-3 relative vs the exact sums) and therefore
 // reproduces `power_ref` itself, where the direct-sum kernel (gls.hip) reproduces the exact sums.
 //
-// Pipeline (all on one stream, nothing but power[nf] leaves the device):
-//   glsfft_prep_{a,c}      weights, centring, YY, tmin (grid-wide, fixed-order partials)  (:99-108,120)
-//   glsfft_spread_kernel   one thread per sample: weights pre-rotated to fmin about tmin (:19-20),
-//                          grid position (:21), whole hits deposited (:22-24), the rest spread over
-//                          four neighbours with cubic Lagrange weights (:25-33) — fp64 global
-//                          atomics into 2 or 3 complex grids (w*y @ df, w @ 2df, w @ df)
-//   fft_pass_kernel<R>     Stockham autosort radix-16/8/4/2 passes, out of place, ping-pong between
-//                          the grid and one scratch buffer; every pass streams the array once
-//                          (HBM-bound: 32 B per point per pass), twiddles from the cycle-domain
-//                          sincos (no tables, no recurrences)                               (:34)
-//   glsfft_epilogue_kernel undo the tmin shift (:35-37), scale by nfft (:38-39), epilogue
+// Pipeline (all on one stream; nothing but power[nf], or the raw sums, leaves the device), for one curve or a batch
+// (blockIdx.y = curve, or curve x grid); per curve 2 or 3 complex grids: (w y @ df), (w @ 2 df), (w @ df) with fit_mean:
+//   prologue               weights, centring, YY, {tmin, tmax, sorted}                               (:99-108, 120)
+//                          glsfft_prep_{a,c}: one curve, grid-wide, fixed-order partials
+//                          glsfft_prep_batch_kernel: one workgroup per curve
+//   extirpolation          `Extirp`: weights pre-rotated to fmin about tmin (:19-20), grid position (:21), whole hits
+//                          deposited (:22-24), the rest over four neighbours with cubic Lagrange weights (:25-33)
+//                          glsfft_deposit_kernel: sorted stamps on a grid that does not wrap - every thread owns cells and
+//                            adds their samples in order, no atomics, no memset; otherwise it only zeroes the grid
+//                          glsfft_spread_kernel: one thread per sample, fp64 global atomics - the grids the deposit
+//                            kernel left empty (stamps out of order, or a grid that wraps), else it returns at once
+//   inverse FFT            Stockham autosort, out of place, ping-pong between the grids and one scratch buffer; every
+//                          pass streams the array once (HBM-bound: 32 B per point per pass); twiddles from the
+//                          cycle-domain sincos (no tables, no recurrences)                                     (:34)
+//                          fft_pass_lds_kernel<RB>: radix 16 x RB through LDS in one trip (N >= 4096)
+//                          fft_pass_kernel<R>: plain radix-16/8/4/2 for what is left
+//                          the first pass reads live cells only, the last stores [0, nf) only
+//   glsfft_epilogue_kernel undo the tmin shift (:35-37), scale by nfft (:38-39), power (:113-132);
+//                          glsfft_raw_sums_kernel stops at S and C (pdc_trig_sums_fft); row_nanmax_kernel for batches
+// How the path got here, with the experiments that were withdrawn: docs/history.md.
 #include "pdc_internal.h"
 #include "gls_epilogue.h"
 #include "gls_sums.h"
@@ -97,7 +106,7 @@ struct LiveArgs {
 };
 
 __device__ __forceinline__ bool deposit_in_order(const double *ord, double nfftd, double dfg) {
-    const double span = ord[1] - ord[0];   // (NaN or -inf when no time stamp is a number: the atomic kernels then)
+    const double span = ord[1] - ord[0];   // (NaN or -inf when no time stamp is a number: the atomic kernel then)
     return ord[2] != 0.0 && span >= 0.0 && (span * nfftd) * dfg < nfftd;
 }
 
@@ -150,21 +159,15 @@ __global__ __launch_bounds__(kBlock) void fft_pass_kernel(const cplx *__restrict
 //   stage B  (jj, s2) pairs, 16/RB per thread: RB-point DFT over r1 -> Y[s2 + 16 s1]
 //            -> out[(j-k)*R + k + s*Ns]
 // Global accesses are runs of >= 16 consecutive complex numbers (256 B).  Requires N >= 4096.
-// (Round 6, measured and withdrawn - profiles/r06_fft_halves_experiment.patch: the exchange between the stages one
-// component at a time - real parts, then imaginary parts, 37 KB of LDS instead of 74, three to four workgroups per CU
-// instead of two, two more barriers: C2's FFT path 0.599 against 0.538 ms on the same box.  The passes are not short of
-// resident waves.)
 template <int RB>
 __global__ __launch_bounds__(256) void fft_pass_lds_kernel(const cplx *__restrict__ in,
                                                             cplx *__restrict__ out, int64_t N,
                                                             int64_t Ns, int64_t keep, LiveArgs lv) {
     constexpr int R = 16 * RB;
     constexpr int JT = 256 / RB;          // butterflies per workgroup
-    // Padded LDS row per butterfly: ONE complex number (16 B) of padding.  Round 6: it was R + 16 - 256 B, a whole number
-    // of LDS bank rows (32 banks x 4 B), i.e. no skew at all: in stage A every lane of a store instruction (fixed s2)
-    // hit the same four banks, a 64-way serialisation, and stage B's loads spread over half of them; the PMC counters
-    // had it (SQ_LDS_BANK_CONFLICT 9.2e6 of 11.3e6 LDS-active cycles per pass, 18 us of a pass's 45 inside LDS).  With
-    // R + 1 the 16-byte slot of (jj, r1, s2) is (jj + s2) mod 8: eight lanes per slot, the minimum for 64 x 16 B.
+    // Padded LDS row per butterfly: ONE complex number (16 B) of padding, not a whole number of LDS bank rows (32 banks
+    // x 4 B), which would be no skew at all.  With R + 1 the 16-byte slot of (jj, r1, s2) is (jj + s2) mod 8: eight
+    // lanes per slot, the minimum for 64 x 16 B.
     constexpr int ROW = R + 1;
     __shared__ cplx tile[JT * ROW];       // [jj][r1][s2]
     __shared__ cplx wR[R];
@@ -250,7 +253,10 @@ struct FftPrepArgs {
     double *scal;   // {YY (filled by the epilogue's reduction), Werr, tmin, tmax, sorted}
 };
 
-__device__ __forceinline__ double block_min_256(double v, double *red) {
+// block-wide minimum for BLOCK-thread blocks, the same in every thread; `red` holds BLOCK / 64 numbers and may be in use
+// up to the call (as with block_sum)
+template <int BLOCK>
+__device__ __forceinline__ double block_min(double v, double *red) {
     for (int o = 32; o > 0; o >>= 1) {
         const double u = __shfl_down(v, o, 64);
         v = u < v ? u : v;
@@ -259,7 +265,7 @@ __device__ __forceinline__ double block_min_256(double v, double *red) {
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     double r = red[0];
-    for (int w = 1; w < kBlock / 64; ++w) r = red[w] < r ? red[w] : r;
+    for (int w = 1; w < BLOCK / 64; ++w) r = red[w] < r ? red[w] : r;
     return r;
 }
 
@@ -278,8 +284,8 @@ __global__ __launch_bounds__(kBlock) void glsfft_prep_a_kernel(FftPrepArgs a) {
     }
     sw = block_sum<kBlock>(sw, red);
     swy = block_sum<kBlock>(swy, red);
-    tmin = block_min_256(tmin, red);
-    ntmax = block_min_256(ntmax, red);
+    tmin = block_min<kBlock>(tmin, red);
+    ntmax = block_min<kBlock>(ntmax, red);
     disorder = block_sum<kBlock>(disorder, red);
     if (threadIdx.x == 0) {
         a.part[blockIdx.x] = sw;
@@ -306,13 +312,13 @@ __global__ __launch_bounds__(kBlock) void glsfft_prep_c_kernel(FftPrepArgs a) {
         const double u = a.part[2 * kMaxPart + i];
         tmin = u < tmin ? u : tmin;
     }
-    tmin = block_min_256(tmin, red);
+    tmin = block_min<kBlock>(tmin, red);
     double ntmax = __builtin_inf();
     for (int i = threadIdx.x; i < a.nparts; i += kBlock) {
         const double u = a.part[3 * kMaxPart + i];
         ntmax = u < ntmax ? u : ntmax;
     }
-    ntmax = block_min_256(ntmax, red);
+    ntmax = block_min<kBlock>(ntmax, red);
     const double disorder = reduce_partials(a.part + 4 * kMaxPart, a.nparts, red);
     double yy = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * kBlock) {
@@ -334,80 +340,161 @@ __global__ __launch_bounds__(kBlock) void glsfft_prep_c_kernel(FftPrepArgs a) {
     }
 }
 
-// ---- extirpolation: spectral.py:18-33 ---------------------------------------------------------------
-struct SpreadArgs {
-    const double *t, *h;   // h = weights of this transform
-    const double *scal;    // scal[2..4] = {tmin, tmax, sorted}
-    double tmin_value;     // (unused)
-    int64_t n, nfft;
-    double df, fmin;
-    double *grid;          // [nfft] complex, zeroed
+// ---- prologue of a batch: B light curves on one grid (bootstrap replicates share t), one workgroup per curve ----
+struct FftBatchPrepArgs {
+    const double *t, *y, *dy;
+    const int64_t *offsets;  // [B + 1]
+    int shared_t, fit_mean;
+    double *w, *wy;   // [n_total]
+    double *scal;     // [B][8] = {YY, Werr, tmin, tmax, sorted, -, -, -}
+    // bootstrap replicates by index (spectral.py:146-148): y, dy = ONE curve, sample i of replicate b is picks[b n + i]
+    const int32_t *picks;
 };
 
+__global__ __launch_bounds__(1024) void glsfft_prep_batch_kernel(FftBatchPrepArgs a) {
+    __shared__ double red[16];
+    const int tid = threadIdx.x;
+    const int64_t off = a.offsets[blockIdx.x], n = a.offsets[blockIdx.x + 1] - off;
+    const double *t = a.shared_t ? a.t : a.t + off;
+    const int32_t *pk = a.picks ? a.picks + off : nullptr;
+    const double *y = pk ? a.y : a.y + off;
+    const double *dy = a.dy ? (pk ? a.dy : a.dy + off) : nullptr;
+    auto at = [pk](int64_t i) -> int64_t { return pk ? (int64_t)pk[i] : i; };
+    double acc = 0.0, tmin = __builtin_inf(), ntmax = __builtin_inf(), disorder = 0.0;
+    for (int64_t i = tid; i < n; i += 1024) {
+        const double e = dy ? dy[at(i)] : 1.0;
+        acc += 1.0 / (e * e);
+        const double ti = t[i];
+        tmin = ti < tmin ? ti : tmin;
+        ntmax = -ti < ntmax ? -ti : ntmax;
+        if (i > 0 && !(ti >= t[i - 1])) disorder = 1.0;   // (a NaN counts as disorder)
+    }
+    const double W = block_sum<1024>(acc, red);
+    disorder = block_sum<1024>(disorder, red);
+    tmin = block_min<1024>(tmin, red);
+    ntmax = block_min<1024>(ntmax, red);
+    double ybar = 0.0;
+    if (a.fit_mean) {
+        acc = 0.0;
+        for (int64_t i = tid; i < n; i += 1024) {
+            const double e = dy ? dy[at(i)] : 1.0;
+            acc += (1.0 / (e * e)) / W * y[at(i)];
+        }
+        ybar = block_sum<1024>(acc, red);
+    }
+    double yy = 0.0;
+    for (int64_t i = tid; i < n; i += 1024) {
+        const double e = dy ? dy[at(i)] : 1.0;
+        const double w = (1.0 / (e * e)) / W;
+        const double yc = y[at(i)] - ybar;
+        a.w[off + i] = w;
+        a.wy[off + i] = w * yc;
+        yy += w * yc * yc;
+    }
+    yy = block_sum<1024>(yy, red);
+    if (tid == 0) {
+        double *s = a.scal + (int64_t)blockIdx.x * 8;
+        s[0] = yy;
+        s[1] = W;
+        s[2] = tmin;
+        s[3] = -ntmax;
+        s[4] = disorder == 0.0 ? 1.0 : 0.0;
+    }
+}
+
+// ---- extirpolation: spectral.py:18-33 ---------------------------------------------------------------
+// One sample on one grid: where it lands and how a weight is shared out, every rule once and in the reference's order
+// of operations.  The atomic route (spread_one) and the ordered one (glsfft_deposit_kernel) are built from these, so
+// they agree to the order of their additions.  The two walks over the deposits stay two: as one visitor called by
+// both, glsfft_deposit_kernel took 128 registers instead of 124 and 402 us instead of 398 for 200 curves.
+struct Extirp {
+    // w * np.exp(2j * np.pi * fmin * (t - tmin)): the phase is fl(fl(2 pi fmin) * dt) radians
+    static __device__ __forceinline__ void prerotation(double fmin, double dt, double &sn, double &cs) {
+        sincos((6.283185307179586 * fmin) * dt, &sn, &cs);
+    }
+    // (t - tmin) * nfft * df, which "% nfft" leaves as it is on a grid that does not wrap
+    static __device__ __forceinline__ double position(double dt, double nfftd, double df) { return (dt * nfftd) * df; }
+    // tnorm = ((t - tmin) * nfft * df) % nfft
+    static __device__ __forceinline__ double tnorm(double dt, double nfftd, double df) {
+        double tn = fmod(position(dt, nfftd, df), nfftd);
+        if (tn != 0.0 && tn < 0.0) tn += nfftd;
+        return tn;
+    }
+    // tnorm % 1 == 0: one deposit of the weight itself at cell tn
+    static __device__ __forceinline__ bool whole(double tn) { return tn - __builtin_floor(tn) == 0.0; }
+    // else four neighbours from here on
+    static __device__ __forceinline__ int64_t first_neighbour(double tn, int64_t nfft) {
+        const int64_t ilo = (int64_t)(tn - 2.0);  // astype(int): truncation toward zero
+        return ilo < 0 ? 0 : (ilo > nfft - 4 ? nfft - 4 : ilo);
+    }
+    // weight h leaves (h * numerator) / divisor(j) at neighbour ilo + 3 - j, j = 0 .. 3 in the reference's order
+    static __device__ __forceinline__ double numerator(double tn, int64_t ilo) {
+        const double x = tn - (double)ilo;
+        return ((x * (x - 1.0)) * (x - 2.0)) * (x - 3.0);
+    }
+    static __device__ __forceinline__ double divisor(int j, double tn, int64_t ind) {
+        const double den[4] = {6.0, -2.0, 2.0, -6.0};  // the reference's running denominator
+        return den[j] * (tn - (double)ind);
+    }
+};
+
+// The curves of a launch and their grids, for both extirpolation kernels.
+struct ExtirpArgs {
+    const double *t, *h0, *h1;   // h0: weights of grid 0 (w y); h1: weights of grids 1 (@ 2 df) and 2 (@ df)
+    const int64_t *offsets;      // per-curve sample ranges; nullptr: one curve of n samples
+    int64_t n;
+    int shared_t, ngrid;         // ngrid = grids per curve in `grids` (3 with fit_mean, else 2; raw sums: 1)
+    int slot_first, nslots;      // deposit slots of this launch: slot 0 = grid 0 (and grid 2, which shares its
+                                 // positions and phases, when ngrid == 3); slot 1 = grid 1
+    int64_t nfft;
+    double df, fmin;
+    double *grids;               // [curve][ngrid][nfft] complex: every live cell is written
+    // (filled by fft_pipeline from the epilogue's scalars)
+    const double *ord;           // ord[curve * ord_stride + {0, 1, 2}] = {tmin, tmax, sorted}
+    int ord_stride;
+};
+
+// ---- atomics: one thread per sample, for the grids that glsfft_deposit_kernel has only zeroed ----------------------
 __device__ __forceinline__ void grid_add(double *grid, int64_t idx, double re, double im) {
     unsafeAtomicAdd(grid + 2 * idx, re);
     unsafeAtomicAdd(grid + 2 * idx + 1, im);
 }
 
-__global__ __launch_bounds__(kBlock) void glsfft_spread_kernel(SpreadArgs a) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= a.n) return;
-    const double tmin = a.scal[2];
-    if (deposit_in_order(a.scal + 2, (double)a.nfft, a.df)) return;   // glsfft_deposit_kernel has done it
-    const double dt = a.t[i] - tmin;
-    // w * np.exp(2j * np.pi * fmin * (t - tmin)): the phase is fl(fl(2 pi fmin) * dt) radians
-    const double ang = (6.283185307179586 * a.fmin) * dt;
-    double sn, cs;
-    sincos(ang, &sn, &cs);
-    const double hre = a.h[i] * cs, him = a.h[i] * sn;
-    // tnorm = ((t - tmin) * nfft * df) % nfft
-    const double nfftd = (double)a.nfft;
-    double tn = fmod((dt * nfftd) * a.df, nfftd);
-    if (tn != 0.0 && tn < 0.0) tn += nfftd;
-    if (tn - __builtin_floor(tn) == 0.0) {  // tnorm % 1 == 0: deposit whole
-        grid_add(a.grid, (int64_t)tn, hre, him);
-        return;
-    }
-    int64_t ilo = (int64_t)(tn - 2.0);  // astype(int): truncation toward zero
-    ilo = ilo < 0 ? 0 : (ilo > a.nfft - 4 ? a.nfft - 4 : ilo);
-    const double x = tn - (double)ilo;
-    const double prod = ((x * (x - 1.0)) * (x - 2.0)) * (x - 3.0);
-    const double nre = hre * prod, nim = him * prod;
-    const double den[4] = {6.0, -2.0, 2.0, -6.0};  // the reference's running denominator
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int64_t ind = ilo + (3 - j);
-        const double d = den[j] * (tn - (double)ind);
-        grid_add(a.grid, ind, nre / d, nim / d);
-    }
-}
-
-__device__ __forceinline__ void spread_one(double *grid, int64_t nfft, double dt, double h, double df,
-                                           double fmin, const double *ord) {
-    if (deposit_in_order(ord, (double)nfft, df)) return;   // glsfft_deposit_kernel has done this grid
-    const double ang = (6.283185307179586 * fmin) * dt;
-    double sn, cs;
-    sincos(ang, &sn, &cs);
-    const double hre = h * cs, him = h * sn;
+__device__ __forceinline__ void spread_one(double *grid, int64_t nfft, double dt, double h, double df, double fmin,
+                                           const double *ord) {
     const double nfftd = (double)nfft;
-    double tn = fmod((dt * nfftd) * df, nfftd);
-    if (tn != 0.0 && tn < 0.0) tn += nfftd;
-    if (tn - __builtin_floor(tn) == 0.0) {
+    if (deposit_in_order(ord, nfftd, df)) return;   // glsfft_deposit_kernel has done this grid
+    double sn, cs;
+    Extirp::prerotation(fmin, dt, sn, cs);
+    const double hre = h * cs, him = h * sn;
+    const double tn = Extirp::tnorm(dt, nfftd, df);
+    if (Extirp::whole(tn)) {
         grid_add(grid, (int64_t)tn, hre, him);
         return;
     }
-    int64_t ilo = (int64_t)(tn - 2.0);
-    ilo = ilo < 0 ? 0 : (ilo > nfft - 4 ? nfft - 4 : ilo);
-    const double x = tn - (double)ilo;
-    const double prod = ((x * (x - 1.0)) * (x - 2.0)) * (x - 3.0);
+    const int64_t ilo = Extirp::first_neighbour(tn, nfft);
+    const double prod = Extirp::numerator(tn, ilo);
     const double nre = hre * prod, nim = him * prod;
-    const double den[4] = {6.0, -2.0, 2.0, -6.0};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int64_t ind = ilo + (3 - j);
-        const double d = den[j] * (tn - (double)ind);
+        const double d = Extirp::divisor(j, tn, ind);
         grid_add(grid, ind, nre / d, nim / d);
     }
+}
+
+__global__ __launch_bounds__(kBlock) void glsfft_spread_kernel(ExtirpArgs a) {
+    const int64_t curve = blockIdx.y;
+    const int64_t off = a.offsets ? a.offsets[curve] : 0;
+    const int64_t n = a.offsets ? a.offsets[curve + 1] - off : a.n;
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const double *ord = a.ord + curve * a.ord_stride;
+    const double dt = a.t[(a.shared_t ? 0 : off) + i] - ord[0];
+    double *grids = a.grids + 2 * ((curve * a.ngrid) * a.nfft);
+    spread_one(grids, a.nfft, dt, a.h0[off + i], a.df, a.fmin, ord);
+    if (a.ngrid > 1) spread_one(grids + 2 * a.nfft, a.nfft, dt, a.h1[off + i], 2.0 * a.df, 2.0 * a.fmin, ord);   // (:110)
+    if (a.ngrid > 2) spread_one(grids + 4 * a.nfft, a.nfft, dt, a.h1[off + i], a.df, a.fmin, ord);
 }
 
 // ---- the same deposits without atomics, in a fixed order ---------------------------------------------
@@ -415,23 +502,10 @@ __device__ __forceinline__ void spread_one(double *grid, int64_t nfft, double dt
 // always so for the default n >= 1 samples per peak), grid positions rise with the sample index, so the
 // samples that touch a cell are consecutive.  A thread owns groups of four consecutive cells: a search
 // finds the first sample that can reach them, the deposits are added in sample order and stored once -
-// bitwise reproducible (the atomic kernels above add in arrival order), and the memset goes away: every
+// bitwise reproducible (the atomic kernel above adds in arrival order), and the memset goes away: every
 // cell up to the last sample's reach is written (the empty ones with zero), the rest is read by nobody.
-// Otherwise this kernel only zeroes the grid and the atomic kernels do the work (`deposit_in_order` is
-// false for them exactly then).
-struct DepositArgs {
-    const double *t, *h0, *h1;   // h0: weights of grid 0 (w y); h1: weights of grids 1 (@ 2 df) and 2 (@ df)
-    const int64_t *offsets;      // per-curve sample ranges; nullptr: one curve of n samples
-    int64_t n;
-    int shared_t, ngrid;         // ngrid = grids per curve in `grids` (3 with fit_mean, else 2)
-    int slot_first, nslots;      // slots of this launch: slot 0 = grid 0 (and grid 2, which shares its
-                                 // positions and phases, when ngrid == 3); slot 1 = grid 1
-    const double *ord;           // ord[curve * ord_stride + {0, 1, 2}] = {tmin, tmax, sorted}
-    int ord_stride;
-    int64_t nfft;
-    double df, fmin;
-    double *grids;               // [curve][ngrid][nfft] complex: every live cell is written
-};
+// Otherwise this kernel only zeroes the grid and the atomic kernel does the work (`deposit_in_order` is
+// false for it exactly then).
 
 constexpr int kDepCells = 4;                     // cells per thread
 #ifndef PDC_DEP_ITERS
@@ -441,11 +515,10 @@ constexpr int kDepIters = PDC_DEP_ITERS;         // groups of cells per thread: 
 constexpr int kDepSpan = kDepCells * kBlock * kDepIters;   // cells per workgroup
 constexpr int kDepStage = 768;                   // samples of a workgroup's range kept in LDS: position, pre-rotation, weights
 
-__global__ __launch_bounds__(kBlock) void glsfft_deposit_kernel(DepositArgs a) {
+__global__ __launch_bounds__(kBlock) void glsfft_deposit_kernel(ExtirpArgs a) {
     __shared__ double s_pos[kDepStage];
-    // round 6: the samples themselves too, with their pre-rotation exp(2 pi i fmin (t - tmin)) evaluated ONCE, by the thread
-    // that stages them (the deposit loop waited for three dependent global loads per sample and ran a sincos for every
-    // (sample, group of cells) visit: 30 us of VALU issue in a 73-us launch)
+    // the samples themselves too, with their pre-rotation exp(2 pi i fmin (t - tmin)) evaluated ONCE, by the thread that
+    // stages them (else three dependent global loads and a sincos for every (sample, group of cells) visit)
     __shared__ double s_cs[kDepStage], s_sn[kDepStage], s_h[kDepStage], s_h2[kDepStage];
     __shared__ unsigned long long s_ballot[2][kBlock / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -463,9 +536,8 @@ __global__ __launch_bounds__(kBlock) void glsfft_deposit_kernel(DepositArgs a) {
     const double *ord = a.ord + curve * a.ord_stride;
     const double dfg = g == 1 ? 2.0 * a.df : a.df, fming = g == 1 ? 2.0 * a.fmin : a.fmin;
     const double nfftd = (double)a.nfft, tmin = ord[0];
-    auto position = [&](int64_t i) -> double {   // tnorm of sample i; used only when the grid does not wrap,
-        return ((t[i] - tmin) * nfftd) * dfg;    // where the reference's "% nfft" (fmod) returns its argument
-    };
+    // tnorm of sample i: used only when the grid does not wrap, where "% nfft" (a libm fmod per probe) changes nothing
+    auto position = [&](int64_t i) -> double { return Extirp::position(t[i] - tmin, nfftd, dfg); };
     const bool ordered = n > 0 && deposit_in_order(ord, nfftd, dfg);   // (workgroup-uniform)
     int64_t w_first = 0, w_last = 0;
     bool staged = false;
@@ -514,7 +586,7 @@ __global__ __launch_bounds__(kBlock) void glsfft_deposit_kernel(DepositArgs a) {
             for (int64_t i = w_first + tid; i < w_last; i += kBlock) {
                 s_pos[i - w_first] = position(i);
                 double sn0, cs0;
-                sincos((6.283185307179586 * fming) * (t[i] - tmin), &sn0, &cs0);
+                Extirp::prerotation(fming, t[i] - tmin, sn0, cs0);
                 s_cs[i - w_first] = cs0;
                 s_sn[i - w_first] = sn0;
                 s_h[i - w_first] = h[i];
@@ -524,126 +596,110 @@ __global__ __launch_bounds__(kBlock) void glsfft_deposit_kernel(DepositArgs a) {
     }
     auto pos_at = [&](int64_t i) -> double { return staged ? s_pos[i - w_first] : position(i); };
     for (int it = 0; it < kDepIters; ++it) {
-    const int64_t g0 = G0 + ((int64_t)it * kBlock + tid) * kDepCells;
-    if (g0 >= live) break;
-    double acc_re[kDepCells], acc_im[kDepCells], twin_re[kDepCells], twin_im[kDepCells];
+        const int64_t g0 = G0 + ((int64_t)it * kBlock + tid) * kDepCells;
+        if (g0 >= live) break;
+        double acc_re[kDepCells], acc_im[kDepCells], twin_re[kDepCells], twin_im[kDepCells];
 #pragma unroll
-    for (int c = 0; c < kDepCells; ++c) acc_re[c] = acc_im[c] = twin_re[c] = twin_im[c] = 0.0;
-    if (ordered) {
-        const double lo_t = (double)(g0 - 4), hi_t = (double)(g0 + kDepCells + 4);
-        int64_t first = w_first, last = w_last;   // first sample of the workgroup's range at or beyond lo_t
-        while (first < last) {
-            const int64_t mid = (first + last) >> 1;
-            if (pos_at(mid) >= lo_t) last = mid; else first = mid + 1;
-        }
-        for (int64_t i = first; i < w_last; ++i) {
-            const double tn = pos_at(i);
-            if (!(tn < hi_t)) break;
-            int64_t ilo = 0;
-            const bool whole = tn - __builtin_floor(tn) == 0.0;
-            if (!whole) {
-                ilo = (int64_t)(tn - 2.0);
-                ilo = ilo < 0 ? 0 : (ilo > a.nfft - 4 ? a.nfft - 4 : ilo);
-                if (ilo + 3 < g0 || ilo >= g0 + kDepCells) continue;
-            } else if ((int64_t)tn < g0 || (int64_t)tn >= g0 + kDepCells) {
-                continue;
+        for (int c = 0; c < kDepCells; ++c) acc_re[c] = acc_im[c] = twin_re[c] = twin_im[c] = 0.0;
+        if (ordered) {
+            const double lo_t = (double)(g0 - 4), hi_t = (double)(g0 + kDepCells + 4);
+            int64_t first = w_first, last = w_last;   // first sample of the workgroup's range at or beyond lo_t
+            while (first < last) {
+                const int64_t mid = (first + last) >> 1;
+                if (pos_at(mid) >= lo_t) last = mid; else first = mid + 1;
             }
-            const double hi_ = staged ? s_h[i - w_first] : h[i];
-            const double h2i = !twin ? 0.0 : (staged ? s_h2[i - w_first] : h2[i]);
-            double sn, cs;
-            if (staged) {
-                sn = s_sn[i - w_first];
-                cs = s_cs[i - w_first];
-            } else {
-                sincos((6.283185307179586 * fming) * (t[i] - tmin), &sn, &cs);
-            }
-            const double hre = hi_ * cs, him = hi_ * sn;
-            const double kre = twin ? h2i * cs : 0.0, kim = twin ? h2i * sn : 0.0;
-            if (whole) {   // one deposit
-                const int64_t ind = (int64_t)tn;
+            for (int64_t i = first; i < w_last; ++i) {
+                const double tn = pos_at(i);
+                if (!(tn < hi_t)) break;
+                int64_t ilo = 0;
+                const bool whole = Extirp::whole(tn);
+                if (!whole) {
+                    ilo = Extirp::first_neighbour(tn, a.nfft);
+                    if (ilo + 3 < g0 || ilo >= g0 + kDepCells) continue;
+                } else if ((int64_t)tn < g0 || (int64_t)tn >= g0 + kDepCells) {
+                    continue;
+                }
+                const double hi_ = staged ? s_h[i - w_first] : h[i];
+                const double h2i = !twin ? 0.0 : (staged ? s_h2[i - w_first] : h2[i]);
+                double sn, cs;
+                if (staged) {
+                    sn = s_sn[i - w_first];
+                    cs = s_cs[i - w_first];
+                } else {
+                    Extirp::prerotation(fming, t[i] - tmin, sn, cs);
+                }
+                const double hre = hi_ * cs, him = hi_ * sn;
+                const double kre = twin ? h2i * cs : 0.0, kim = twin ? h2i * sn : 0.0;
+                if (whole) {   // one deposit
+                    const int64_t ind = (int64_t)tn;
 #pragma unroll
-                for (int c = 0; c < kDepCells; ++c)
-                    if (ind == g0 + c) {
-                        acc_re[c] += hre;
-                        acc_im[c] += him;
-                        twin_re[c] += kre;
-                        twin_im[c] += kim;
-                    }
-                continue;
-            }
-            const double x = tn - (double)ilo;
-            const double prod = ((x * (x - 1.0)) * (x - 2.0)) * (x - 3.0);
-            const double nre = hre * prod, nim = him * prod, mre = kre * prod, mim = kim * prod;
-            const double den[4] = {6.0, -2.0, 2.0, -6.0};
+                    for (int c = 0; c < kDepCells; ++c)
+                        if (ind == g0 + c) {
+                            acc_re[c] += hre;
+                            acc_im[c] += him;
+                            twin_re[c] += kre;
+                            twin_im[c] += kim;
+                        }
+                    continue;
+                }
+                const double prod = Extirp::numerator(tn, ilo);
+                const double nre = hre * prod, nim = him * prod, mre = kre * prod, mim = kim * prod;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int64_t ind = ilo + (3 - j);
-                if (ind < g0 || ind >= g0 + kDepCells) continue;
-                const double d = den[j] * (tn - (double)ind);
-                const double vre = nre / d, vim = nim / d;
-                const double ure = twin ? mre / d : 0.0, uim = twin ? mim / d : 0.0;
+                for (int j = 0; j < 4; ++j) {
+                    const int64_t ind = ilo + (3 - j);
+                    if (ind < g0 || ind >= g0 + kDepCells) continue;
+                    const double d = Extirp::divisor(j, tn, ind);
+                    const double vre = nre / d, vim = nim / d;
+                    const double ure = twin ? mre / d : 0.0, uim = twin ? mim / d : 0.0;
 #pragma unroll
-                for (int c = 0; c < kDepCells; ++c)
-                    if (ind == g0 + c) {
-                        acc_re[c] += vre;
-                        acc_im[c] += vim;
-                        twin_re[c] += ure;
-                        twin_im[c] += uim;
-                    }
+                    for (int c = 0; c < kDepCells; ++c)
+                        if (ind == g0 + c) {
+                            acc_re[c] += vre;
+                            acc_im[c] += vim;
+                            twin_re[c] += ure;
+                            twin_im[c] += uim;
+                        }
+                }
             }
         }
+        double *out = a.grids + 2 * ((curve * a.ngrid + g) * a.nfft + g0);
+        double *out2 = a.grids + 2 * ((curve * a.ngrid + 2) * a.nfft + g0);
+#pragma unroll
+        for (int c = 0; c < kDepCells; ++c)
+            if (g0 + c < a.nfft) {
+                out[2 * c] = acc_re[c];
+                out[2 * c + 1] = acc_im[c];
+                if (twin) {
+                    out2[2 * c] = twin_re[c];
+                    out2[2 * c + 1] = twin_im[c];
+                }
+            }
     }
-    double *out = a.grids + 2 * ((curve * a.ngrid + g) * a.nfft + g0);
-    double *out2 = a.grids + 2 * ((curve * a.ngrid + 2) * a.nfft + g0);
-#pragma unroll
-    for (int c = 0; c < kDepCells; ++c)
-        if (g0 + c < a.nfft) {
-            out[2 * c] = acc_re[c];
-            out[2 * c + 1] = acc_im[c];
-            if (twin) {
-                out2[2 * c] = twin_re[c];
-                out2[2 * c + 1] = twin_im[c];
-            }
-        }
-    }
-}
-
-// All three (or two) grids of one curve in a single launch: (w*y @ df), (w @ 2 df), (w @ df).
-struct Spread3Args {
-    const double *t, *wy, *w, *scal;
-    int64_t n, nfft;
-    double df, fmin;
-    double *grids;  // [ngrid][nfft] complex, zeroed
-    int fit_mean;
-};
-
-__global__ __launch_bounds__(kBlock) void glsfft_spread3_kernel(Spread3Args a) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= a.n) return;
-    const double dt = a.t[i] - a.scal[2];
-    spread_one(a.grids, a.nfft, dt, a.wy[i], a.df, a.fmin, a.scal + 2);
-    spread_one(a.grids + 2 * a.nfft, a.nfft, dt, a.w[i], 2.0 * a.df, 2.0 * a.fmin, a.scal + 2);   // (:110)
-    if (a.fit_mean) spread_one(a.grids + 4 * a.nfft, a.nfft, dt, a.w[i], a.df, a.fmin, a.scal + 2);
 }
 
 // ---- epilogue: spectral.py:34-39 then :113-132 ----------------------------------------------------------
 struct FftEpiArgs {
-    const cplx *gh, *g2, *g1;  // transforms of (w y @ df), (w @ 2 df), (w @ df, may be null)
-    const double *scal;
-    const double *ypart;       // partial YY sums (nparts of them)
-    int nparts;
-    int64_t nfft, nf;
+    const double *ypart;   // partial YY sums of a single curve (nparts of them); nullptr: YY = scal[0]
+    int nparts, psd;
+    int64_t nf;
+    double *power;         // [curve][nf]; glsfft_raw_sums_kernel: S
+    double *raw_c;         // glsfft_raw_sums_kernel: C
+    const double *scal;    // scal[curve * scal_stride + {0 .. 4}] = {YY, Werr, tmin, tmax, sorted}
+    int scal_stride;
+    // (filled by fft_pipeline)
+    int ngrid;
+    const cplx *result;    // [curve][ngrid][nfft]: transforms of (w y @ df), (w @ 2 df), (w @ df) with fit_mean
+    int64_t nfft;
     double df, fmin;
-    int fit_mean, psd;
-    double *power;             // or raw outputs
-    double *raw_s, *raw_c;
-    double tmin_value;
-    int raw;
 };
 
-// fftgrid *= exp(2j pi tmin f), f = fmin + df*arange(nf); C = nfft*re, S = nfft*im
+// fftgrid[:nf] of pocketfft's ifft, which divides by nfft (the reference multiplies it back: do both so that the
+// roundings match), *= exp(2j pi tmin f); C = nfft*re, S = nfft*im
 __device__ __forceinline__ void finish_sum(cplx z, double tmin, double f, double nfftd, double &S,
                                            double &C) {
+    const double scale = 1.0 / nfftd;
+    z.re *= scale;
+    z.im *= scale;
     if (tmin != 0.0) {
         const double ang = (6.283185307179586 * tmin) * f;
         double sn, cs;
@@ -656,210 +712,60 @@ __device__ __forceinline__ void finish_sum(cplx z, double tmin, double f, double
 
 __global__ __launch_bounds__(kBlock) void glsfft_epilogue_kernel(FftEpiArgs a) {
     __shared__ double red[kBlock / 64];
-    const double YY = a.raw ? 0.0 : reduce_partials(a.ypart, a.nparts, red);
+    const int64_t b = blockIdx.y;
+    const double *sc = a.scal + b * a.scal_stride;
+    const double YY = a.ypart ? reduce_partials(a.ypart, a.nparts, red) : sc[0];   // (workgroup-uniform)
     const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (j >= a.nf) return;
-    const double nfftd = (double)a.nfft;
-    // pocketfft's ifft divides by nfft and the reference multiplies it back: do both so that the
-    // roundings match
-    const double scale = 1.0 / nfftd;
-    if (a.raw) {
-        const double tmin = a.tmin_value;
-        cplx z = a.gh[j];
-        z.re *= scale;
-        z.im *= scale;
-        double S, C;
-        finish_sum(z, tmin, a.fmin + a.df * (double)j, nfftd, S, C);
-        a.raw_s[j] = S;
-        a.raw_c[j] = C;
-        return;
-    }
-    const double tmin = a.scal[2];
-    const double f = a.fmin + a.df * (double)j;
-    double Sh, Ch, S2, C2, S = 0.0, C = 0.0;
-    cplx z = a.gh[j];
-    z.re *= scale;
-    z.im *= scale;
-    finish_sum(z, tmin, f, nfftd, Sh, Ch);
-    z = a.g2[j];
-    z.re *= scale;
-    z.im *= scale;
-    finish_sum(z, tmin, 2.0 * a.fmin + (2.0 * a.df) * (double)j, nfftd, S2, C2);
-    double p;
-    if (a.fit_mean) {
-        z = a.g1[j];
-        z.re *= scale;
-        z.im *= scale;
-        finish_sum(z, tmin, f, nfftd, S, C);
-        p = gls_power_from_sums<true>(Sh, Ch, S, C, S2, C2, YY, a.scal[1], a.psd);
-    } else {
-        p = gls_power_from_sums<false>(Sh, Ch, S, C, S2, C2, YY, a.scal[1], a.psd);
-    }
-    a.power[j] = p;
-}
-
-
-// ---- batched form: B light curves on one grid (bootstrap replicates share t) -----------------------
-struct FftBatchArgs {
-    const double *t, *y, *dy;
-    const int64_t *offsets;  // [B + 1]
-    int shared_t, fit_mean, psd, ngrid;
-    int64_t nfft, nf;
-    double df, fmin;
-    double *w, *wy;   // [n_total]
-    double *scal;     // [B][8] = {YY, Werr, tmin, tmax, sorted, -, -, -}
-    cplx *grids;      // [B][ngrid][nfft]
-    const cplx *result;  // where the transforms ended up (grids or scratch), same layout
-    double *power;    // [B][nf]
-    // bootstrap replicates by index (spectral.py:146-148): y, dy = ONE curve, sample i of replicate b is picks[b n + i]
-    const int32_t *picks = nullptr;
-};
-
-__global__ __launch_bounds__(1024) void glsfft_prep_batch_kernel(FftBatchArgs a) {
-    __shared__ double red[16];
-    const int tid = threadIdx.x;
-    const int64_t off = a.offsets[blockIdx.x], n = a.offsets[blockIdx.x + 1] - off;
-    const double *t = a.shared_t ? a.t : a.t + off;
-    const int32_t *pk = a.picks ? a.picks + off : nullptr;
-    const double *y = pk ? a.y : a.y + off;
-    const double *dy = a.dy ? (pk ? a.dy : a.dy + off) : nullptr;
-    auto at = [pk](int64_t i) -> int64_t { return pk ? (int64_t)pk[i] : i; };
-    double acc = 0.0, tmin = __builtin_inf(), ntmax = __builtin_inf(), disorder = 0.0;
-    for (int64_t i = tid; i < n; i += 1024) {
-        const double e = dy ? dy[at(i)] : 1.0;
-        acc += 1.0 / (e * e);
-        const double ti = t[i];
-        tmin = ti < tmin ? ti : tmin;
-        ntmax = -ti < ntmax ? -ti : ntmax;
-        if (i > 0 && !(ti >= t[i - 1])) disorder = 1.0;   // (a NaN counts as disorder)
-    }
-    const double W = block_sum<1024>(acc, red);
-    disorder = block_sum<1024>(disorder, red);
-    auto block_min = [&](double v) -> double {
-        for (int o = 32; o > 0; o >>= 1) {
-            const double u = __shfl_down(v, o, 64);
-            v = u < v ? u : v;
-        }
-        __syncthreads();
-        if ((tid & 63) == 0) red[tid >> 6] = v;
-        __syncthreads();
-        v = red[0];
-        for (int w = 1; w < 16; ++w) v = red[w] < v ? red[w] : v;
-        __syncthreads();
-        return v;
-    };
-    tmin = block_min(tmin);
-    ntmax = block_min(ntmax);
-    double ybar = 0.0;
-    if (a.fit_mean) {
-        acc = 0.0;
-        for (int64_t i = tid; i < n; i += 1024) {
-            const double e = dy ? dy[at(i)] : 1.0;
-            acc += (1.0 / (e * e)) / W * y[at(i)];
-        }
-        ybar = block_sum<1024>(acc, red);
-    }
-    double yy = 0.0;
-    for (int64_t i = tid; i < n; i += 1024) {
-        const double e = dy ? dy[at(i)] : 1.0;
-        const double w = (1.0 / (e * e)) / W;
-        const double yc = y[at(i)] - ybar;
-        a.w[off + i] = w;
-        a.wy[off + i] = w * yc;
-        yy += w * yc * yc;
-    }
-    yy = block_sum<1024>(yy, red);
-    if (tid == 0) {
-        double *s = a.scal + (int64_t)blockIdx.x * 8;
-        s[0] = yy;
-        s[1] = W;
-        s[2] = tmin;
-        s[3] = -ntmax;
-        s[4] = disorder == 0.0 ? 1.0 : 0.0;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void glsfft_spread_batch_kernel(FftBatchArgs a) {
-    const int64_t b = blockIdx.y;
-    const int64_t off = a.offsets[b], n = a.offsets[b + 1] - off;
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const double *t = a.shared_t ? a.t : a.t + off;
-    const double *ord = a.scal + b * 8 + 2;
-    const double dt = t[i] - ord[0];
-    double *g0 = reinterpret_cast<double *>(a.grids + (b * a.ngrid) * a.nfft);
-    spread_one(g0, a.nfft, dt, a.wy[off + i], a.df, a.fmin, ord);
-    spread_one(g0 + 2 * a.nfft, a.nfft, dt, a.w[off + i], 2.0 * a.df, 2.0 * a.fmin, ord);
-    if (a.fit_mean) spread_one(g0 + 4 * a.nfft, a.nfft, dt, a.w[off + i], a.df, a.fmin, ord);
-}
-
-__global__ __launch_bounds__(kBlock) void glsfft_epilogue_batch_kernel(FftBatchArgs a) {
-    const int64_t b = blockIdx.y;
-    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (j >= a.nf) return;
-    const double nfftd = (double)a.nfft, scale = 1.0 / nfftd;
-    const double *sc = a.scal + b * 8;
-    const double tmin = sc[2];
+    const double nfftd = (double)a.nfft, tmin = sc[2];
     const cplx *g = a.result + (b * a.ngrid) * a.nfft;
     const double f = a.fmin + a.df * (double)j;
     double Sh, Ch, S2, C2, S = 0.0, C = 0.0;
-    cplx z = g[j];
-    z.re *= scale;
-    z.im *= scale;
-    finish_sum(z, tmin, f, nfftd, Sh, Ch);
-    z = g[a.nfft + j];
-    z.re *= scale;
-    z.im *= scale;
-    finish_sum(z, tmin, 2.0 * a.fmin + (2.0 * a.df) * (double)j, nfftd, S2, C2);
+    finish_sum(g[j], tmin, f, nfftd, Sh, Ch);
+    finish_sum(g[a.nfft + j], tmin, 2.0 * a.fmin + (2.0 * a.df) * (double)j, nfftd, S2, C2);
     double p;
-    if (a.fit_mean) {
-        z = g[2 * a.nfft + j];
-        z.re *= scale;
-        z.im *= scale;
-        finish_sum(z, tmin, f, nfftd, S, C);
-        p = gls_power_from_sums<true>(Sh, Ch, S, C, S2, C2, sc[0], sc[1], a.psd);
+    if (a.ngrid == 3) {
+        finish_sum(g[2 * a.nfft + j], tmin, f, nfftd, S, C);
+        p = gls_power_from_sums<true>(Sh, Ch, S, C, S2, C2, YY, sc[1], a.psd);
     } else {
-        p = gls_power_from_sums<false>(Sh, Ch, S, C, S2, C2, sc[0], sc[1], a.psd);
+        p = gls_power_from_sums<false>(Sh, Ch, S, C, S2, C2, YY, sc[1], a.psd);
     }
     a.power[b * a.nf + j] = p;
 }
 
-// NaN-aware maximum and its first index per row (Signal.amax / argmax, core.py:202-215)
+// pdc_trig_sums_fft: one curve, one grid, S and C as they are
+__global__ __launch_bounds__(kBlock) void glsfft_raw_sums_kernel(FftEpiArgs a) {
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= a.nf) return;
+    double S, C;
+    finish_sum(a.result[j], a.scal[2], a.fmin + a.df * (double)j, (double)a.nfft, S, C);
+    a.power[j] = S;
+    a.raw_c[j] = C;
+}
+
+// NaN-aware maximum and its first index per row (Signal.amax / argmax, core.py:202-215).  Wave w takes the w-th
+// quarter of the row, its lanes stride through it: ascending ranges per lane and per wave, as ArgMax asks.
 __global__ __launch_bounds__(kBlock) void row_nanmax_kernel(const double *power, int64_t nf,
                                                             double *amax, int64_t *argmax) {
     __shared__ double rv[kBlock / 64];
     __shared__ long long ri[kBlock / 64];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (scalar: so is its range)
     const double *x = power + (int64_t)blockIdx.x * nf;
-    double best = 0.0;
-    long long bi = -1;
-    for (int64_t i = threadIdx.x; i < nf; i += kBlock) {
-        const double v = x[i];
-        if (v == v && (bi < 0 || v > best)) {
-            best = v;
-            bi = i;
-        }
+    const int64_t quarter = (nf + kBlock / 64 - 1) / (kBlock / 64);
+    const int64_t beg = wave * quarter, end = beg + quarter < nf ? beg + quarter : nf;
+    ArgMax m;
+    // (four loads in flight: one at a time, a wave on its own quarter took 20 us for 200 rows of 12000 against the 17 of
+    // a workgroup striding over the row together)
+    for (int64_t i = beg + lane; i < end; i += 4 * 64) {
+        double v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = i + 64 * u < end ? x[i + 64 * u] : __builtin_nan("");
+#pragma unroll
+        for (int u = 0; u < 4; ++u) m.take(v[u], i + 64 * u);
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_down(best, o, 64);
-        const long long oi = __shfl_down(bi, o, 64);
-        if (oi >= 0 && (bi < 0 || ov > best || (ov == best && oi < bi))) {
-            best = ov;
-            bi = oi;
-        }
-    }
-    if ((threadIdx.x & 63) == 0) {
-        rv[threadIdx.x >> 6] = best;
-        ri[threadIdx.x >> 6] = bi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kBlock / 64; ++w)
-            if (ri[w] >= 0 && (bi < 0 || rv[w] > best || (rv[w] == best && ri[w] < bi))) {
-                best = rv[w];
-                bi = ri[w];
-            }
-        if (amax) amax[blockIdx.x] = bi >= 0 ? best : __builtin_nan("");
-        if (argmax) argmax[blockIdx.x] = bi;
+    if (m.block_fold<kBlock / 64>(rv, ri, lane, wave)) {
+        if (amax) amax[blockIdx.x] = m.j >= 0 ? m.v : __builtin_nan("");
+        if (argmax) argmax[blockIdx.x] = m.j;
     }
 }
 
@@ -903,8 +809,9 @@ cplx *inverse_fft(hipStream_t st, cplx *a, cplx *b, int64_t N, int batch = 1, in
         int lds_bits = 0;
         if (!no_lds && bits >= 5 && N >= 4096)  // a workgroup covers R * JT = 4096 points
             lds_bits = bits >= 8 ? 8 : bits;
+        const int done = lds_bits ? lds_bits : r;   // bits of this pass
+        const int64_t keep = (bits == done && keep_out >= 0) ? keep_out : N;  // final pass only
         if (lds_bits) {
-            const int64_t keep = (bits == lds_bits && keep_out >= 0) ? keep_out : N;  // final pass only
             const int64_t R = (int64_t)1 << lds_bits;
             const int jt = 256 / (int)(R / 16);
             const dim3 grid((unsigned)((N / R) / jt), (unsigned)batch);
@@ -914,22 +821,16 @@ cplx *inverse_fft(hipStream_t st, cplx *a, cplx *b, int64_t N, int batch = 1, in
                 case 6: hipLaunchKernelGGL(fft_pass_lds_kernel<4>, grid, dim3(256), 0, st, src, dst, N, Ns, keep, lv); break;
                 default: hipLaunchKernelGGL(fft_pass_lds_kernel<2>, grid, dim3(256), 0, st, src, dst, N, Ns, keep, lv); break;
             }
-            Ns <<= lds_bits;
-            bits -= lds_bits;
-            cplx *tmp = src;
-            src = dst;
-            dst = tmp;
-            continue;
+        } else {
+            switch (r) {
+                case 4: launch_pass<16>(st, src, dst, N, Ns, batch, keep, lv); break;
+                case 3: launch_pass<8>(st, src, dst, N, Ns, batch, keep, lv); break;
+                case 2: launch_pass<4>(st, src, dst, N, Ns, batch, keep, lv); break;
+                default: launch_pass<2>(st, src, dst, N, Ns, batch, keep, lv); break;
+            }
         }
-        const int64_t keep = (bits == r && keep_out >= 0) ? keep_out : N;  // final pass only
-        switch (r) {
-            case 4: launch_pass<16>(st, src, dst, N, Ns, batch, keep, lv); break;
-            case 3: launch_pass<8>(st, src, dst, N, Ns, batch, keep, lv); break;
-            case 2: launch_pass<4>(st, src, dst, N, Ns, batch, keep, lv); break;
-            default: launch_pass<2>(st, src, dst, N, Ns, batch, keep, lv); break;
-        }
-        Ns <<= r;
-        bits -= r;
+        Ns <<= done;
+        bits -= done;
         cplx *tmp = src;
         src = dst;
         dst = tmp;
@@ -937,28 +838,65 @@ cplx *inverse_fft(hipStream_t st, cplx *a, cplx *b, int64_t N, int batch = 1, in
     return src;
 }
 
-void launch_deposit(hipStream_t st, const DepositArgs &d, int64_t n_curves) {
-    hipLaunchKernelGGL(glsfft_deposit_kernel, dim3((unsigned)((d.nfft + kDepSpan - 1) / kDepSpan), (unsigned)(n_curves * d.nslots)),
-                       dim3(kBlock), 0, st, d);
+// The `n_curves` curves of `x`, the longest of n_max samples: deposits -> atomics -> inverse FFT -> epilogue (-> row
+// maxima).  `scratch`: ping-pong partner of x.grids; `e`: the caller's part of the epilogue's arguments.
+// grid_by_grid (one curve): the passes of one grid after the other, see pdc_gls_scan_fft_dev.
+int fft_pipeline(hipStream_t st, ExtirpArgs x, int64_t n_curves, int64_t n_max, cplx *scratch, bool grid_by_grid,
+                 FftEpiArgs e, double *amax = nullptr, int64_t *argmax = nullptr) {
+    x.ord = e.scal + 2;
+    x.ord_stride = e.scal_stride;
+    // ALL grids' deposits in one launch up front: a deposit launch is a chain of dependent searches, ~50 us whatever it
+    // writes, and only the live fifth of a grid is written
+    hipLaunchKernelGGL(glsfft_deposit_kernel, dim3((unsigned)((x.nfft + kDepSpan - 1) / kDepSpan), (unsigned)(n_curves * x.nslots)),
+                       dim3(kBlock), 0, st, x);
+    if (n_max > 0)
+        hipLaunchKernelGGL(glsfft_spread_kernel, dim3((unsigned)((n_max + kBlock - 1) / kBlock), (unsigned)n_curves),
+                           dim3(kBlock), 0, st, x);
+    PDC_HIP(hipGetLastError());
+    cplx *grids = reinterpret_cast<cplx *>(x.grids);
+    if (grid_by_grid) {   // (every grid's transform ends in the same half of its ping-pong: the layout of the results holds)
+        for (int g = 0; g < x.ngrid; ++g)
+            e.result = inverse_fft(st, grids + g * x.nfft, scratch + g * x.nfft, x.nfft, 1, e.nf, LiveArgs{x.ord, 0, 1, g, x.df}) - g * x.nfft;
+    } else {
+        e.result = inverse_fft(st, grids, scratch, x.nfft, (int)(n_curves * x.ngrid), e.nf, LiveArgs{x.ord, x.ord_stride, x.ngrid, 0, x.df});
+    }
+    PDC_HIP(hipGetLastError());
+    e.ngrid = x.ngrid;
+    e.nfft = x.nfft;
+    e.df = x.df;
+    e.fmin = x.fmin;
+    const dim3 bins((unsigned)((e.nf + kBlock - 1) / kBlock), (unsigned)n_curves);
+    if (e.raw_c)
+        hipLaunchKernelGGL(glsfft_raw_sums_kernel, bins, dim3(kBlock), 0, st, e);
+    else
+        hipLaunchKernelGGL(glsfft_epilogue_kernel, bins, dim3(kBlock), 0, st, e);
+    if (amax || argmax) hipLaunchKernelGGL(row_nanmax_kernel, dim3((unsigned)n_curves), dim3(kBlock), 0, st, e.power, e.nf, amax, argmax);
+    PDC_HIP(hipGetLastError());
+    return PDC_OK;
 }
 
+// Workspace: the weights of n samples, `scal_bytes` of scalars (and partials), n_grids grids and their ping-pong partner
+// (both contiguous: batched FFT stride = nfft), power_rows rows of nf powers.
 struct FftLayout {
-    int64_t wy, w, scal, grid[3], scratch, total;
+    int64_t wy, w, scal, grids, scratch, power, total;
 };
 
-FftLayout fft_layout(int64_t n, int64_t nfft) {
-    auto up = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
+FftLayout fft_layout(int64_t n, int64_t scal_bytes, int64_t n_grids, int64_t nfft, int64_t power_rows = 0, int64_t nf = 0) {
     FftLayout L;
-    L.wy = 0;
-    L.w = up(n * 8);
-    L.scal = L.w + up(n * 8);
-    int64_t off = L.scal + up((6 * kMaxPart + 8) * 8);  // scal[8] | part[5][kMaxPart] | ypart[kMaxPart]
-    for (int g = 0; g < 3; ++g) L.grid[g] = off + g * nfft * 16;  // contiguous: batched FFT stride = nfft
-    off += up(3 * nfft * 16);
-    L.scratch = off;
-    L.total = off + up(3 * nfft * 16);  // ping-pong partner of all three grids
+    int64_t at = 0;
+    auto sub = [&](int64_t bytes) { const int64_t o = at; at += (bytes + 255) & ~(int64_t)255; return o; };
+    L.wy = sub(n * 8);
+    L.w = sub(n * 8);
+    L.scal = sub(scal_bytes);
+    L.grids = sub(n_grids * nfft * 16);
+    L.scratch = sub(n_grids * nfft * 16);
+    L.power = sub(power_rows * nf * 8);
+    L.total = at;
     return L;
 }
+
+// one curve: scal[8] | part[5][kMaxPart] | ypart[kMaxPart], and three grids whether fit_mean or not
+FftLayout fft_layout_single(int64_t n, int64_t nfft) { return fft_layout(n, (6 * kMaxPart + 8) * 8, 3, nfft); }
 
 }  // namespace
 
@@ -966,7 +904,7 @@ extern "C" {
 
 int64_t pdc_gls_fft_work_bytes(int64_t n, int64_t nf) {
     if (n < 0 || nf < 0) return -1;
-    return fft_layout(n, fft_length(nf > 0 ? nf : 1)).total;
+    return fft_layout_single(n, fft_length(nf > 0 ? nf : 1)).total;
 }
 
 int pdc_gls_scan_fft_dev(int device, void *stream, const double *d_t, const double *d_y,
@@ -976,7 +914,7 @@ int pdc_gls_scan_fft_dev(int device, void *stream, const double *d_t, const doub
     PDC_REQUIRE(n >= 0 && nf >= 0 && nf < ((int64_t)1 << 40), "gls_fft: bad size");
     if (nf == 0) return PDC_OK;
     const int64_t nfft = fft_length(nf);
-    const FftLayout L = fft_layout(n, nfft);
+    const FftLayout L = fft_layout_single(n, nfft);
     PDC_REQUIRE(work && work_bytes >= L.total, "gls_fft: workspace too small (%lld < %lld bytes)",
                 (long long)work_bytes, (long long)L.total);
     PDC_TRY(use_device(device));
@@ -985,8 +923,6 @@ int pdc_gls_scan_fft_dev(int device, void *stream, const double *d_t, const doub
     double *wy = reinterpret_cast<double *>(base + L.wy);
     double *w = reinterpret_cast<double *>(base + L.w);
     double *scal = reinterpret_cast<double *>(base + L.scal);
-    cplx *grid[3], *scratch = reinterpret_cast<cplx *>(base + L.scratch);
-    for (int g = 0; g < 3; ++g) grid[g] = reinterpret_cast<cplx *>(base + L.grid[g]);
 
     int nparts = (int)((n + 4 * kBlock - 1) / (4 * kBlock));
     nparts = nparts < 1 ? 1 : (nparts > kMaxPart ? kMaxPart : nparts);
@@ -997,51 +933,14 @@ int pdc_gls_scan_fft_dev(int device, void *stream, const double *d_t, const doub
 
     const int ngrid = fit_mean ? 3 : 2;
     // One grid's ping-pong (32 B per point) may fit in the 256 MiB Infinity Cache while all of them do
-    // not: then zero, fill and transform the grids one after the other so that each stays cache-warm
-    // (measured at nfft = 2^23: 0.66 vs 0.69 ms); otherwise one memset, one fused spread launch and
-    // batched FFT passes (gridDim.y = ngrid; 6.4 vs 6.7 ms at nfft = 2^26).
+    // not: then the PASSES grid by grid, so that each grid's ping-pong stays cache-warm (measured at
+    // nfft = 2^23: 0.66 vs 0.69 ms); otherwise batched FFT passes (gridDim.y = ngrid; 6.4 vs 6.7 ms at
+    // nfft = 2^26).  The deposits are one launch either way (fft_pipeline).
     const int64_t mall = (int64_t)256 << 20;
-    const cplx *result[3] = {nullptr, nullptr, nullptr};
-    // (round 6: ALL grids' deposits in one launch up front in both branches - a deposit launch is a chain of dependent
-    // searches, ~50 us whatever it writes, and only the live fifth of a grid is written: 27 MB that the other grids'
-    // passes may push out of the Infinity Cache cost ~5 us to read back, a second launch cost 50.)
-    launch_deposit(st, DepositArgs{d_t, wy, w, nullptr, n, 0, ngrid, 0, 2, scal + 2, 0, nfft, df, fmin,
-                                   reinterpret_cast<double *>(grid[0])}, 1);
-    if (n > 0) {
-        Spread3Args s3{d_t, wy, w, scal, n, nfft, df, fmin, reinterpret_cast<double *>(grid[0]), fit_mean};
-        hipLaunchKernelGGL(glsfft_spread3_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)),
-                           dim3(kBlock), 0, st, s3);
-    }
-    if (nfft * 32 <= mall && (int64_t)ngrid * nfft * 32 > mall) {
-        // the PASSES grid by grid: a grid's 256 MiB ping-pong is what has to stay cache-warm
-        for (int g = 0; g < ngrid; ++g)
-            result[g] = inverse_fft(st, grid[g], scratch + g * nfft, nfft, 1, nf, LiveArgs{scal + 2, 0, 1, g, df});
-    } else {
-        const cplx *res = inverse_fft(st, grid[0], scratch, nfft, ngrid, nf, LiveArgs{scal + 2, 0, ngrid, 0, df});
-        for (int g = 0; g < ngrid; ++g) result[g] = res + g * nfft;
-    }
-    PDC_HIP(hipGetLastError());
-    FftEpiArgs e;
-    e.gh = result[0];
-    e.g2 = result[1];
-    e.g1 = result[2];
-    e.scal = scal;
-    e.ypart = p.ypart;
-    e.nparts = nparts;
-    e.nfft = nfft;
-    e.nf = nf;
-    e.df = df;
-    e.fmin = fmin;
-    e.fit_mean = fit_mean;
-    e.psd = psd;
-    e.power = d_power;
-    e.raw_s = e.raw_c = nullptr;
-    e.tmin_value = 0.0;
-    e.raw = 0;
-    hipLaunchKernelGGL(glsfft_epilogue_kernel, dim3((unsigned)((nf + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, st, e);
-    PDC_HIP(hipGetLastError());
-    return PDC_OK;
+    const bool grid_by_grid = nfft * 32 <= mall && (int64_t)ngrid * nfft * 32 > mall;
+    return fft_pipeline(st, ExtirpArgs{d_t, wy, w, nullptr, n, 0, ngrid, 0, 2, nfft, df, fmin, reinterpret_cast<double *>(base + L.grids)},
+                        1, n, reinterpret_cast<cplx *>(base + L.scratch), grid_by_grid,
+                        FftEpiArgs{p.ypart, nparts, psd, nf, d_power, nullptr, scal, 0});
 }
 
 int pdc_gls_scan_fft(const double *t, const double *y, const double *dy, int64_t n, double fmin,
@@ -1087,67 +986,27 @@ int fft_batch_host(const double *t, const double *y, const double *dy, const int
     chunk = chunk < 1 ? 1 : chunk;
     chunk = chunk > n_curves ? n_curves : chunk;
     chunk = chunk > 65535 / ngrid ? 65535 / ngrid : chunk;
-    auto up = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
-    const int64_t o_w = 0, o_wy = up(n_total * 8), o_scal = o_wy + up(n_total * 8);
-    const int64_t o_grid = o_scal + up(n_curves * 64);
-    const int64_t o_scratch = o_grid + up(chunk * ngrid * nfft * 16);
-    const int64_t o_pow = o_scratch + up(chunk * ngrid * nfft * 16);
-    const int64_t wb = o_pow + up(chunk * nf * 8);
+    const FftLayout L = fft_layout(n_total, n_curves * 64, chunk * ngrid, nfft, chunk, nf);
     in.upload(hc, t, y, dy, offsets, n_curves, picks != nullptr);   // (bootstrap: one curve of values / errors on the device)
     const int32_t *d_picks = hc.in(SLOT_OUT0, picks, n_total * 4);
     double *d_amax = amax_out ? hc.out<double>(SLOT_OUT1, n_curves * 8) : nullptr;
     int64_t *d_arg = argmax_out ? hc.out<int64_t>(SLOT_OUT2, n_curves * 8) : nullptr;
-    char *base = hc.out<char>(SLOT_WORK, wb);
+    char *base = hc.out<char>(SLOT_WORK, L.total);
     PDC_TRY(hc.status);
     hipStream_t st = hc.stream();
-    FftBatchArgs a;
-    a.picks = d_picks;
-    a.t = in.d_t;
-    a.y = in.d_y;
-    a.dy = in.d_dy;
-    a.offsets = in.d_off;
-    a.shared_t = shared_t;
-    a.fit_mean = fit_mean;
-    a.psd = psd;
-    a.ngrid = ngrid;
-    a.nfft = nfft;
-    a.nf = nf;
-    a.df = df;
-    a.fmin = fmin;
-    a.w = reinterpret_cast<double *>(base + o_w);
-    a.wy = reinterpret_cast<double *>(base + o_wy);
-    a.scal = reinterpret_cast<double *>(base + o_scal);
-    a.grids = reinterpret_cast<cplx *>(base + o_grid);
-    a.result = nullptr;
-    a.power = reinterpret_cast<double *>(base + o_pow);
-    cplx *scratch = reinterpret_cast<cplx *>(base + o_scratch);
-    hipLaunchKernelGGL(glsfft_prep_batch_kernel, dim3((unsigned)n_curves), dim3(1024), 0, st, a);
+    double *w = reinterpret_cast<double *>(base + L.w), *wy = reinterpret_cast<double *>(base + L.wy);
+    double *scal = reinterpret_cast<double *>(base + L.scal), *power = reinterpret_cast<double *>(base + L.power);
+    hipLaunchKernelGGL(glsfft_prep_batch_kernel, dim3((unsigned)n_curves), dim3(1024), 0, st,
+                       FftBatchPrepArgs{in.d_t, in.d_y, in.d_dy, in.d_off, shared_t, fit_mean, w, wy, scal, d_picks});
     PDC_HIP(hipGetLastError());
-    const double *scal_all = a.scal;
     for (int64_t c0 = 0; c0 < n_curves; c0 += chunk) {
         const int64_t bc = n_curves - c0 < chunk ? n_curves - c0 : chunk;
-        FftBatchArgs c = a;
-        c.offsets = a.offsets + c0;
-        c.scal = const_cast<double *>(scal_all) + c0 * 8;
-        launch_deposit(st, DepositArgs{a.t, a.wy, a.w, c.offsets, 0, shared_t, ngrid, 0, 2, c.scal + 2, 8, nfft, df, fmin,
-                                       reinterpret_cast<double *>(c.grids)}, bc);
-        if (n_max > 0) {
-            hipLaunchKernelGGL(glsfft_spread_batch_kernel,
-                               dim3((unsigned)((n_max + kBlock - 1) / kBlock), (unsigned)bc), dim3(kBlock),
-                               0, st, c);
-            PDC_HIP(hipGetLastError());
-        }
-        c.result = inverse_fft(st, c.grids, scratch, nfft, (int)(bc * ngrid), nf, LiveArgs{c.scal + 2, 8, ngrid, 0, df});
-        PDC_HIP(hipGetLastError());
-        hipLaunchKernelGGL(glsfft_epilogue_batch_kernel,
-                           dim3((unsigned)((nf + kBlock - 1) / kBlock), (unsigned)bc), dim3(kBlock), 0, st, c);
-        PDC_HIP(hipGetLastError());
-        if (amax_out || argmax_out) {
-            hipLaunchKernelGGL(row_nanmax_kernel, dim3((unsigned)bc), dim3(kBlock), 0, st, c.power, nf,
-                               d_amax ? d_amax + c0 : nullptr, d_arg ? d_arg + c0 : nullptr);
-            PDC_HIP(hipGetLastError());
-        }
-        hc.back(power_out ? power_out + c0 * nf : nullptr, c.power, bc * nf * 8);
+        PDC_TRY(fft_pipeline(st, ExtirpArgs{in.d_t, wy, w, in.d_off + c0, 0, shared_t, ngrid, 0, 2, nfft, df, fmin,
+                                            reinterpret_cast<double *>(base + L.grids)},
+                             bc, n_max, reinterpret_cast<cplx *>(base + L.scratch), false,
+                             FftEpiArgs{nullptr, 0, psd, nf, power, nullptr, scal + c0 * 8, 8},
+                             d_amax ? d_amax + c0 : nullptr, d_arg ? d_arg + c0 : nullptr));
+        hc.back(power_out ? power_out + c0 * nf : nullptr, power, bc * nf * 8);
     }
     hc.back(amax_out, d_amax, n_curves * 8);
     hc.back(argmax_out, d_arg, n_curves * 8);
@@ -1190,33 +1049,14 @@ int pdc_trig_sums_fft(const double *t, const double *h, int64_t n, double df, in
     const double scal_host[8] = {0.0, 0.0, tmin, tmax, sorted ? 1.0 : 0.0, 0.0, 0.0, 0.0};
     double *d_t = hc.in(SLOT_IN0, t, n * 8), *d_h = hc.in(SLOT_IN1, h, n * 8);
     double *d_s = hc.out<double>(SLOT_OUT0, nf * 8), *d_c = hc.out<double>(SLOT_OUT1, nf * 8);
-    char *d_work = hc.out<char>(SLOT_WORK, nfft * 32 + 512);
+    const FftLayout L = fft_layout(0, sizeof(scal_host), 1, nfft);   // one curve, one grid, the caller's weights
+    char *base = hc.out<char>(SLOT_WORK, L.total);
     PDC_TRY(hc.status);
-    cplx *grid = reinterpret_cast<cplx *>(d_work), *scratch = grid + nfft;
-    double *scal = reinterpret_cast<double *>(d_work + nfft * 32);
+    double *scal = reinterpret_cast<double *>(base + L.scal);
     hc.put(scal, scal_host, sizeof(scal_host));
-    hipStream_t st = hc.stream();
-    launch_deposit(st, DepositArgs{d_t, d_h, d_h, nullptr, n, 0, 1, 0, 1, scal + 2, 0, nfft, df, fmin,
-                                   reinterpret_cast<double *>(grid)}, 1);
-    SpreadArgs s{d_t, d_h, scal, tmin, n, nfft, df, fmin, reinterpret_cast<double *>(grid)};
-    hipLaunchKernelGGL(glsfft_spread_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock),
-                       0, st, s);
-    PDC_HIP(hipGetLastError());
-    cplx *res = inverse_fft(st, grid, scratch, nfft, 1, nf, LiveArgs{scal + 2, 0, 1, 0, df});
-    PDC_HIP(hipGetLastError());
-    FftEpiArgs e{};
-    e.gh = res;
-    e.nfft = nfft;
-    e.nf = nf;
-    e.df = df;
-    e.fmin = fmin;
-    e.raw_s = d_s;
-    e.raw_c = d_c;
-    e.tmin_value = tmin;
-    e.raw = 1;
-    hipLaunchKernelGGL(glsfft_epilogue_kernel, dim3((unsigned)((nf + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, st, e);
-    PDC_HIP(hipGetLastError());
+    PDC_TRY(fft_pipeline(hc.stream(), ExtirpArgs{d_t, d_h, d_h, nullptr, n, 0, 1, 0, 1, nfft, df, fmin, reinterpret_cast<double *>(base + L.grids)},
+                         1, n, reinterpret_cast<cplx *>(base + L.scratch), false,
+                         FftEpiArgs{nullptr, 0, 0, nf, d_s, d_c, scal, 0}));
     hc.back(S_out, d_s, nf * 8);
     hc.back(C_out, d_c, nf * 8);
     return hc.finish();

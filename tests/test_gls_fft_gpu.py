@@ -209,6 +209,98 @@ def test_batched_fft_path_equals_single_calls():
         assert_tier_f(power[b], _cabi.gls_scan_fft(tt, yy[picks[b]], None, fmin, df, nf), 1e-9, 1e-12)
 
 
+def _shuffled_inside_curves(offsets, seed):
+    rng = np.random.default_rng(seed)
+    return np.concatenate([offsets[b] + rng.permutation(offsets[b + 1] - offsets[b]) for b in range(offsets.size - 1)])
+
+
+def test_batch_with_shuffled_stamps_takes_the_atomic_route_and_agrees_with_the_sorted_batch():
+    lens = [300, 301, 7]
+    curves = [synth(n, 300 + i) for i, n in enumerate(lens)]
+    offsets = np.concatenate([[0], np.cumsum(lens)])
+    t, y, dy = (np.concatenate([c[i] for c in curves]) for i in range(3))
+    perm = _shuffled_inside_curves(offsets, 17)
+    nf, df, fmin = 3000, 0.00021, 0.0004
+    for fit_mean in (True, False):
+        ordered = _cabi.gls_scan_fft_batch(t, y, dy, offsets, fmin, df, nf, fit_mean)[0]
+        shuffled = _cabi.gls_scan_fft_batch(t[perm], y[perm], dy[perm], offsets, fmin, df, nf, fit_mean)[0]
+        for b in range(len(lens)):
+            assert_tier_f(shuffled[b], ordered[b])
+    # a shuffled shared axis, three replicates
+    tt, yy, _ = curves[0]
+    picks = np.random.default_rng(18).integers(0, 300, (3, 300))
+    offs = np.arange(4) * 300
+    p1 = np.random.default_rng(19).permutation(300)
+    for fit_mean in (True, False):
+        ordered = _cabi.gls_scan_fft_batch(tt, yy[picks].ravel(), None, offs, fmin, df, nf, fit_mean, shared_t=True)[0]
+        shuffled = _cabi.gls_scan_fft_batch(tt[p1], yy[picks][:, p1].ravel(), None, offs, fmin, df, nf, fit_mean,
+                                            shared_t=True)[0]
+        for b in range(3):
+            assert_tier_f(shuffled[b], ordered[b])
+
+
+def test_raw_sums_with_shuffled_stamps_take_the_atomic_route_and_agree_with_the_sorted_call():
+    t, y, dy = synth(300, 8)
+    w, yc, _ = so.gls_weights(y, dy, True)
+    h = w * yc
+    perm = np.random.default_rng(23).permutation(300)
+    nf, df, fmin = 3000, 0.00021, 0.0004
+    S, C = _cabi.trig_sums_fft(t, h, df, nf, fmin)
+    Ss, Cs = _cabi.trig_sums_fft(t[perm], h[perm], df, nf, fmin)
+    amp = np.max(np.hypot(S, C))
+    assert np.max(np.abs(Ss - S)) <= 1e-12 * amp and np.max(np.abs(Cs - C)) <= 1e-12 * amp
+
+
+@pytest.mark.parametrize("fit_mean", [True, False])
+def test_a_grid_that_wraps_takes_the_atomics_behind_sorted_stamps(fit_mean):
+    """df = 1.5 / span: positions pass the end of every grid, `deposit_in_order` is false for all of them."""
+    t, y, dy = synth(300, 41)
+    nf = 40
+    df = 1.5 / (t[-1] - t[0])
+    fmin = 0.5 * df
+    freq = fmin + df * np.arange(nf)
+    want = so.gls_power(t, y, dy, freq, df, fmin, fit_mean, sums="fft")
+    assert np.all(np.isfinite(want))
+    assert_tier_f(_cabi.gls_scan_fft(t, y, dy, fmin, df, nf, fit_mean), want)
+    # batch: the curve, and its first half, whose grid at 2 df wraps and whose grids at df do not
+    half = 150
+    offsets = np.array([0, 300, 300 + half])
+    cat = [np.concatenate([a, a[:half]]) for a in (t, y, dy)]
+    power = _cabi.gls_scan_fft_batch(*cat, offsets, fmin, df, nf, fit_mean)[0]
+    assert_tier_f(power[0], want)
+    assert_tier_f(power[1], so.gls_power(t[:half], y[:half], dy[:half], freq, df, fmin, fit_mean, sums="fft"))
+    w, yc, _ = so.gls_weights(y, dy, fit_mean)
+    S, C = _cabi.trig_sums_fft(t, w * yc, df, nf, fmin)
+    Sr, Cr = so.trig_sum_fft(t, w * yc, df, nf, fmin)
+    amp = np.max(np.hypot(Sr, Cr))
+    assert np.max(np.abs(S - Sr)) <= 1e-12 * amp and np.max(np.abs(C - Cr)) <= 1e-12 * amp
+
+
+@pytest.mark.parametrize("nf", [7, 3000])           # below one wave; every wave busy
+@pytest.mark.parametrize("fit_mean", [True, False])
+def test_row_maxima_where_ties_and_nan_decide(nf, fit_mean):
+    """An all-zero curve: every bin NaN without psd (argmax -1, amax NaN), every bin 0.0 with it (the first of
+    equal maxima: argmax 0) - as the reference's epilogue gives them."""
+    lens = [50, 40, 60]
+    curves = [synth(n, 500 + i) for i, n in enumerate(lens)]
+    curves[1] = (curves[1][0], np.zeros(lens[1]), curves[1][2])
+    offsets = np.concatenate([[0], np.cumsum(lens)])
+    t, y, dy = (np.concatenate([c[i] for c in curves]) for i in range(3))
+    df, fmin = 0.00021, 0.0004
+    freq = fmin + df * np.arange(nf)
+    for psd in (False, True):
+        zero_row = so.gls_power(*curves[1], freq, df, fmin, fit_mean, psd, sums="fft")
+        assert np.all(zero_row == 0.0) if psd else np.all(np.isnan(zero_row))
+        power, amax, argmax = _cabi.gls_scan_fft_batch(t, y, dy, offsets, fmin, df, nf, fit_mean, psd, want_peaks=True)
+        assert np.array_equal(power[1], zero_row, equal_nan=True)
+        if psd:
+            assert argmax[1] == 0 and amax[1] == 0.0
+        else:
+            assert argmax[1] == -1 and np.isnan(amax[1])
+        for b in (0, 2):
+            assert argmax[b] == np.nanargmax(power[b]) and amax[b] == np.nanmax(power[b])
+
+
 def test_bootstrap_1000_replicates_through_both_paths_agree_on_the_false_alarm_level():
     t, y, dy = synth(400, 31)
     fft, direct = GLS(method="fft"), GLS()
