@@ -430,7 +430,9 @@ int pdc_bls_scan_ragged_dev(int device, void *stream, const double *d_t, const d
  * `work` is scratch of at least pdc_gls_work_bytes(n_total, n_curves, nf) bytes on the same
  * device (non-decreasing in n_total and in nf: a buffer sized for the largest call serves all; for a
  * single curve it includes up to 48 MiB for the partial sums of short grids, whose samples are cut
- * into parts as well).  d_offsets may be NULL for a single curve of n_total samples. */
+ * into parts as well; for the mirrored-pair kernel 256 bytes per sample of offset table, 32 bytes per sample of fill
+ * steps and 128 bytes per 64 samples and per curve of chunk remainders).  d_offsets may be NULL for a single curve of
+ * n_total samples. */
 int64_t pdc_gls_work_bytes(int64_t n_total, int64_t n_curves, int64_t nf);
 int pdc_gls_scan_dev(int device, void *stream,
                      const double *d_t, const double *d_y, const double *d_dy,
@@ -442,14 +444,16 @@ int pdc_gls_scan_dev(int device, void *stream,
 /* TEST HOOK (not for callers): the route the CALLING THREAD's last direct-sum scan took inside the library (every entry
  * above, pdc_gls_bootstrap with method 0 and the plans' enqueueing thread end in the same dispatcher) and its launch
  * shape, recorded on the host just before the launches.  The record is per host thread, so concurrent scans on other
- * threads do not disturb it; all zeros before the thread's first scan.  out[13] = route (1 general, 2 general with
+ * threads do not disturb it; all zeros before the thread's first scan.  out[14] = route (1 general, 2 general with
  * sample parts, 3 balanced pieces, 4 shared time axis, 5 shared time axis with two frequencies per lane), K (frequencies
  * per thread; per lane on the shared routes), S (waves per frequency tile; 0 on the shared routes), frequency tiles,
  * final sample part count (1: not cut), 1 when the parts are dealt to the XCDs, workgroup slots of the balanced launch
  * (0: not balanced), 1 when the grid-wide prologue ran, curves per padded row of the shared weight table, its curve
  * groups, samples per part, 128-sample chunks per tile of the balanced launch, 1 when the odd column-waves of the
  * mirrored-pair kernel took every sample's table halves in the opposite order (only with PDC_GLS_LEAD=1 in the
- * environment; always 0 at S = 4 and where the pair kernel did not run). */
+ * environment; always 0 at S = 4 and where the pair kernel did not run), 1 when the mirrored-pair kernel took its
+ * chunks' remainders from the array made once per call, 0 when every tile summed them in its table fill
+ * (PDC_GLS_CHUNK_SUMS=0 in the environment, a launch whose stretches are not chunk-aligned, no pair kernel). */
 int pdc_test_gls_last_dispatch(int64_t *out);
 /* TEST HOOK (not for callers): whether the CALLING THREAD's last direct-sum scan ran the mirrored-pair kernel (K = 16 in
  * the two GLS modes; PDC_GLS_PAIR=0 in the environment keeps the plain kernel), per host thread like the record above.

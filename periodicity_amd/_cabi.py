@@ -522,7 +522,7 @@ def gls_bootstrap(t, y, dy, picks, f0, delta, nf, fit_mean=True, psd=False, meth
 
 GLS_ROUTES = ("none", "general", "parts", "balanced", "shared", "shared2")
 _GLS_DISPATCH_FIELDS = ("route", "K", "S", "tiles", "parts", "parts_by_xcd", "bal_slots", "wide_prep", "bpad", "groups",
-                        "z_len", "bal_chunks", "lead_swap")
+                        "z_len", "bal_chunks", "lead_swap", "chunk_sums")
 
 
 def gls_last_dispatch():

@@ -23,6 +23,8 @@
 //                     2-omega sums follow from the double-angle identities), each one fma because
 //                     sin/cos are carried pre-multiplied by sqrt(w).  The epilogue
 //                     (spectral.py:113-132) is fused, so only power[nf] is written.
+//   gls_pair_*_kernel (K = 16, the two GLS modes) what the mirrored-pair scan reads per sample and per chunk whatever
+//                     the tile: the offset table, the steps of the table fill, the chunks' remainders.
 //   gls_peak_kernel   NaN-aware max / argmax per curve from per-workgroup partials.
 //
 // No MFMA: with one weight vector per curve the accumulation is a matrix-vector product and the
@@ -68,7 +70,10 @@ struct GlsArgs {
     // lead swap (pair instances with two or more column-waves per stream): the odd columns take every sample's table
     // halves in the opposite order, see the scalar pipeline of the kernel.  (Here, in the padding after `psd`: the
     // argument block of every instance keeps its size and offsets.)
-    int lead_swap = 0;
+    // chunk_sums (pair instances): every stretch of samples a workgroup scans starts on a chunk boundary of its curve
+    // and ends on one or at the curve's end, so the chunks' remainders G_m, F_m come from gls_pair_chunk_kernel's
+    // array instead of being summed again by every tile (same values, same order of additions).
+    int16_t lead_swap = 0, chunk_sums = 0;
     double *power;     // [n_curves][nf] or nullptr
     double *raw_s;     // MODE_RAW outputs
     double *raw_c;
@@ -87,7 +92,9 @@ struct GlsArgs {
     int64_t bal_slots = 0, bal_units = 0, bal_chunks = 0, bal_tile_freqs = 0;
     TrendScalars trend = {};   // MODE_TREND only
     // mirrored pairs (gls_scan_kernel<..., PAIR = true>): [n_total + 2][8][4] = {cos, sin, cos 2, sin 2}(psi_m),
-    // psi_m = 2 pi (m + 1/2) delta t' (gls_pair_table_kernel)
+    // psi_m = 2 pi (m + 1/2) delta t' (gls_pair_table_kernel); right behind it (no argument of their own: the block
+    // keeps its size) the per-sample steps of the table fill, [n_total][4] (gls_pair_step_kernel), and the chunks'
+    // remainders, [n_total / kChunk + n_curves][16] (gls_pair_chunk_kernel) - pair_step(), pair_chunk_sums() below
     const double *pair_tab = nullptr;
 };
 
@@ -304,6 +311,81 @@ __global__ __launch_bounds__(kBlock) void gls_pair_table_kernel(const double *re
     o[1] = make_double2(c2, s2);
 }
 
+// What the pair kernel's table fill needs per sample or per chunk of a curve and NOT per tile is made once per call as
+// well, with the fill's own operations on the fill's own inputs (the bits every tile used to compute for itself):
+//   gls_pair_step_kernel    {sin, cos}(Theta), {sin, cos}(8 Theta), Theta = 2 pi 16 delta t': the steps of the fill's two
+//                           rotation chains, 32 bytes per sample
+//   gls_pair_chunk_kernel   the sixteen remainders {G_m, F_m} of every chunk of kChunk samples, counted from its curve's
+//                           first sample: thread (stretch, m16) adds its kChunk / 16 samples in order, the sixteen
+//                           stretches are added in order, samples past the curve's end add 0.  Curve c's chunk j is row
+//                           offsets[c] / kChunk + c + j (rows of different curves never meet: a curve has at most
+//                           n / kChunk + 1 chunks).
+constexpr int kPairStep = 4;               // doubles per sample
+__host__ __device__ constexpr int64_t pair_chunk_rows(int64_t n_total, int64_t n_curves, int chunk) { return n_total / chunk + n_curves; }
+__host__ __device__ __forceinline__ const double *pair_step(const double *tab, int64_t n_total) { return tab + (n_total + 2) * kPairRow; }
+__host__ __device__ __forceinline__ const double *pair_chunk_sums(const double *tab, int64_t n_total) {
+    return pair_step(tab, n_total) + n_total * kPairStep;
+}
+
+__global__ __launch_bounds__(kBlock) void gls_pair_step_kernel(const double *rec, double *step, int64_t n_total, double delta) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_total) return;
+    double2 kk[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) kk[q] = sincos_coefficient(q);
+    const double tp = rec[i * 6 + 5];
+    const double kdelta = 16.0 * delta;   // (K delta of the scan, exact)
+    double2 s1, s8;
+    sincos_cycles_k(frac_product(kdelta, tp), kk, s1.x, s1.y);
+    sincos_cycles_k(frac_product(8.0 * kdelta, tp), kk, s8.x, s8.y);
+    double2 *o = reinterpret_cast<double2 *>(step + i * kPairStep);
+    o[0] = s1;
+    o[1] = s8;
+}
+
+template <int CHUNK>
+__global__ __launch_bounds__(kBlock) void gls_pair_chunk_kernel(const double *rec, const double *tab, const int64_t *offsets,
+                                                                int64_t n_total, int64_t n_curves, double *sums) {
+    __shared__ double red[16][16];
+    const int tid = threadIdx.x;
+    const int64_t row = blockIdx.x;
+    // the curve whose rows hold this one: the last c with offsets[c] / CHUNK + c <= row
+    int64_t c = 0;
+    if (offsets) {
+        int64_t hi = n_curves - 1;
+        while (c < hi) {
+            const int64_t mid = (c + hi + 1) / 2;
+            if (offsets[mid] / CHUNK + mid <= row) c = mid;
+            else hi = mid - 1;
+        }
+    }
+    const int64_t off = offsets ? offsets[c] : 0;
+    const int64_t n = offsets ? offsets[c + 1] - off : n_total;
+    const int64_t base = (row - (off / CHUNK + c)) * CHUNK;
+    if (base >= n) return;   // (the whole workgroup: a row no curve uses)
+    constexpr int SPP = CHUNK / 16;
+    const int m16 = tid & 15, seg = tid >> 4;
+    const int64_t i0 = base + seg * SPP;
+    const double *tp_ = tab + (off + i0) * kPairRow + (m16 & 7) * 4 + (m16 < 8 ? 1 : 3);
+    const double *rp_ = rec + (off + i0) * 6 + 1;
+    double acc = 0.0;
+#pragma unroll
+    for (int q = 0; q < SPP; ++q) {
+        const bool live = i0 + q < n;
+        const double sq = live ? rp_[q * 6] : 0.0;
+        const double v = live ? tp_[q * kPairRow] : 0.0;
+        acc = __builtin_fma(sq * sq, m16 < 8 ? v * v : v, acc);
+    }
+    red[seg][m16] = acc;
+    __syncthreads();
+    if (tid < 16) {
+        double g = red[0][tid];
+#pragma unroll
+        for (int q = 1; q < 16; ++q) g += red[q][tid];
+        sums[row * 16 + tid] = g;
+    }
+}
+
 // ---- epilogue: spectral.py:113-132 (gls_epilogue.h); the 2-omega sums come from the double-angle
 // identities sin 2a = 2 sin a cos a, cos 2a = 1 - 2 sin^2 a ------------------------------------------
 template <int MODE>
@@ -370,9 +452,10 @@ __device__ __forceinline__ double bglst_loglik(double Sh, double Ch, double S, d
 //     Sh+- = sum A1 c +- sum B1 s      Ch+- = sum B1 c -+ sum A1 s      (S+-, C+- the same with A2, B2)
 //     SS+- = sum a2 c2 + G_m +- sum ab s2,           G_m = sum w s_m^2
 //     SC+- = sum ab c2 +- (F_m / 2 - sum a2 s2),     F_m = sum w s2_m        (both from a^2 + b^2 = w)
-// G_m and F_m do not depend on the thread: the table fill adds each chunk's sixteen values into a workgroup
-// accumulator (fixed order), and they enter when the twelve sums are recombined into the six per frequency after the
-// chunk loop.  From there on - the SPLIT fold, partial sums, epilogue, maxima - nothing differs.
+// G_m and F_m do not depend on the thread - nor on the tile: each chunk's sixteen values (gls_pair_chunk_kernel, once
+// per call; summed in the table fill where GlsArgs::chunk_sums is 0) are added into a workgroup accumulator in chunk
+// order, and they enter when the twelve sums are recombined into the six per frequency after the chunk loop.  From
+// there on - the SPLIT fold, partial sums, epilogue, maxima - nothing differs.
 template <int K, int MODE, int SPLIT, bool BAL = false, bool PAIR = false>
 __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(GlsArgs a) {
     static_assert(!PAIR || (K == 2 * kPairM && (MODE == MODE_FIT_MEAN || MODE == MODE_NO_MEAN)), "mirrored pairs: K = 16, the two GLS modes");
@@ -461,7 +544,7 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
     if (PAIR) {
         int t16 = tid_;
         asm volatile("" : "+v"(t16));   // (opaque: the mask is not kept across the loops)
-        if (t16 < 16) gf_acc[t16] = 0.0;   // (touched by this thread alone until the barrier after the chunk loop)
+        if (t16 < 16) gf_acc[t16] = 0.0;   // (a barrier on; then one thread's alone until the barrier after the chunk loop)
     }
 
     const int64_t s_begin = BAL ? bal_c0 * kChunk : (a.partial ? (int64_t)zpart * a.z_len : 0);
@@ -476,33 +559,110 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
         if (TIGHT) asm volatile("" : "+v"(tid));
         const int lane = tid & 63;
         const int slot_a = col * 8 + (lane >> 3), slot_b = COLS * 8 + (lane & 7);
-        if (PAIR) {
-            // this chunk's G_m = sum w s_m^2 and F_m = sum w s2_m: thread (stretch, m16) adds its stretch of kChunk / 16
-            // samples in order; after the barrier sixteen threads add the stretches in order.  (These loads also bring
-            // the chunk's table rows into L2 ahead of the scalar loads of the accumulation loop.)
-            constexpr int SPP = kChunk / 16;
-            const int m16 = tid & 15, seg = tid >> 4;
-            const int64_t i0 = base + seg * SPP;
-            const double *tp_ = a.pair_tab + (off + i0) * kPairRow + (m16 & 7) * 4 + (m16 < 8 ? 1 : 3);
-            const double *rp_ = a.rec + (off + i0) * 6 + 1;
-            double acc = 0.0;
-#pragma unroll
-            for (int q = 0; q < SPP; ++q) {
-                const bool live = i0 + q < s_end;
-                const double sq = live ? rp_[q * 6] : 0.0;
-                const double v = live ? tp_[q * kPairRow] : 0.0;
-                acc = __builtin_fma(sq * sq, m16 < 8 ? v * v : v, acc);
-            }
-            gf_red[seg][m16] = acc;
-            __builtin_amdgcn_sched_barrier(0);   // (done before the fill's own registers are live)
-        }
         // ---- per-sample rotation tables (two threads per sample) ------------------------------------
         // Thread (col, lane) starts at phase theta_tile + (64 col + 8 a + b) Theta with a = lane / 8,
         // b = lane % 8 and Theta = 2 pi K delta t': its seed is tab[8 col + a] rotated by tab[8 COLS + b]
-        // instead of a sincos.  The even thread of a sample makes {sin, cos}(b Theta) (one sincos, a
-        // chain of 6 rotations) and the tile's base phase (one sincos, scaled by sqrt(w) where the
-        // sums want it); the odd thread walks that base in steps of 8 Theta (one sincos, 8 COLS - 1
-        // rotations).
+        // instead of a sincos.
+        if constexpr (PAIR) {
+            // The steps {sin, cos}(Theta) and {sin, cos}(8 Theta) come per sample from gls_pair_step_kernel, so a sample's
+            // two threads no longer meet: the WALK thread makes the tile's base phase (the fill's one sincos, scaled by
+            // sqrt(w)) and walks it in steps of 8 Theta (8 COLS - 1 rotations), the CHAIN thread makes {sin, cos}(b Theta)
+            // (6 rotations).  Threads [0, kChunk) walk and [kChunk, 2 kChunk) chain: a wave runs ONE role, not both under
+            // a lane mask, and nothing is handed from lane to lane.
+#ifdef PDC_GLS_PROBE_FILL
+            // TIMING PROBE (never defined by the Makefile; wrong results): the chunks after a piece's first keep the
+            // first chunk's LDS tables - no fill, no remainders; the touches of the table rows and the two barriers
+            // stay - the headline time with a free fill
+            const bool fill_now = base == s_begin;
+#else
+            constexpr bool fill_now = true;
+#endif
+            const bool stored = a.chunk_sums != 0;
+            if (!stored && fill_now) {
+                // (a launch whose stretches do not start and end on the curve's chunk boundaries)
+                // this chunk's G_m = sum w s_m^2 and F_m = sum w s2_m: thread (stretch, m16) adds its stretch of kChunk / 16
+                // samples in order; after the barrier sixteen threads add the stretches in order.  (These loads also bring
+                // the chunk's table rows into L2 ahead of the scalar loads of the accumulation loop.)
+                constexpr int SPP = kChunk / 16;
+                const int m16 = tid & 15, seg = tid >> 4;
+                const int64_t i0 = base + seg * SPP;
+                const double *tp_ = a.pair_tab + (off + i0) * kPairRow + (m16 & 7) * 4 + (m16 < 8 ? 1 : 3);
+                const double *rp_ = a.rec + (off + i0) * 6 + 1;
+                double acc = 0.0;
+#pragma unroll
+                for (int q = 0; q < SPP; ++q) {
+                    const bool live = i0 + q < s_end;
+                    const double sq = live ? rp_[q * 6] : 0.0;
+                    const double v = live ? tp_[q * kPairRow] : 0.0;
+                    acc = __builtin_fma(sq * sq, m16 < 8 ? v * v : v, acc);
+                }
+                gf_red[seg][m16] = acc;
+                __builtin_amdgcn_sched_barrier(0);   // (done before the fill's own registers are live)
+            }
+            const int il = tid & (kChunk - 1);
+            // (rows past the end of the curve are never accumulated; they only need finite input)
+            const bool live = base + il < s_end;
+            const double2 *stp = reinterpret_cast<const double2 *>(pair_step(a.pair_tab, a.n_total) + (off + base + il) * kPairStep);
+            if (tid < kChunk) {
+                if (fill_now) {
+                    const double tp = live ? a.rec[(off + base + il) * 6 + 5] : 0.0;
+                    const double sqw = live ? a.rec[(off + base + il) * 6 + 1] : 0.0;
+                    const double2 step8 = live ? stp[1] : make_double2(0.0, 0.0);
+                    double2 kk[6];
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) kk[q] = sc_k[q];
+                    // the base phase is lane 0's centre, f_tile + 7.5 delta = f_tile + 8 delta - delta / 2 (both exact)
+                    double r_base = frac_product(f_tile, tp);
+                    double dl = a.delta;
+                    asm volatile("" : "+v"(dl));   // (opaque: its multiples are made here, not kept across the loops)
+                    r_base += frac_product(8.0 * dl, tp) - frac_product(0.5 * dl, tp);
+                    double2 b0;
+                    sincos_cycles_k(r_base, kk, b0.x, b0.y);
+                    // carry u = sqrt(w) sin, v = sqrt(w) cos: rotations are linear, and every sum becomes one fma
+                    b0.x *= sqw;
+                    b0.y *= sqw;
+                    tab[il][0] = b0;
+#pragma unroll
+                    for (int q = 1; q < COLS * 8; ++q) {
+                        b0 = rot2(b0, step8);
+                        tab[il][q] = b0;
+                    }
+                }
+            } else if (tid < 2 * kChunk) {
+                // What the in-fill remainder loads did besides: the chunk's 2 kChunk lines of the offset table are in L2
+                // before the scalar loads of the accumulation loop ask for them.  A chain thread touches its row's two.
+                // (plain loads, asked for first and waited for last: their values are not used)
+                double touch0 = 0.0, touch1 = 0.0;
+                if (stored && live) {
+                    const double *row = a.pair_tab + (off + base + il) * kPairRow;
+                    touch0 = row[0];
+                    touch1 = row[kPairRow / 2];
+                }
+                if (fill_now) {
+                    // the chunk's stored remainders (curve-relative chunk base / kChunk), added in chunk order - the
+                    // order of the in-fill sums - by sixteen threads of this role, which has the shorter chain
+                    double g_chunk = 0.0;
+                    if (stored && il < 16)
+                        g_chunk = pair_chunk_sums(a.pair_tab, a.n_total)[(off / kChunk + curve + base / kChunk) * 16 + il];
+                    const double2 step1 = live ? stp[0] : make_double2(0.0, 0.0);
+                    double one = 1.0, zero = 0.0;
+                    asm volatile("" : "+v"(one), "+v"(zero));   // (made here, not kept in four registers across the loops)
+                    tab[il][COLS * 8] = make_double2(zero, one);
+                    tab[il][COLS * 8 + 1] = step1;
+                    double2 cur = step1;
+#pragma unroll
+                    for (int q = 2; q < 8; ++q) {
+                        cur = rot2(cur, step1);
+                        tab[il][COLS * 8 + q] = cur;
+                    }
+                    if (stored && il < 16) gf_acc[il] += g_chunk;
+                }
+                asm volatile("" : : "v"(touch0), "v"(touch1));
+            }
+        } else {
+        // The even thread of a sample makes {sin, cos}(b Theta) (one sincos, a chain of 6 rotations) and the tile's
+        // base phase (one sincos, scaled by sqrt(w) where the sums want it); the odd thread walks that base in steps
+        // of 8 Theta (one sincos, 8 COLS - 1 rotations).
         if (tid < 2 * kChunk) {
             const int il = tid >> 1;
             // (rows past the end of the curve are never accumulated; they only need finite input)
@@ -532,14 +692,7 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
                     cur = rot2(cur, step1);
                     tab[il][COLS * 8 + q] = cur;
                 }
-                double r_base = frac_product(f_tile, tp);
-                // PAIR: the base phase is lane 0's centre, f_tile + 7.5 delta = f_tile + 8 delta - delta / 2 (both exact)
-                if (PAIR) {
-                    double dl = a.delta;
-                    asm volatile("" : "+v"(dl));   // (opaque: its multiples are made here, not kept across the loops)
-                    r_base += frac_product(8.0 * dl, tp) - frac_product(0.5 * dl, tp);
-                }
-                sincos_fill(r_base, cur.x, cur.y);
+                sincos_fill(frac_product(f_tile, tp), cur.x, cur.y);
                 if (MODE == MODE_FIT_MEAN || MODE == MODE_NO_MEAN || MODE == MODE_TREND) {
                     // carry u = sqrt(w) sin, v = sqrt(w) cos: rotations and the recurrence are linear,
                     // and every sum becomes one fma (the record holds sqrt(w) and sqrt(w) y)
@@ -562,12 +715,17 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
                 }
             }
         }
+        }
         __syncthreads();
         const int cnt = (int)((s_end - base) < kChunk ? (s_end - base) : kChunk);
         const int i_end = cnt < (part + 1) * (kChunk / SPLIT) ? cnt : (part + 1) * (kChunk / SPLIT);
         const int i_beg = part * (kChunk / SPLIT);
         if constexpr (PAIR) {
-            if (tid < 16) {   // the chunk's sixteen remainders, stretches in order
+#ifdef PDC_GLS_PROBE_FILL
+            if (tid < 16 && !a.chunk_sums && base == s_begin) {
+#else
+            if (tid < 16 && !a.chunk_sums) {   // (summed in the fill) the chunk's sixteen remainders, stretches in order
+#endif
                 double g = gf_red[0][tid];
 #pragma unroll
                 for (int q = 1; q < 16; ++q) g += gf_red[q][tid];
@@ -1431,7 +1589,7 @@ struct WorkLayout {
 // scan meanwhile.
 enum Route { ROUTE_NONE = 0, ROUTE_GENERAL = 1, ROUTE_PARTS = 2, ROUTE_BALANCED = 3, ROUTE_SHARED = 4, ROUTE_SHARED2 = 5 };
 struct Dispatch {
-    int64_t route, K, S, tiles, parts, parts_by_xcd, bal_slots, wide_prep, bpad, groups, z_len, bal_chunks, lead_swap;
+    int64_t route, K, S, tiles, parts, parts_by_xcd, bal_slots, wide_prep, bpad, groups, z_len, bal_chunks, lead_swap, chunk_sums;
 };
 thread_local Dispatch g_last_dispatch = {};
 // TEST HOOK (pdc_test_gls_last_pair): whether that scan ran the mirrored-pair kernel, and the bytes of its offset table
@@ -1454,7 +1612,9 @@ WorkLayout layout(int64_t n_total, int64_t n_curves, int64_t nf) {
     int64_t cells = kPartsMax * nf < kPartialCells ? kPartsMax * nf : kPartialCells;
     cells = cells > 3 * nf ? cells : 3 * nf;   // balanced pieces: up to three partial sums per frequency
     w.pair = w.partial + (n_curves == 1 ? up(cells * 6 * 8) : 0);
-    w.total = w.pair + up((n_total + 2) * kPairRow * 8);   // the mirrored-pair offset table + the two rows read ahead
+    // the mirrored-pair offset table + the two rows read ahead | the fill's per-sample steps | the chunks' remainders
+    // (rows for the shorter chunk, 64 samples, serve the longer one too)
+    w.total = w.pair + up(((n_total + 2) * kPairRow + n_total * kPairStep + pair_chunk_rows(n_total, n_curves, 64) * 16) * 8);
     return w;
 }
 
@@ -1621,6 +1781,11 @@ int scan_dev(int device, hipStream_t st, const double *d_t, const double *d_y, c
         hipLaunchKernelGGL(gls_pair_table_kernel, dim3((unsigned)((cells + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                            (const double *)p.rec, tab, n_total, delta);
         PDC_HIP(hipGetLastError());
+        if (n_total > 0) {
+            hipLaunchKernelGGL(gls_pair_step_kernel, dim3((unsigned)((n_total + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                               (const double *)p.rec, const_cast<double *>(pair_step(tab, n_total)), n_total, delta);
+            PDC_HIP(hipGetLastError());
+        }
         a.pair_tab = tab;
         // Lead swap: the odd column-waves of the pair kernel take the table halves in the opposite order (S = 4 has
         // one column per stream: nothing to swap).  OFF unless PDC_GLS_LEAD=1 (read once per process; 0 states the
@@ -1662,6 +1827,20 @@ int scan_dev(int device, hipStream_t st, const double *d_t, const double *d_y, c
             grid.y = (unsigned)parts;
         }
     }
+    // Mirrored pairs: the chunks' remainders once per call (gls_pair_chunk_kernel) wherever every stretch a workgroup
+    // scans starts on a chunk boundary of its curve and ends on one or at the curve's end - whole curves and balanced
+    // pieces by construction, sample parts when z_len is a multiple of the chunk (today always: 128).  Any other
+    // launch, and PDC_GLS_CHUNK_SUMS=0 (read once per process; 1 states the default), sums them in the fill.
+    static const int env_chunk = [] { const char *e = getenv("PDC_GLS_CHUNK_SUMS"); return e ? atoi(e) : 1; }();
+    if (a.pair_tab && n_total > 0 && env_chunk != 0 && (parts == 1 || a.z_len % (S == 1 ? 64 : 128) == 0)) {
+        double *sums = const_cast<double *>(pair_chunk_sums(a.pair_tab, n_total));
+        const dim3 rows((unsigned)pair_chunk_rows(n_total, n_curves, S == 1 ? 64 : 128));
+        if (S == 1) hipLaunchKernelGGL(gls_pair_chunk_kernel<64>, rows, dim3(kBlock), 0, st, a.rec, a.pair_tab, d_offsets, n_total, n_curves, sums);
+        else hipLaunchKernelGGL(gls_pair_chunk_kernel<128>, rows, dim3(kBlock), 0, st, a.rec, a.pair_tab, d_offsets, n_total, n_curves, sums);
+        PDC_HIP(hipGetLastError());
+        a.chunk_sums = 1;
+    }
+    rec.chunk_sums = a.chunk_sums;
     rec.route = parts > 1 ? ROUTE_PARTS : ROUTE_GENERAL;
     rec.K = K;
     rec.S = S;
@@ -1735,9 +1914,9 @@ extern "C" {
 int pdc_test_gls_last_dispatch(int64_t *out) {
     PDC_REQUIRE(out, "pdc_test_gls_last_dispatch: NULL argument");
     const Dispatch &d = g_last_dispatch;
-    const int64_t v[13] = {d.route, d.K, d.S, d.tiles, d.parts, d.parts_by_xcd, d.bal_slots, d.wide_prep,
-                           d.bpad, d.groups, d.z_len, d.bal_chunks, d.lead_swap};
-    for (int i = 0; i < 13; ++i) out[i] = v[i];
+    const int64_t v[14] = {d.route, d.K, d.S, d.tiles, d.parts, d.parts_by_xcd, d.bal_slots, d.wide_prep,
+                           d.bpad, d.groups, d.z_len, d.bal_chunks, d.lead_swap, d.chunk_sums};
+    for (int i = 0; i < 14; ++i) out[i] = v[i];
     return PDC_OK;
 }
 
