@@ -346,6 +346,54 @@ int64_t pdc_wwz_work_bytes(int64_t n, int64_t nf, int64_t ntau);
  * thread, rows per launch, launches of the scan kernel.  Any pointer may be NULL. */
 int pdc_wwz_last_dispatch(int *k, int *rows_per_launch, int64_t *launches);
 
+/* ---- the Keplerian periodogram (Zechmeister & Kurster 2009, A&A 496, 577, section 4) -----------------------------------
+ * The reference has no such class - PARITY UNPINNED BY THE REFERENCE.  Per trial frequency the best weighted least-squares
+ * fit of a Keplerian orbit over a grid of eccentricities ecc[ne], each in [0, 0.95], and mean anomalies at t[0] m0[nm],
+ * each in [0, 1) cycles.  Inputs, weights w_i = dy_i^-2 / sum dy^-2 (dy == NULL: unit uncertainties), centring of y on
+ * its weighted mean (fit_mean) and the grid rule f_j = f0 + j delta (numpy's arange fill) as pdc_mhgls_scan;
+ * t' = t - t[0].  Cell c = k nm + l of bin j:
+ *     phi_i = frac(f_j t'_i), reduced exactly;   M_i = 2 pi (phi_i - m0_l);   E_i solves E - e_k sin E = M_i;
+ *     cos nu = (cos E - e) / (1 - e cos E),   sin nu = sqrt(1 - e^2) sin E / (1 - e cos E);
+ *     cube[j][k][l] = b^T M^-1 b / YY        (psd: b^T M^-1 b * 0.5 * sum dy^-2)
+ * with design columns cos nu, sin nu and a constant when fit_mean, M = Phi^T diag(w) Phi, b = Phi^T diag(w) y,
+ * YY = sum w y^2.  A cell whose M has a Cholesky pivot that is not > 0, or not finite, is NaN.  At e = 0 the cell is the
+ * GLS power for every m0.  Outputs, any of them NULL, not all:
+ *     power_out[nf]   the largest cell of the bin, as np.nanmax gives it;
+ *     cell_out[nf]    the index of that cell as np.nanargmax over the row-major [ne][nm] cells finds it: NaN never wins,
+ *         the lowest index of equal maxima wins; index -1 and power NaN where every cell is NaN;
+ *     cube_out[nf][ne][nm]   every cell (for tests and small problems);
+ *     best_out[1], best_at_out[2] = (bin, cell)   the largest power_out in ascending bin order; NaN and (-1, -1) if no
+ *         bin has a value.
+ * Checked before any device is looked for: f0 finite and >= 0, delta finite and > 0, nf >= 1, n >= 4, 1 <= ne, 1 <= nm,
+ * ne nm <= 65535, every ecc finite and in [0, 0.95], every m0 finite and in [0, 1), not every output NULL, and in the
+ * host form finite t.  The `_dev` form takes device pointers (ecc and m0 too) and cannot look at the lists: a cell whose
+ * e or m0 is out of range indexes nothing and is NaN.  The Kepler solve has a fixed trip count (Markley 1995): cos nu and
+ * sin nu are within 1e-12 of their values over the whole range, which is what the cap of 0.95 on e buys (d nu / d M
+ * reaches 125 there).  PDC_WORK_BUDGET_GB cuts the grid into slabs of whole tiles, at least one, scanned one after the
+ * other.  No atomics: the same bits from call to call, and no bit of a cell depends on its place in the lists, on the
+ * other cells of the call or on the slabs.  The `_dev` form enqueues on `stream` and keeps its own workspace per
+ * (device, stream). */
+int pdc_kepler_scan(const double *t, const double *y, const double *dy, int64_t n, double f0, double delta, int64_t nf,
+                    const double *ecc, int64_t ne, const double *m0, int64_t nm, int fit_mean, int psd, double *power_out,
+                    int32_t *cell_out, double *cube_out, double *best_out, int64_t *best_at_out, int device);
+int pdc_kepler_scan_dev(int device, void *stream, const double *d_t, const double *d_y, const double *d_dy, int64_t n,
+                        double f0, double delta, int64_t nf, const double *d_ecc, int64_t ne, const double *d_m0,
+                        int64_t nm, int fit_mean, int psd, double *d_power, int32_t *d_cell, double *d_cube,
+                        double *d_best, int64_t *d_best_at);
+/* cos nu and sin nu of `count` pairs (phase[i] in cycles, any finite value; e[i] in [0, 0.95]) by the device function
+ * the scan runs.  Host arrays. */
+int pdc_kepler_anomaly(const double *phase, const double *e, int64_t count, double *cos_out, double *sin_out, int device);
+/* Cells per thread of the scan (a workgroup takes one tile of bins and this many cells).  No GPU needed. */
+int pdc_kepler_cell_group(void);
+/* Bins per tile of the scan: 256.  No GPU needed. */
+int64_t pdc_kepler_tile_bins(void);
+/* Workspace bytes of a scan under the current PDC_WORK_BUDGET_GB; -1 for sizes out of range (what the scan refuses, the
+ * cube counted when want_cube).  No GPU needed. */
+int64_t pdc_kepler_work_bytes(int64_t n, int64_t nf, int64_t ne, int64_t nm, int want_cube);
+/* What the CALLING THREAD's last Keplerian scan launched (as pdc_htest_last_dispatch; zeros before the first): cells per
+ * thread, cell groups, launches of the scan kernel (slabs).  Any pointer may be NULL. */
+int pdc_kepler_last_dispatch(int *kc, int *groups, int64_t *launches);
+
 /* ---- BLS: box least squares (Kovacs, Zucker & Mazeh 2002, A&A 391, 369) ----------------------------------------------
  * The reference has no such class - PARITY UNPINNED BY THE REFERENCE.  The search for a box-shaped dip (a transit, a
  * detached eclipse): per trial period the best two-level model of the folded curve.  Weights and centring as

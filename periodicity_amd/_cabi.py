@@ -66,6 +66,14 @@ PROTOTYPES = {
     "pdc_wwz_tile_bins": (_L, []),
     "pdc_wwz_work_bytes": (_L, [_L, _L, _L]),
     "pdc_wwz_last_dispatch": (_I, [C.POINTER(_I), C.POINTER(_I), c_int64_p]),
+    "pdc_kepler_scan": (_I, [_VP, _VP, _VP, _L, _D, _D, _L, _VP, _L, _VP, _L, _I, _I, _VP, _VP, _VP, _VP, _VP, _I]),
+    "pdc_kepler_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _D, _D, _L, _VP, _L, _VP, _L, _I, _I,
+                                 _VP, _VP, _VP, _VP, _VP]),
+    "pdc_kepler_anomaly": (_I, [_VP, _VP, _L, _VP, _VP, _I]),
+    "pdc_kepler_cell_group": (_I, []),
+    "pdc_kepler_tile_bins": (_L, []),
+    "pdc_kepler_work_bytes": (_L, [_L, _L, _L, _L, _I]),
+    "pdc_kepler_last_dispatch": (_I, [C.POINTER(_I), C.POINTER(_I), c_int64_p]),
     "pdc_bls_scan": (_I, [_VP, _VP, _VP, _L, _VP, _L, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _I]),
     "pdc_bls_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _VP, _L, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "pdc_bls_scan_ragged": (_I, [_VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I,
@@ -446,6 +454,64 @@ def wwz_last_dispatch():
     k, rows, launches = C.c_int(0), C.c_int(0), C.c_int64(0)
     check(lib().pdc_wwz_last_dispatch(C.byref(k), C.byref(rows), C.byref(launches)))
     return k.value, rows.value, launches.value
+
+
+def kepler_scan(t, y, dy, f0, delta, nf, ecc, m0, fit_mean=True, psd=False, want_cube=False, want_bins=True,
+                device=None):
+    """Keplerian periodogram (``pdc_kepler_scan``): per trial frequency the best weighted least-squares fit of a
+    Keplerian orbit over the eccentricities ``ecc`` (each in [0, 0.95]) times the mean anomalies at ``t[0]``, ``m0``
+    (cycles, each in [0, 1)).  Returns a dict: ``power`` / ``cell`` (int32) ``[nf]`` (None without ``want_bins``),
+    ``cube`` ``[nf][ne][nm]`` (None without ``want_cube``) and ``best`` = ``(value, bin, cell)``."""
+    t, y, ecc, m0 = _f64(t, "t"), _f64(y, "y"), _f64(ecc, "ecc"), _f64(m0, "m0")
+    dy = None if dy is None else _f64(dy, "dy")
+    if y.size != t.size or (dy is not None and dy.size != t.size):
+        raise ValueError("Input arrays have incompatible lengths.")
+    nf = int(nf)
+    out = {"power": np.empty(max(nf, 0)) if want_bins else None,
+           "cell": np.empty(max(nf, 0), dtype=np.int32) if want_bins else None,
+           "cube": np.empty((max(nf, 0), ecc.size, m0.size)) if want_cube else None}
+    best, best_at = np.full(1, np.nan), np.full(2, -1, dtype=np.int64)
+    dev = default_device() if device is None else device
+    check(lib().pdc_kepler_scan(_ptr(t), _ptr(y), _ptr(dy), t.size, f0, delta, nf, _ptr(ecc), ecc.size, _ptr(m0), m0.size,
+                                int(bool(fit_mean)), int(bool(psd)), _ptr(out["power"]), _ptr(out["cell"]),
+                                _ptr(out["cube"]), _ptr(best), _ptr(best_at), dev))
+    out["best"] = (float(best[0]), int(best_at[0]), int(best_at[1]))
+    return out
+
+
+def kepler_anomaly(phase, e, device=None):
+    """``(cos nu, sin nu)`` of the true anomaly at the mean anomalies ``phase`` (cycles, any finite value) of orbits of
+    eccentricity ``e`` (each in [0, 0.95]), by the solver of the Keplerian scan (``pdc_kepler_anomaly``)."""
+    phase, e = _f64(phase, "phase"), _f64(e, "e")
+    if e.size != phase.size:
+        raise ValueError("Input arrays have incompatible lengths.")
+    cos_nu, sin_nu = np.empty(phase.size), np.empty(phase.size)
+    dev = default_device() if device is None else device
+    check(lib().pdc_kepler_anomaly(_ptr(phase), _ptr(e), phase.size, _ptr(cos_nu), _ptr(sin_nu), dev))
+    return cos_nu, sin_nu
+
+
+def kepler_cell_group():
+    """Cells per thread of the Keplerian scan; no GPU needed."""
+    return int(lib().pdc_kepler_cell_group())
+
+
+def kepler_tile_bins():
+    """Bins per tile of the Keplerian scan; no GPU needed."""
+    return int(lib().pdc_kepler_tile_bins())
+
+
+def kepler_work_bytes(n, nf, ne, nm, want_cube=False):
+    """Workspace bytes of a Keplerian scan under the current ``PDC_WORK_BUDGET_GB`` (-1: sizes out of range); no GPU
+    needed."""
+    return int(lib().pdc_kepler_work_bytes(int(n), int(nf), int(ne), int(nm), int(bool(want_cube))))
+
+
+def kepler_last_dispatch():
+    """``(kc, groups, launches)`` of this thread's last Keplerian scan."""
+    kc, groups, launches = C.c_int(0), C.c_int(0), C.c_int64(0)
+    check(lib().pdc_kepler_last_dispatch(C.byref(kc), C.byref(groups), C.byref(launches)))
+    return kc.value, groups.value, launches.value
 
 
 def bls_scan(t, y, dy, periods, n_bins, len_min, len_max, min_points=5, dips_only=False, slices=0, device=None):

@@ -20,7 +20,7 @@ import numpy as np
 from . import _cabi
 from .core import FSeries, TSeries, _batch_errs, _batch_offsets, _batch_request, _batch_slots
 
-__all__ = ["GLS", "LombScargle", "BGLST", "MultiHarmonicGLS", "MultibandGLS", "HTest", "ZTest", "SpinSearch", "GLSBatch", "PeakTable"]
+__all__ = ["GLS", "LombScargle", "BGLST", "MultiHarmonicGLS", "KeplerianGLS", "BestOrbit", "MultibandGLS", "HTest", "ZTest", "SpinSearch", "GLSBatch", "PeakTable"]
 
 
 def _as_tseries(signal):
@@ -475,6 +475,173 @@ class MultiHarmonicGLS(GLS):
 
     def batch(self, *args, **kwargs):
         raise NotImplementedError("MultiHarmonicGLS.batch is not implemented: the ragged-grid batch computes GLS power only")
+
+
+BestOrbit = _collections.namedtuple("BestOrbit", "frequency e m0 power")
+
+
+def _frac_product(a, b):
+    """``frac(a * b)`` in [-1/2, 1/2] with the product carried exactly (Veltkamp split, Dekker product), as the kernels
+    reduce their cycles."""
+    a, b = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
+    hi = a * b
+    ca, cb = 134217729.0 * a, 134217729.0 * b
+    a1, b1 = ca - (ca - a), cb - (cb - b)
+    a2, b2 = a - a1, b - b1
+    lo = ((a1 * b1 - hi) + a1 * b2 + a2 * b1) + a2 * b2
+    return (hi - np.rint(hi)) + lo
+
+
+def _true_anomaly(cycles, e):
+    """``(cos nu, sin nu)`` at mean anomaly ``cycles`` by a bracketed Newton iteration in fp64.  O(N) host arithmetic
+    for ``orbit`` and ``model``, not part of the scan."""
+    cycles = np.asarray(cycles, dtype=float)
+    m = cycles - np.rint(cycles)
+    M = 2 * np.pi * np.abs(m)
+    lo, hi = np.zeros_like(M), np.full_like(M, np.pi)
+    E = M + e * np.sin(M)
+    for _ in range(64):
+        g = E - e * np.sin(E) - M
+        lo, hi = np.where(g < 0, E, lo), np.where(g > 0, E, hi)
+        step = E - g / (1 - e * np.cos(E))
+        E = np.where((step > lo) & (step < hi), step, 0.5 * (lo + hi))
+    inv = 1 / (1 - e * np.cos(E))
+    return (np.cos(E) - e) * inv, np.sign(m) * np.sqrt((1 - e) * (1 + e)) * np.sin(E) * inv
+
+
+class KeplerianGLS(GLS):
+    """Keplerian periodogram (Zechmeister & Kurster 2009, A&A 496, 577, section 4): at every trial frequency the best
+    weighted least-squares fit of a Keplerian orbit, scanned over a grid of eccentricities and times of periastron -
+    the statistic for radial-velocity curves of eccentric orbits, where a sinusoid loses most of the power.
+
+    The reference has no such class - **parity unpinned by the reference**.  Grid, weights, centring and the two
+    normalisations are those of ``GLS``.  With ``phi = frac(f (t - t[0]))``, ``M = 2 pi (phi - m0)``, ``E`` the solution
+    of ``E - e sin E = M`` and ``nu`` the true anomaly, the design columns are ``cos nu, sin nu`` plus a constant when
+    ``fit_mean``, and a cell ``(f, e, m0)`` holds ``b^T M^-1 b / YY`` as ``MultiHarmonicGLS`` defines it; the
+    periodogram is the largest cell of each frequency.  At ``e = 0`` a cell is the GLS power.  Evaluated by
+    ``csrc/kepler.hip``; nothing here computes a periodogram on the CPU.
+
+    Parameters
+    ----------
+    fmin, fmax, n, psd: as ``GLS``.
+    ecc: int or array, keyword-only, optional
+        Eccentricities, each in [0, 0.95]; an int gives ``np.linspace(0, 0.9, ecc)`` (default 10).
+    n_phase: int or array, keyword-only, optional
+        Mean anomalies at the first sample in cycles, each in [0, 1); an int gives ``np.arange(n_phase) / n_phase``
+        (default 32).  The time of periastron of a cell is ``t[0] + m0 / f``.
+    device: int, keyword-only, optional
+
+    After a call: ``.cell`` (per bin the index ``k * len(m0) + l`` of its best cell, -1 where every cell is NaN),
+    ``.eccentricity`` and ``.periastron_phase`` (per bin, NaN there), ``.cube`` (``[nf][ne][nm]``, None unless
+    ``want_cube``) and ``.best``, the ``BestOrbit(frequency, e, m0, power)`` of the highest bin.
+    """
+
+    MAX_ECC = 0.95
+    MAX_CELLS = 65535
+
+    def __init__(self, fmin=None, fmax=None, n=5, psd=False, *, ecc=10, n_phase=32, device=None):
+        self.ecc = self._list(ecc, "ecc", lambda k: np.linspace(0.0, 0.9, k), lambda a: (a >= 0) & (a <= self.MAX_ECC),
+                              f"in [0, {self.MAX_ECC}]")
+        self.m0 = self._list(n_phase, "n_phase", lambda k: np.arange(k) / k, lambda a: (a >= 0) & (a < 1), "in [0, 1)")
+        if self.ecc.size * self.m0.size > self.MAX_CELLS:
+            raise ValueError(f"at most {self.MAX_CELLS} cells (eccentricities times phases) per frequency")
+        super().__init__(fmin, fmax, n, psd, device=device)
+
+    @staticmethod
+    def _list(value, name, from_count, in_range, range_text):
+        if isinstance(value, bool):
+            raise ValueError(f"{name} must be a count or an array")
+        if isinstance(value, (int, np.integer)):
+            if value < 1:
+                raise ValueError(f"{name} must be at least 1")
+            return from_count(int(value))
+        a = np.array(value, dtype=float)
+        if a.ndim != 1 or a.size < 1:
+            raise ValueError(f"{name} must be a count or a one-dimensional array that is not empty")
+        if not np.all(in_range(a)):   # (NaN fails every comparison)
+            raise ValueError(f"every entry of {name} must be finite and {range_text}")
+        return a
+
+    def __call__(self, signal, err=None, fit_mean=True, want_cube=False):
+        """``FSeries(frequency, power)`` on the grid of ``GLS``, the power of a bin that of its best cell;
+        ``period_at_highest_peak`` etc. as for ``GLS``."""
+        signal = _as_tseries(signal)
+        self.frequency = self._grid(signal)
+        f0, delta, nf = _cabi.grid_params(self.frequency)
+        if nf < 2:   # a grid of one bin has no step of its own; any positive step rebuilds it
+            delta = 1.0
+        have_err = err is not None
+        if not have_err:
+            err = np.ones_like(signal.values)
+        dy = np.asarray(err, dtype=float) if have_err else None
+        t = np.asarray(signal.time, dtype=float)
+        y = np.asarray(signal.values, dtype=float)
+        dev = _cabi.pick_device(self.device, None)
+        out = _cabi.kepler_scan(t, y, dy, f0, delta, nf, self.ecc, self.m0, fit_mean, self.psd, want_cube=want_cube,
+                                device=dev)
+        self.err = err
+        self.fit_mean = bool(fit_mean)
+        self.signal = signal
+        self.cell = out["cell"]
+        self.cube = out["cube"]
+        found = self.cell >= 0
+        at = np.where(found, self.cell, 0)
+        self.eccentricity = np.where(found, self.ecc[at // self.m0.size], np.nan)
+        self.periastron_phase = np.where(found, self.m0[at % self.m0.size], np.nan)
+        value, bin_, cell = out["best"]
+        self.best_bin = bin_
+        self.best = (BestOrbit(np.nan, np.nan, np.nan, np.nan) if bin_ < 0 else
+                     BestOrbit(float(self.frequency[bin_]), float(self.ecc[cell // self.m0.size]),
+                               float(self.m0[cell % self.m0.size]), value))
+        self.periodogram = FSeries(self.frequency, out["power"])
+        return self.periodogram
+
+    def _bin(self, f0):
+        """The bin nearest ``f0`` (None: the best bin) of the last call, which must have a cell."""
+        j = self.best_bin if f0 is None else int(np.argmin(np.abs(self.frequency - f0)))
+        if j < 0 or self.cell[j] < 0:
+            raise ValueError("no cell of that bin has a value")
+        return j
+
+    def _fit(self, j):
+        """Host refit at bin ``j`` and its cell: ``(f, e, m0, ybar, theta)`` with theta the coefficients of
+        ``cos nu, sin nu`` and, with ``fit_mean``, the constant.  O(N) host arithmetic, not part of the scan."""
+        f, e, m0 = float(self.frequency[j]), float(self.eccentricity[j]), float(self.periastron_phase[j])
+        sigma = np.asarray(self.err, dtype=float)
+        t = np.asarray(self.signal.time, dtype=float)
+        y = np.asarray(self.signal.values, dtype=float)
+        ybar = np.dot(y, sigma ** -2.0) / np.sum(sigma ** -2.0) if self.fit_mean else 0.0
+        A = self._design(t, f, e, m0) / sigma[:, None]
+        theta = np.linalg.solve(A.T @ A, A.T @ ((y - ybar) / sigma))
+        return f, e, m0, ybar, theta
+
+    def _design(self, times, f, e, m0):
+        c, s = _true_anomaly(_frac_product(f, np.asarray(times, dtype=float) - float(self.signal.time[0])) - m0, e)
+        return np.stack([c, s] + ([np.ones_like(c)] if self.fit_mean else []), axis=1)
+
+    def orbit(self, f0=None):
+        """The orbit fitted at the bin nearest ``f0`` (None: the best bin) and that bin's cell, as a dict
+        ``period, K, e, omega, gamma, t_peri`` of ``y = K (cos(nu + omega) + e cos omega) + gamma``: with the fitted
+        coefficients ``A cos nu + B sin nu + const``, ``A = K cos omega``, ``B = -K sin omega``,
+        ``gamma = const - K e cos omega + ybar`` and ``t_peri = t[0] + m0 / f``."""
+        f, e, m0, ybar, theta = self._fit(self._bin(f0))
+        A, B = float(theta[0]), float(theta[1])
+        const = float(theta[2]) if self.fit_mean else 0.0
+        return {"period": 1.0 / f, "K": float(np.hypot(A, B)), "e": e, "omega": float(np.arctan2(-B, A) % (2 * np.pi)),
+                "gamma": const - A * e + ybar, "t_peri": float(self.signal.time[0]) + m0 / f}
+
+    def model(self, tf, f0=None):
+        """The orbit of ``orbit(f0)`` evaluated at times ``tf``."""
+        f, e, m0, ybar, theta = self._fit(self._bin(f0))
+        return TSeries(tf, ybar + self._design(tf, f, e, m0) @ theta)
+
+    def bootstrap(self, *args, **kwargs):
+        raise NotImplementedError("KeplerianGLS has no bootstrap yet: the batched replicate kernels compute GLS power only")
+
+    fap = fal = bootstrap
+
+    def batch(self, *args, **kwargs):
+        raise NotImplementedError("KeplerianGLS.batch is not implemented: the ragged-grid batch computes GLS power only")
 
 
 class MultibandGLS(GLS):
