@@ -394,6 +394,45 @@ int64_t pdc_kepler_work_bytes(int64_t n, int64_t nf, int64_t ne, int64_t nm, int
  * thread, cell groups, launches of the scan kernel (slabs).  Any pointer may be NULL. */
 int pdc_kepler_last_dispatch(int *kc, int *groups, int64_t *launches);
 
+/* ---- DCF: the discrete correlation function (Edelson & Krolik 1988, ApJ 333, 646) --------------------------------------
+ * The reference has an autocorrelation for evenly sampled series only (an inverse FFT on median_dt, core.py:578-608) and
+ * no cross-correlation - PARITY UNPINNED BY THE REFERENCE.  Auto- and cross-correlation of unevenly sampled curves: every
+ * ordered pair of a sample i of (ta[na], a[na]) and a sample j of (tb[nb], b[nb]) is binned by its lag; nothing is
+ * interpolated.  Times are finite and never decrease; a and b are taken as they come (centring is the caller's);
+ * edges[nlag + 1] is finite and strictly increasing.  THE DEFINITION: pair (i, j) has lag d = fl(tb[j] - ta[i]), one IEEE
+ * double subtraction, and belongs to bin k iff edges[k] <= d < edges[k+1], compared in double - no other form of the
+ * comparison is evaluated anywhere, so a pair with edges[0] <= d < edges[nlag] is in exactly one bin.  With
+ * skip_same_index the pairs i == j are left out (autocorrelation: na == nb, the same arrays twice).  Per bin:
+ *     pairs_out[k]            the count;
+ *     sums_out[6][nlag]       Sa = sum a_i, Sb = sum b_j, Saa = sum a_i^2, Sbb = sum b_j^2, Sab = sum a_i b_j,
+ *                             Sabab = sum (a_i b_j)^2 over the bin's pairs, in this order;
+ * an empty bin has count 0 and six sums of exactly 0.0.  A NaN in a or b is no error: it reaches the sums of the bins
+ * its pairs fall in (a_i: Sa, Saa, Sab, Sabab; b_j: Sb, Sbb, Sab, Sabab) and no others.  To first order in 2^-53 each
+ * sum is within (pairs[k] + 8) 2^-53 sum |term| of its exact value (the bound the tests hold it to).  The i are cut into chunks of `chunk` consecutive samples (0: the
+ * library chooses, pdc_dcf_chunk; positive: a test and tuning hook, like `slices` of pdc_bls_scan), each chunk writes a
+ * slab of partial sums to the workspace and the slabs are summed in chunk order: no atomics, the same bits from call to
+ * call (another chunk: other roundings, the same counts).  PDC_WORK_BUDGET_GB enlarges the chunk until the slabs fit; a
+ * budget that not even one chunk of all samples fits in is an error.  Checked before any device is looked for: 0 <= na,
+ * nb <= 2^31 - 64 (0 is valid: all-zero outputs), 1 <= nlag <= 2^22, chunk >= 0 and fewer than 2^24 chunks, skip_same_index only with na == nb, no NULL
+ * argument, and in the host form finite times that never decrease and finite, strictly increasing edges (the `_dev` form
+ * cannot look at them: they are its caller's precondition, and no value of them indexes memory out of bounds).  The
+ * `_dev` form takes device pointers, enqueues on `stream` and keeps its own workspace per (device, stream). */
+int pdc_dcf_scan(const double *ta, const double *a, int64_t na, const double *tb, const double *b, int64_t nb,
+                 const double *edges, int64_t nlag, int skip_same_index, int64_t chunk, int64_t *pairs_out,
+                 double *sums_out, int device);
+int pdc_dcf_scan_dev(int device, void *stream, const double *d_ta, const double *d_a, int64_t na, const double *d_tb,
+                     const double *d_b, int64_t nb, const double *d_edges, int64_t nlag, int skip_same_index,
+                     int64_t chunk, int64_t *d_pairs, double *d_sums);
+/* Workspace bytes of a scan under the current PDC_WORK_BUDGET_GB (chunk as for the scan); -1 for sizes the scan
+ * refuses.  No GPU needed. */
+int64_t pdc_dcf_work_bytes(int64_t na, int64_t nb, int64_t nlag, int64_t chunk);
+/* The samples per chunk the library chooses for chunk == 0 under the current PDC_WORK_BUDGET_GB (at least 1); -1 for
+ * sizes the scan refuses.  No GPU needed. */
+int64_t pdc_dcf_chunk(int64_t na, int64_t nb, int64_t nlag);
+/* What the CALLING THREAD's last DCF scan launched (as pdc_htest_last_dispatch; zeros before the first): the chunks
+ * (0: a curve was empty) and the samples per chunk.  Any pointer may be NULL. */
+int pdc_dcf_last_dispatch(int64_t *chunks, int64_t *chunk);
+
 /* ---- BLS: box least squares (Kovacs, Zucker & Mazeh 2002, A&A 391, 369) ----------------------------------------------
  * The reference has no such class - PARITY UNPINNED BY THE REFERENCE.  The search for a box-shaped dip (a transit, a
  * detached eclipse): per trial period the best two-level model of the folded curve.  Weights and centring as

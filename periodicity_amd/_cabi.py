@@ -74,6 +74,11 @@ PROTOTYPES = {
     "pdc_kepler_tile_bins": (_L, []),
     "pdc_kepler_work_bytes": (_L, [_L, _L, _L, _L, _I]),
     "pdc_kepler_last_dispatch": (_I, [C.POINTER(_I), C.POINTER(_I), c_int64_p]),
+    "pdc_dcf_scan": (_I, [_VP, _VP, _L, _VP, _VP, _L, _VP, _L, _I, _L, _VP, _VP, _I]),
+    "pdc_dcf_scan_dev": (_I, [_I, _VP, _VP, _VP, _L, _VP, _VP, _L, _VP, _L, _I, _L, _VP, _VP]),
+    "pdc_dcf_work_bytes": (_L, [_L, _L, _L, _L]),
+    "pdc_dcf_chunk": (_L, [_L, _L, _L]),
+    "pdc_dcf_last_dispatch": (_I, [c_int64_p, c_int64_p]),
     "pdc_bls_scan": (_I, [_VP, _VP, _VP, _L, _VP, _L, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _I]),
     "pdc_bls_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _VP, _L, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "pdc_bls_scan_ragged": (_I, [_VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I,
@@ -512,6 +517,43 @@ def kepler_last_dispatch():
     kc, groups, launches = C.c_int(0), C.c_int(0), C.c_int64(0)
     check(lib().pdc_kepler_last_dispatch(C.byref(kc), C.byref(groups), C.byref(launches)))
     return kc.value, groups.value, launches.value
+
+
+def dcf_scan(ta, a, tb, b, edges, skip_same_index=False, chunk=0, device=None):
+    """Discrete correlation function (``pdc_dcf_scan``): every ordered pair of a sample of ``(ta, a)`` and a sample
+    of ``(tb, b)`` binned by its lag ``tb[j] - ta[i]`` into ``edges[k] <= lag < edges[k+1]``; times that never decrease.
+    Returns ``(pairs, sums)``: the int64 count per bin and the ``[6][nlag]`` sums Sa, Sb, Saa, Sbb, Sab, Sabab.
+    ``skip_same_index`` leaves out the pairs ``i == j`` (autocorrelation: pass the same arrays twice); ``chunk``:
+    samples of the first curve per partial sum (0: chosen from the shape; every value gives the same counts)."""
+    same = ta is tb and a is b
+    ta, a, edges = _f64(ta, "ta"), _f64(a, "a"), _f64(edges, "edges")
+    tb, b = (ta, a) if same else (_f64(tb, "tb"), _f64(b, "b"))
+    if a.size != ta.size or b.size != tb.size:
+        raise ValueError("Input arrays have incompatible lengths.")
+    nlag = edges.size - 1
+    pairs, sums = np.empty(max(nlag, 0), dtype=np.int64), np.empty((6, max(nlag, 0)))
+    dev = default_device() if device is None else device
+    check(lib().pdc_dcf_scan(_ptr(ta), _ptr(a), ta.size, _ptr(tb), _ptr(b), tb.size, _ptr(edges), nlag,
+                             int(bool(skip_same_index)), int(chunk), _ptr(pairs), _ptr(sums), dev))
+    return pairs, sums
+
+
+def dcf_chunk(na, nb, nlag):
+    """Samples per chunk a DCF scan would choose under the current ``PDC_WORK_BUDGET_GB`` (-1: sizes out of range); no
+    GPU needed."""
+    return int(lib().pdc_dcf_chunk(int(na), int(nb), int(nlag)))
+
+
+def dcf_work_bytes(na, nb, nlag, chunk=0):
+    """Workspace bytes of a DCF scan under the current ``PDC_WORK_BUDGET_GB`` (-1: sizes out of range); no GPU needed."""
+    return int(lib().pdc_dcf_work_bytes(int(na), int(nb), int(nlag), int(chunk)))
+
+
+def dcf_last_dispatch():
+    """``(chunks, chunk)`` of this thread's last DCF scan."""
+    chunks, chunk = C.c_int64(0), C.c_int64(0)
+    check(lib().pdc_dcf_last_dispatch(C.byref(chunks), C.byref(chunk)))
+    return chunks.value, chunk.value
 
 
 def bls_scan(t, y, dy, periods, n_bins, len_min, len_max, min_points=5, dips_only=False, slices=0, device=None):
