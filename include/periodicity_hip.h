@@ -816,6 +816,17 @@ int64_t pdc_phase_work_bytes(int kind, int64_t n, int64_t n_periods, int nb, int
 int pdc_phase_scan_dev(int kind, int device, void *stream, const double *d_t, const double *d_v, int64_t n,
                        const double *d_periods, int64_t n_periods, int nb, int nc, double sigma,
                        double *d_out, void *work, int64_t work_bytes);
+/* TEST HOOKS (not for callers): the route of the phase-binning scans (kinds 0, 1, 2 and 4; every entry above ends in one
+ * dispatcher, and one host function chooses its route).  pdc_test_phase_shape gives the route a scan of that shape would
+ * take in this process - PDC_PDM_SPLIT and PDC_PDM_NZ are honoured as the launcher honours them - and touches no device;
+ * pdc_test_phase_last_dispatch gives the route of the last launch in this process, written on the host just before the
+ * kernels go out (all zeros before the first).  out[11] = kind, 1 in split mode (sample statistics from two launches of
+ * their own, the samples cut in slices on grid.y, a finishing launch), threads per workgroup of the scan kernel, waves
+ * that share one group of 64 trial periods, trial periods per workgroup, workgroups in x, sample slices (1: not cut),
+ * samples per slice (0 when unsplit), partial sums of the sample statistics (0 when unsplit), dynamic LDS bytes of the
+ * scan kernel, dynamic LDS bytes of the finishing kernel (0 when unsplit). */
+int pdc_test_phase_shape(int kind, int64_t n, int64_t n_periods, int nb, int nc, int64_t *out);
+int pdc_test_phase_last_dispatch(int64_t *out);
 
 /* The period grid cut into contiguous slabs over `n_devices` GPUs of this node (one process, one
  * stream per slab; a device may be listed more than once).  Replaces the multiprocessing.Pool

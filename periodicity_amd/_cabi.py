@@ -160,6 +160,8 @@ PROTOTYPES = {
     "pdc_gl_scan_dev": (_I, [_I, _VP, _VP, _L, _VP, _L, _I, _I, _VP]),
     "pdc_phase_work_bytes": (_L, [_I, _L, _L, _I, _I]),
     "pdc_phase_scan_dev": (_I, [_I, _I, _VP, _VP, _VP, _L, _VP, _L, _I, _I, _D, _VP, _VP, _L]),
+    "pdc_test_phase_shape": (_I, [_I, _L, _L, _I, _I, c_int64_p]),
+    "pdc_test_phase_last_dispatch": (_I, [c_int64_p]),
     "pdc_pdm_scan_multi": (_I, [_VP, _VP, _L, _VP, _L, _I, _I, _D, _VP, _VP, _I]),
     "pdc_aov_scan_multi": (_I, [_VP, _VP, _L, _VP, _L, _I, _VP, _VP, _I]),
     "pdc_cond_entropy_scan_multi": (_I, [_VP, _VP, _L, _VP, _L, _I, _I, _VP, _VP, _I]),
@@ -1076,6 +1078,25 @@ def stringlength_scan(t, m, periods, device=None, devices=None):
 
 
 PHASE_KINDS = {"pdm": 0, "aov": 1, "cond_entropy": 2, "stringlength": 3, "gregory_loredo": 4, "supersmoother": 5}
+_PHASE_DISPATCH_FIELDS = ("kind", "split", "block", "waves", "periods_per_wg", "workgroups", "n_z", "z_len", "n_stat",
+                          "scan_lds", "finish_lds")
+
+
+def phase_shape(kind, n, n_periods, nb, nc=1):
+    """TEST HOOK (``pdc_test_phase_shape``): the route a phase-binning scan of this shape would take in this process,
+    as a dict; no device is touched.  ``kind``: a key of ``PHASE_KINDS`` or its number; ``nb``, ``nc`` as
+    ``pdc_phase_scan_dev`` takes them (Gregory-Loredo: ``nb = m * n_offsets``, ``nc = m``)."""
+    out = (C.c_int64 * len(_PHASE_DISPATCH_FIELDS))()
+    check(lib().pdc_test_phase_shape(PHASE_KINDS.get(kind, kind), int(n), int(n_periods), int(nb), int(nc), out))
+    return dict(zip(_PHASE_DISPATCH_FIELDS, (int(v) for v in out)))
+
+
+def phase_last_dispatch():
+    """TEST HOOK (``pdc_test_phase_last_dispatch``): the route of the last phase-binning launch in this process, with
+    the keys of :func:`phase_shape`; all zeros before the first."""
+    out = (C.c_int64 * len(_PHASE_DISPATCH_FIELDS))()
+    check(lib().pdc_test_phase_last_dispatch(out))
+    return dict(zip(_PHASE_DISPATCH_FIELDS, (int(v) for v in out)))
 
 
 def supersmoother_scan(t, y, periods, alpha=0.0, device=None, devices=None):

@@ -26,7 +26,7 @@
 #include "pdc_internal.h"
 
 #include <cstdlib>
-#include <type_traits>
+#include <mutex>
 
 using namespace pdc;
 
@@ -285,57 +285,68 @@ __global__ __launch_bounds__(64 * kFinZ) void pdm_finish_kernel(PdmArgs a) {
 }
 
 // dynamic-LDS limit of a kernel, raised once per device (not on every call)
+constexpr size_t kScanLdsCap = 150 * 1024;   // the scan kernels'
+constexpr size_t kFinLdsCap = 128 * 1024;    // the finishing kernel's (+ 24 KB of its own)
 template <typename Kernel>
 int allow_lds(Kernel kernel) {
-    return allow_dynamic_lds((const void *)kernel, 150 * 1024);
+    return allow_dynamic_lds((const void *)kernel, (int)kScanLdsCap);
 }
 
-// Split mode (few trial periods, many samples; see phase_stat_dev): how the samples are cut and how
-// much scratch the partial histograms take.  n_z == 1: not split.
-struct SplitShape {
-    bool use = false;   // take the split mode (possibly with ONE slice: statistics once per launch, not per workgroup)
+// The ONE place where the route of a phase-binning scan is chosen (phase_stat_dev only carries it out;
+// pdc_test_phase_shape reports it without a device, pdc_test_phase_last_dispatch what the last launch took).
+//   unsplit: one launch of pdm_scan_kernel<block, waves>; every workgroup reduces the sample statistics itself
+//   split (few trial periods, many samples): pdm_stats_kernel x2, pdm_scan_kernel<256, 4, ZS> over n_z slices of
+//            z_len samples on blockIdx.y, pdm_finish_kernel - and how much scratch the partial histograms take
+struct PhaseRoute {
+    int kind = 0;
+    bool split = false;   // the split mode (possibly with ONE slice: statistics once per launch, not per workgroup)
+    int block = 0;        // threads per workgroup of the scan kernel (0: nothing is launched)
+    int waves = 0;        // SPLIT: waves that share a group of 64 trial periods
+    int per_wg = 0;       // trial periods per workgroup
+    int64_t wgs = 0;      // workgroups in x
     int64_t n_z = 1, z_len = 0, p_pad = 0, bytes = 0;
     int n_stat = 0;
+    size_t scan_lds = 0, fin_lds = 0;   // dynamic LDS of the scan / finishing kernel
     size_t stat_b = 0, psum_b = 0, pq_b = 0, pcnt_b = 0;
 };
 
-
-SplitShape split_shape(int kind, int64_t n, int64_t n_periods, int nb, int nc) {
+PhaseRoute phase_route(int kind, int64_t n, int64_t n_periods, int nb, int nc) {
     static const int env_split = [] { const char *e = getenv("PDC_PDM_SPLIT"); return e ? atoi(e) : -1; }();
-    SplitShape sh;
+    // PDC_PDM_NZ forces the slice count where the rounds-filled score would choose it (experiments)
+    static const int env_nz = [] { const char *e = getenv("PDC_PDM_NZ"); return e ? atoi(e) : 0; }();
+    PhaseRoute r;
+    r.kind = kind;
     if (kind == 1) nc = 1;
     const int m0 = kind >= 2 ? nb : nb * nc;
     const int last = kind == 2 ? (nb + 1) * nc - 1 : m0;
     const int nbins = last + 1;
     const int64_t groups0 = (n_periods + 63) / 64;
     const bool counts_only = kind >= 2;
+    const int bpb = counts_only ? 4 : 12;
+    if (n_periods == 0) return r;
     // the counts-only kinds MUST cut more than kCellSamples samples into slices (16-bit cells); everything
     // else about the split is a choice, which PDC_PDM_SPLIT=0 turns off
     const int64_t must_z = counts_only ? (n + kCellSamples - 1) / kCellSamples : 1;
-    if (n_periods == 0 || n == 0) return sh;
-    const bool may = env_split != 0 && n >= 32 * kChunk && lds_bytes(last, 256, counts_only ? 4 : 12) <= 150 * 1024 &&
-                     (size_t)nbins * 64 * (counts_only ? 8 : 16) <= 128 * 1024;   // (+ 24 KB of the finishing kernel's own)
-    if (!may && must_z <= 1) return sh;
+    const bool may = env_split != 0 && n >= 32 * kChunk && lds_bytes(last, 256, bpb) <= kScanLdsCap &&
+                     (size_t)nbins * 64 * (counts_only ? 8 : 16) <= kFinLdsCap;
     const int64_t max_z = n / (8 * kChunk) > must_z ? n / (8 * kChunk) : must_z;
-    int64_t n_z = 1;
-    if (!may) {
-        n_z = must_z;
-    } else if (groups0 * 4 < 3072) {
+    // slices asked for; 0: unsplit
+    const int64_t asked = [&]() -> int64_t {
+        if (n == 0 || (!may && must_z <= 1)) return 0;
+        if (!may) return must_z;
         // (four workgroups of four waves fit a CU: below ~3000 waves the period grid alone leaves SIMD slots empty)
-        n_z = (4096 + groups0 * 4 - 1) / (groups0 * 4);
-    } else {
+        if (groups0 * 4 < 3072) return (4096 + groups0 * 4 - 1) / (groups0 * 4);
         // Enough waves - but workgroups come in rounds of kSlots (4 per CU, LDS-limited), and a last round
         // that is half empty costs as much as a full one: C5's 1563 workgroups take two rounds for 1.53
         // rounds' worth of work.  Cutting the samples in n_z slices multiplies the workgroups (each a slice
         // shorter): take the n_z <= 16 with the best (share of its rounds filled) - (cost of its slices), or
-        // the unsplit grid if that scores higher.  PDC_PDM_NZ forces a value (experiments).
-        static const int env_nz = [] { const char *e = getenv("PDC_PDM_NZ"); return e ? atoi(e) : 0; }();
+        // the unsplit grid if that scores higher.
         // resident workgroups of the scan kernel: LDS-limited (PDM at nb x nc = 10: 38 KB -> 4 per CU, 1024 on
         // the chip; the counts-only kinds with many cells hold fewer), at most 8 per CU (4 waves each)
-        const int64_t per_cu = kLdsPerCU / (int64_t)(lds_bytes(last, 256, counts_only ? 4 : 12) + 512);
+        const int64_t per_cu = kLdsPerCU / (int64_t)(lds_bytes(last, 256, bpb) + 512);
         const int64_t kSlots = kCUs * (per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu));
         auto rounds_filled = [&](int64_t w) { return (double)w / (double)((w + kSlots - 1) / kSlots * kSlots); };
-        // the unsplit launch packs 64, 128 or 256 periods into a workgroup (phase_stat_dev below), and every
+        // the unsplit launch packs 64, 128 or 256 periods into a workgroup (below), and every
         // one of its workgroups reduces the sample statistics by itself (two passes over all samples: ~5 % of
         // a C5 workgroup's time) where the split mode has them from two short launches.  A slice costs its
         // partial histograms through L2 and a share of the finishing launch: ~1.2 % each (measured at C5:
@@ -343,7 +354,7 @@ SplitShape split_shape(int kind, int64_t n, int64_t n_periods, int nb, int nc) {
         // 1.3e5 periods 6.50 ms against 5.91 in 5 slices)
         const int64_t w_unsplit = groups0 >= 4096 ? (groups0 + 3) / 4 : (groups0 >= 2048 ? (groups0 + 1) / 2 : groups0);
         double best = rounds_filled(w_unsplit) - 0.05;
-        n_z = 0;   // 0: unsplit
+        int64_t n_z = 0;
         // (slices of at most ~16k samples measured best wherever they were tried - N = 5e4: 5 slices, 1e5: 8 -
         // beyond what the filled rounds explain)
         int64_t z_min = (n + 16383) / 16384;
@@ -357,33 +368,81 @@ SplitShape split_shape(int kind, int64_t n, int64_t n_periods, int nb, int nc) {
             }
         }
         if (env_nz > 0) n_z = env_nz;
-        if (n_z == 0 && must_z <= 1) return sh;
-        if (n_z == 0) n_z = must_z;
+        if (n_z == 0 && must_z > 1) n_z = must_z;
+        return n_z;
+    }();
+    if (asked == 0) {
+        // waves = ceil(P/64) * SPLIT; aim at >= 4 waves per SIMD (4096 on the chip).  A [bin][thread] histogram of
+        // 256 threads that does not fit the LDS cap runs one wave per workgroup.
+        if (lds_bytes(last, 256, bpb) > kScanLdsCap) r.block = 64, r.waves = 1;
+        else r.block = 256, r.waves = groups0 >= 4096 ? 1 : (groups0 >= 2048 ? 2 : 4);
+        r.per_wg = r.block / r.waves;
+        r.wgs = (n_periods + r.per_wg - 1) / r.per_wg;
+        r.scan_lds = lds_bytes(last, r.block, bpb);
+        return r;
     }
-    n_z = n_z < max_z ? n_z : max_z;
+    int64_t n_z = asked < max_z ? asked : max_z;
     n_z = n_z > must_z ? n_z : must_z;
     n_z = n_z < 1 ? 1 : n_z;
     int64_t z_len = ((n + n_z - 1) / n_z + kChunk - 1) / kChunk * kChunk;
     if (counts_only && z_len > kCellSamples) z_len = kCellSamples;   // (kCellSamples is a multiple of kChunk)
     n_z = (n + z_len - 1) / z_len;
-    sh.use = true;
-    sh.n_z = n_z;
-    sh.z_len = z_len;
-    sh.p_pad = groups0 * 64;
-    sh.n_stat = (int)((n + 1023) / 1024 < kStatParts ? (n + 1023) / 1024 : kStatParts);
-    sh.stat_b = (size_t)3 * kStatParts * 8;
-    sh.psum_b = counts_only ? 0 : (size_t)n_z * nbins * sh.p_pad * 8;
-    sh.pq_b = counts_only ? 0 : (size_t)n_z * 2 * sh.p_pad * 8;
-    sh.pcnt_b = (size_t)n_z * (counts_only ? (nbins + 1) / 2 : nbins) * sh.p_pad * 4;
-    sh.bytes = (int64_t)(sh.stat_b + sh.psum_b + sh.pq_b + sh.pcnt_b);
-    return sh;
+    r.split = true;
+    r.block = 256;
+    r.waves = 4;
+    r.per_wg = 64;
+    r.wgs = groups0;
+    r.scan_lds = lds_bytes(last, 256, bpb);
+    r.fin_lds = (size_t)nbins * 64 * (counts_only ? 8 : 16);
+    r.n_z = n_z;
+    r.z_len = z_len;
+    r.p_pad = groups0 * 64;
+    r.n_stat = (int)((n + 1023) / 1024 < kStatParts ? (n + 1023) / 1024 : kStatParts);
+    r.stat_b = (size_t)3 * kStatParts * 8;
+    r.psum_b = counts_only ? 0 : (size_t)n_z * nbins * r.p_pad * 8;
+    r.pq_b = counts_only ? 0 : (size_t)n_z * 2 * r.p_pad * 8;
+    r.pcnt_b = (size_t)n_z * (counts_only ? (nbins + 1) / 2 : nbins) * r.p_pad * 4;
+    r.bytes = (int64_t)(r.stat_b + r.psum_b + r.pq_b + r.pcnt_b);
+    return r;
+}
+
+// The arguments every entry checks before it asks for a route.
+bool phase_shape_ok(int kind, int64_t n, int64_t n_periods, int nb, int nc) {
+    return !(kind < 0 || kind > 4 || kind == 3 || n < 0 || n_periods < 0 || nb < 1 || nc < 1);
+}
+
+// TEST HOOK (pdc_test_phase_last_dispatch): the route of the last phase_stat_dev launch in this process, written on
+// the host just before the launches.
+constexpr int kRouteFields = 11;
+std::mutex g_last_route_lock;
+int64_t g_last_route[kRouteFields] = {};
+void route_fields(const PhaseRoute &r, int64_t *out) {
+    const int64_t v[kRouteFields] = {r.kind, r.split ? 1 : 0, r.block, r.waves, r.per_wg, r.wgs, r.n_z, r.z_len, r.n_stat,
+                                     (int64_t)r.scan_lds, (int64_t)r.fin_lds};
+    for (int i = 0; i < kRouteFields; ++i) out[i] = v[i];
+}
+
+// The scan kernel of a route: the instance <block, waves, split> of statistic K.
+template <int K>
+int launch_scan(const PhaseRoute &r, const PdmArgs &a, hipStream_t st) {
+    auto go = [&](auto kernel) -> int {
+        PDC_TRY(allow_lds(kernel));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)r.wgs, (unsigned)(r.split ? r.n_z : 1)), dim3((unsigned)r.block),
+                           r.scan_lds, st, a);
+        return PDC_OK;
+    };
+    if (r.split) return go(pdm_scan_kernel<256, 4, true, K>);
+    if (r.block == 64) return go(pdm_scan_kernel<64, 1, false, K>);
+    if (r.waves == 1) return go(pdm_scan_kernel<256, 1, false, K>);
+    if (r.waves == 2) return go(pdm_scan_kernel<256, 2, false, K>);
+    return go(pdm_scan_kernel<256, 4, false, K>);
 }
 
 }  // namespace
 
 int64_t pdc::phase_stat_work_bytes(int kind, int64_t n, int64_t n_periods, int nb, int nc) {
-    if (kind < 0 || kind > 4 || kind == 3 || n < 0 || n_periods < 0 || nb < 1 || nc < 1) return -1;
-    return split_shape(kind, n, n_periods, nb, nc).bytes;
+    if (!phase_shape_ok(kind, n, n_periods, nb, nc)) return -1;
+    return phase_route(kind, n, n_periods, nb, nc).bytes;
 }
 
 // kind 0: PDM theta; 1: AoV over nb phase bins; 2: conditional entropy over nb x nc cells.
@@ -406,79 +465,68 @@ int pdc::phase_stat_dev(int kind, int device, hipStream_t st, const double *d_t,
     PdmArgs a{d_t, d_x, d_periods, n, n_periods, nb, nc, sigma, d_out};
     a.kind = kind;
     // Few trial periods and many samples (the reference's default grid has 1000 periods): lanes are
-    // periods, so the period grid alone would leave most of the chip idle.  Split the SAMPLES over
+    // periods, so the period grid alone would leave most of the chip idle.  The split mode cuts the SAMPLES over
     // blockIdx.y as well: statistics once (two short grid-wide launches), partial histograms per
-    // slice, one finishing launch that adds them in slice order.  PDC_PDM_SPLIT=0 disables it.
-    const int64_t groups0 = (n_periods + 63) / 64;
-    const int nbins = last + 1;
-    const SplitShape sh = split_shape(kind, n, n_periods, nb, nc);
-    if (sh.use) {
-        a.p_pad = sh.p_pad;
-        a.n_z = (int)sh.n_z;
-        a.z_len = sh.z_len;
-        a.n_stat = sh.n_stat;
-        PDC_TRY(allow_dynamic_lds((const void *)pdm_finish_kernel, 128 * 1024));   // (+ 24 KB of its own)
-        void *spv = work;
-        ScratchPin pin;
+    // slice, one finishing launch that adds them in slice order.  phase_route decides; PDC_PDM_SPLIT=0 disables it.
+    const PhaseRoute r = phase_route(kind, n, n_periods, nb, nc);
+    {
+        std::lock_guard<std::mutex> hold(g_last_route_lock);
+        route_fields(r, g_last_route);
+    }
+    void *spv = work;
+    ScratchPin pin;
+    if (r.split) {
+        a.p_pad = r.p_pad;
+        a.n_z = (int)r.n_z;
+        a.z_len = r.z_len;
+        a.n_stat = r.n_stat;
+        PDC_TRY(allow_dynamic_lds((const void *)pdm_finish_kernel, (int)kFinLdsCap));
         if (work) {
-            PDC_REQUIRE(work_bytes >= sh.bytes, "phase scan: workspace too small (%lld < %lld bytes)",
-                        (long long)work_bytes, (long long)sh.bytes);
+            PDC_REQUIRE(work_bytes >= r.bytes, "phase scan: workspace too small (%lld < %lld bytes)",
+                        (long long)work_bytes, (long long)r.bytes);
         } else {   // cached per (device, stream): see pdc_internal.h on why not hipMallocAsync
-            PDC_TRY(pin.take(device, st, sh.bytes, &spv));
+            PDC_TRY(pin.take(device, st, r.bytes, &spv));
         }
         char *const sp = static_cast<char *>(spv);
         // PDC_PDM_POISON=1 fills the scratch with a NaN pattern first (debugging aid: every word the kernels
         // read must have been written by them)
         static const bool poison = [] { const char *e = getenv("PDC_PDM_POISON"); return e && e[0] == '1'; }();
-        if (poison) PDC_HIP(hipMemsetAsync(sp, 0x7f, (size_t)sh.bytes, st));
+        if (poison) PDC_HIP(hipMemsetAsync(sp, 0x7f, (size_t)r.bytes, st));
         a.stat = reinterpret_cast<double *>(sp);
-        a.psum = reinterpret_cast<double *>(sp + sh.stat_b);
-        a.pq = reinterpret_cast<double *>(sp + sh.stat_b + sh.psum_b);
-        a.pcnt = reinterpret_cast<unsigned *>(sp + sh.stat_b + sh.psum_b + sh.pq_b);
+        a.psum = reinterpret_cast<double *>(sp + r.stat_b);
+        a.pq = reinterpret_cast<double *>(sp + r.stat_b + r.psum_b);
+        a.pcnt = reinterpret_cast<unsigned *>(sp + r.stat_b + r.psum_b + r.pq_b);
         hipLaunchKernelGGL(pdm_stats_kernel, dim3((unsigned)a.n_stat), dim3(256), 0, st, a, 0);
         hipLaunchKernelGGL(pdm_stats_kernel, dim3((unsigned)a.n_stat), dim3(256), 0, st, a, 1);
-        // (the statistic only matters to the finishing launch - and, for the counts-only kinds, to what the
-        // histogram holds; it is a template argument so that a profile tells the launches apart)
-        const size_t zlds = lds_bytes(last, 256, kind >= 2 ? 4 : 12);
-        const dim3 zgrid((unsigned)groups0, (unsigned)sh.n_z);
-        auto zlaunch = [&](auto kernel) -> int {
-            PDC_TRY(allow_lds(kernel));
-            hipLaunchKernelGGL(kernel, zgrid, dim3(256), zlds, st, a);
-            return PDC_OK;
-        };
-        if (kind == 4) PDC_TRY(zlaunch(pdm_scan_kernel<256, 4, true, 4>));
-        else if (kind == 2) PDC_TRY(zlaunch(pdm_scan_kernel<256, 4, true, 2>));
-        else if (kind == 1) PDC_TRY(zlaunch(pdm_scan_kernel<256, 4, true, 1>));
-        else PDC_TRY(zlaunch(pdm_scan_kernel<256, 4, true, 0>));
-        hipLaunchKernelGGL(pdm_finish_kernel, dim3((unsigned)groups0), dim3(64 * kFinZ), (size_t)nbins * 64 * (kind >= 2 ? 8 : 16), st, a);
-        PDC_HIP(hipGetLastError());
-        return PDC_OK;
     }
-    const int bpb = kind >= 2 ? 4 : 12;
-    auto launch = [&](auto kernel, int block, int periods_per_block) -> int {
-        PDC_TRY(allow_lds(kernel));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((n_periods + periods_per_block - 1) / periods_per_block)),
-                           dim3((unsigned)block), lds_bytes(last, block, bpb), st, a);
-        return PDC_OK;
-    };
-    auto launch_kind = [&](auto kind_tag) -> int {
-        constexpr int K = decltype(kind_tag)::value;
-        if (lds_bytes(last, 256, bpb) > 150 * 1024) return launch(pdm_scan_kernel<64, 1, false, K>, 64, 64);
-        // waves = ceil(P/64) * SPLIT; aim at >= 4 waves per SIMD (4096 on the chip)
-        const int64_t groups = (n_periods + 63) / 64;
-        if (groups >= 4096) return launch(pdm_scan_kernel<256, 1, false, K>, 256, 256);
-        if (groups >= 2048) return launch(pdm_scan_kernel<256, 2, false, K>, 256, 128);
-        return launch(pdm_scan_kernel<256, 4, false, K>, 256, 64);
-    };
-    if (kind == 4) PDC_TRY(launch_kind(std::integral_constant<int, 4>{}));
-    else if (kind == 2) PDC_TRY(launch_kind(std::integral_constant<int, 2>{}));
-    else if (kind == 1) PDC_TRY(launch_kind(std::integral_constant<int, 1>{}));
-    else PDC_TRY(launch_kind(std::integral_constant<int, 0>{}));
+    // (the statistic only matters to the epilogue - and, for the counts-only kinds, to what the histogram holds;
+    // it is a template argument so that a profile tells the launches apart)
+    if (kind == 4) PDC_TRY(launch_scan<4>(r, a, st));
+    else if (kind == 2) PDC_TRY(launch_scan<2>(r, a, st));
+    else if (kind == 1) PDC_TRY(launch_scan<1>(r, a, st));
+    else PDC_TRY(launch_scan<0>(r, a, st));
+    if (r.split) hipLaunchKernelGGL(pdm_finish_kernel, dim3((unsigned)r.wgs), dim3(64 * kFinZ), r.fin_lds, st, a);
     PDC_HIP(hipGetLastError());
     return PDC_OK;
 }
 
 extern "C" {
+
+int pdc_test_phase_shape(int kind, int64_t n, int64_t n_periods, int nb, int nc, int64_t *out) {
+    PDC_REQUIRE(out && phase_shape_ok(kind, n, n_periods, nb, nc), "pdc_test_phase_shape: bad argument");
+    PDC_REQUIRE(kind != 4 || nb % nc == 0, "pdc_test_phase_shape: the fine bins (%d) must be a multiple of m (%d)", nb, nc);
+    PDC_REQUIRE((kind == 2 ? (int64_t)(nb + 1) * nc - 1 : (int64_t)nb * (kind == 0 ? nc : 1)) <= 190,
+                "pdc_test_phase_shape: more than the 191 histogram bins that fit in LDS");
+    route_fields(phase_route(kind, n, n_periods, nb, nc), out);
+    return PDC_OK;
+}
+
+int pdc_test_phase_last_dispatch(int64_t *out) {
+    PDC_REQUIRE(out, "pdc_test_phase_last_dispatch: NULL argument");
+    std::lock_guard<std::mutex> hold(g_last_route_lock);
+    for (int i = 0; i < kRouteFields; ++i) out[i] = g_last_route[i];
+    return PDC_OK;
+}
 
 int64_t pdc_phase_work_bytes(int kind, int64_t n, int64_t n_periods, int nb, int nc) {
     if (kind == 3) return pdc_stringlength_work_bytes(n, n_periods);
