@@ -433,6 +433,61 @@ int64_t pdc_dcf_chunk(int64_t na, int64_t nb, int64_t nlag);
  * (0: a curve was empty) and the samples per chunk.  Any pointer may be NULL. */
 int pdc_dcf_last_dispatch(int64_t *chunks, int64_t *chunk);
 
+/* ---- GP: celerite log-likelihoods of one curve under many kernels (Foreman-Mackey et al. 2017, AJ 154, 220) -----------
+ * The reference's gp.py evaluates `gp.compute(...); gp.log_likelihood(y)` once per hyper-parameter vector through
+ * celerite2; these entries evaluate M vectors ("candidates") in one call.  A candidate is J terms of four coefficients
+ * (a, b, c, nu): k(D) = sum_j exp(-c_j |D|) (a_j cos(2 pi nu_j D) + b_j sin(2 pi nu_j |D|)) - nu = d / 2 pi of
+ * celerite's d, in CYCLES per time unit, so that phases are reduced before they meet 2 pi; a real term is b = nu = 0 -
+ * plus jitter[m] >= 0 added to every var and a mean.  coeff is [M][J][4], jitter [M], mean [M] or NULL (0).
+ * t_rel[n] = t - t[0] of the sorted times (never decreasing, t_rel[0] == 0), y[n], var[n] = err^2 >= 0.  The recursion
+ * is the celerite2 one (S <- P o (S + D W W^T) o P^T: no overflow), see csrc/gp.hip.
+ *     loglike_out[M]   ln L = -1/2 sum_n (z_n^2 / D_n + ln D_n) - n/2 ln 2 pi; -inf for a candidate with a D_n that is not
+ *                      a positive finite number (its matrix is not positive definite);
+ *     mean_out[M]      the mean used: with fit_mean the profiled one, sum z z1 / D / sum z1^2 / D (z1 the solve of the
+ *                      all-ones vector), and ln L is the likelihood at it; else mean[m] (0 without mean); NaN where
+ *                      ln L is -inf;
+ *     status_out[M]    0, or the 1-based index of the first sample whose D_n is not positive and finite.
+ * fit_mean with a mean array is refused.  A candidate's bits depend on its coefficients and the curve alone - not on
+ * m, M, its neighbours or the slabs: PDC_WORK_BUDGET_GB cuts M into slabs of whole workgroups (64 candidates) whose
+ * repacked coefficients fit the budget beside the fixed part, at least one workgroup.  No atomics.
+ * pdc_gp_scan: the candidates are a grid [np][nq], period-major, nq <= 65535 cells of nuisance parameters per trial
+ * period; besides the likelihoods (cube_out[np][nq], may be NULL)
+ *     profile_out[np]      the largest finite ln L of the period's cells (the first of equal ones); NaN if none;
+ *     cell_out[np]         its cell, -1 if none;
+ *     marginal_out[np]     ln of the mean likelihood of the cells: logsumexp over the finite cells - ln nq; -inf if none;
+ *     period_mean_out[np]  mean_out of that cell; NaN if none;
+ *     best_out[1], best_at_out[2]   the largest profile value (of equal ones the first period), its period and cell;
+ *                          NaN and (-1, -1) if no cell of the grid is finite.
+ * Any output may be NULL, not all.  Checked before any device is looked for: 1 <= n < 2^31, 1 <= J <=
+ * pdc_gp_max_terms(), 1 <= M <= 2^40, np nq == M, np <= 2^38, and in the host form finite t_rel that starts at 0 and never
+ * decreases, finite y, finite var >= 0, finite coefficients with c >= 0, finite jitter >= 0, finite means (the `_dev`
+ * form cannot look: they are its caller's precondition, and no value of them indexes memory).  The `_dev` forms take
+ * device pointers, enqueue on `stream` and keep their own workspace per (device, stream). */
+int pdc_gp_loglike(const double *t_rel, const double *y, const double *var, int64_t n, const double *coeff, int J,
+                   const double *jitter, const double *mean, int64_t M, int fit_mean, double *loglike_out, double *mean_out,
+                   int32_t *status_out, int device);
+int pdc_gp_loglike_dev(int device, void *stream, const double *d_t_rel, const double *d_y, const double *d_var, int64_t n,
+                       const double *d_coeff, int J, const double *d_jitter, const double *d_mean, int64_t M, int fit_mean,
+                       double *d_loglike, double *d_mean_out, int32_t *d_status);
+int pdc_gp_scan(const double *t_rel, const double *y, const double *var, int64_t n, const double *coeff, int J,
+                const double *jitter, const double *mean, int64_t M, int fit_mean, int64_t np, int64_t nq,
+                double *profile_out, int32_t *cell_out, double *marginal_out, double *period_mean_out, double *cube_out,
+                double *best_out, int64_t *best_at_out, int device);
+int pdc_gp_scan_dev(int device, void *stream, const double *d_t_rel, const double *d_y, const double *d_var, int64_t n,
+                    const double *d_coeff, int J, const double *d_jitter, const double *d_mean, int64_t M, int fit_mean,
+                    int64_t np, int64_t nq, double *d_profile, int32_t *d_cell, double *d_marginal, double *d_period_mean,
+                    double *d_cube, double *d_best, int64_t *d_best_at);
+/* Workspace bytes of a scan under the current PDC_WORK_BUDGET_GB (want_cube: the caller's cube takes the likelihoods); -1
+ * for sizes out of range.  pdc_gp_loglike needs less: the records and the slab's coefficients alone.  No GPU needed. */
+int64_t pdc_gp_work_bytes(int64_t n, int64_t M, int J, int want_cube);
+/* The largest J the library was built for.  No GPU needed. */
+int pdc_gp_max_terms(void);
+/* Samples the likelihood kernel stages at a time (the seam its tests straddle).  No GPU needed. */
+int pdc_gp_chunk_samples(void);
+/* What the CALLING THREAD's last GP call launched (as pdc_htest_last_dispatch; zeros before the first): J, fit_mean,
+ * launches of the likelihood kernel (slabs).  Any pointer may be NULL. */
+int pdc_gp_last_dispatch(int *J, int *fit_mean, int64_t *launches);
+
 /* ---- BLS: box least squares (Kovacs, Zucker & Mazeh 2002, A&A 391, 369) ----------------------------------------------
  * The reference has no such class - PARITY UNPINNED BY THE REFERENCE.  The search for a box-shaped dip (a transit, a
  * detached eclipse): per trial period the best two-level model of the folded curve.  Weights and centring as

@@ -79,6 +79,15 @@ PROTOTYPES = {
     "pdc_dcf_work_bytes": (_L, [_L, _L, _L, _L]),
     "pdc_dcf_chunk": (_L, [_L, _L, _L]),
     "pdc_dcf_last_dispatch": (_I, [c_int64_p, c_int64_p]),
+    "pdc_gp_loglike": (_I, [_VP, _VP, _VP, _L, _VP, _I, _VP, _VP, _L, _I, _VP, _VP, _VP, _I]),
+    "pdc_gp_loglike_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _VP, _I, _VP, _VP, _L, _I, _VP, _VP, _VP]),
+    "pdc_gp_scan": (_I, [_VP, _VP, _VP, _L, _VP, _I, _VP, _VP, _L, _I, _L, _L, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I]),
+    "pdc_gp_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _VP, _I, _VP, _VP, _L, _I, _L, _L,
+                             _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pdc_gp_work_bytes": (_L, [_L, _L, _I, _I]),
+    "pdc_gp_max_terms": (_I, []),
+    "pdc_gp_chunk_samples": (_I, []),
+    "pdc_gp_last_dispatch": (_I, [C.POINTER(_I), C.POINTER(_I), c_int64_p]),
     "pdc_bls_scan": (_I, [_VP, _VP, _VP, _L, _VP, _L, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _I]),
     "pdc_bls_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _VP, _L, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "pdc_bls_scan_ragged": (_I, [_VP, _VP, _VP, _VP, _L, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I,
@@ -556,6 +565,77 @@ def dcf_last_dispatch():
     chunks, chunk = C.c_int64(0), C.c_int64(0)
     check(lib().pdc_dcf_last_dispatch(C.byref(chunks), C.byref(chunk)))
     return chunks.value, chunk.value
+
+
+def _gp_inputs(t_rel, y, var, coeff, jitter, mean):
+    """The arrays both GP entries take: ``coeff`` ``[M][J][4]`` of (a, b, c, nu), ``jitter`` and ``mean`` scalars or ``[M]``."""
+    t_rel, y, var = _f64(t_rel, "t_rel"), _f64(y, "y"), _f64(var, "var")
+    if y.size != t_rel.size or var.size != t_rel.size:
+        raise ValueError("Input arrays have incompatible lengths.")
+    coeff = np.ascontiguousarray(coeff, dtype=np.float64)
+    if coeff.ndim != 3 or coeff.shape[2] != 4:
+        raise ValueError("coeff must have the shape [M][J][4]")
+    M = coeff.shape[0]
+    jitter = np.ascontiguousarray(np.broadcast_to(np.asarray(jitter, dtype=np.float64), (M,)))
+    if mean is not None:
+        mean = np.ascontiguousarray(np.broadcast_to(np.asarray(mean, dtype=np.float64), (M,)))
+    return t_rel, y, var, coeff, jitter, mean
+
+
+def gp_loglike(t_rel, y, var, coeff, jitter=0.0, mean=None, fit_mean=False, device=None):
+    """Celerite log-likelihoods of one curve under ``M`` kernels (``pdc_gp_loglike``): ``t_rel = t - t[0]`` of the sorted
+    times, ``var = err ** 2``, ``coeff`` ``[M][J][4]`` of (a, b, c, nu = d / 2 pi).  Returns ``(log_likelihood, mean,
+    status)``, each ``[M]``; ``status`` (int32) is 0 or the 1-based sample at which the matrix stopped being positive
+    definite (then the likelihood is -inf)."""
+    t_rel, y, var, coeff, jitter, mean = _gp_inputs(t_rel, y, var, coeff, jitter, mean)
+    M, J = coeff.shape[:2]
+    ll, mu, status = np.empty(M), np.empty(M), np.empty(M, dtype=np.int32)
+    dev = default_device() if device is None else device
+    check(lib().pdc_gp_loglike(_ptr(t_rel), _ptr(y), _ptr(var), t_rel.size, _ptr(coeff), J, _ptr(jitter), _ptr(mean), M,
+                               int(bool(fit_mean)), _ptr(ll), _ptr(mu), _ptr(status), dev))
+    return ll, mu, status
+
+
+def gp_scan(t_rel, y, var, coeff, n_periods, jitter=0.0, mean=None, fit_mean=False, want_cube=False, device=None):
+    """The same likelihoods for a period-major grid ``[n_periods][nq]`` folded per period (``pdc_gp_scan``).  Returns a
+    dict: ``profile``, ``cell`` (int32), ``marginal``, ``mean`` ``[n_periods]``, ``cube`` ``[n_periods][nq]`` (None
+    without ``want_cube``) and ``best`` = ``(value, period, cell)``."""
+    t_rel, y, var, coeff, jitter, mean = _gp_inputs(t_rel, y, var, coeff, jitter, mean)
+    M, J = coeff.shape[:2]
+    n_periods = int(n_periods)
+    nq = M // n_periods if n_periods > 0 else 0
+    rows = max(n_periods, 0)
+    out = {"profile": np.empty(rows), "cell": np.empty(rows, dtype=np.int32), "marginal": np.empty(rows),
+           "mean": np.empty(rows), "cube": np.empty((rows, nq)) if want_cube else None}
+    best, best_at = np.full(1, np.nan), np.full(2, -1, dtype=np.int64)
+    dev = default_device() if device is None else device
+    check(lib().pdc_gp_scan(_ptr(t_rel), _ptr(y), _ptr(var), t_rel.size, _ptr(coeff), J, _ptr(jitter), _ptr(mean), M,
+                            int(bool(fit_mean)), n_periods, nq, _ptr(out["profile"]), _ptr(out["cell"]),
+                            _ptr(out["marginal"]), _ptr(out["mean"]), _ptr(out["cube"]), _ptr(best), _ptr(best_at), dev))
+    out["best"] = (float(best[0]), int(best_at[0]), int(best_at[1]))
+    return out
+
+
+def gp_work_bytes(n, M, J, want_cube=False):
+    """Workspace bytes of a GP call under the current ``PDC_WORK_BUDGET_GB`` (-1: sizes out of range); no GPU needed."""
+    return int(lib().pdc_gp_work_bytes(int(n), int(M), int(J), int(bool(want_cube))))
+
+
+def gp_max_terms():
+    """The largest number of celerite terms of a candidate; no GPU needed."""
+    return int(lib().pdc_gp_max_terms())
+
+
+def gp_chunk_samples():
+    """Samples the likelihood kernel stages at a time; no GPU needed."""
+    return int(lib().pdc_gp_chunk_samples())
+
+
+def gp_last_dispatch():
+    """``(J, fit_mean, launches)`` of this thread's last GP call."""
+    J, fit_mean, launches = C.c_int(0), C.c_int(0), C.c_int64(0)
+    check(lib().pdc_gp_last_dispatch(C.byref(J), C.byref(fit_mean), C.byref(launches)))
+    return J.value, fit_mean.value, launches.value
 
 
 def bls_scan(t, y, dy, periods, n_bins, len_min, len_max, min_points=5, dips_only=False, slices=0, device=None):
