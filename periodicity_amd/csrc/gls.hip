@@ -771,11 +771,20 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
             auto trow = [](const int i) { return i * 4; };
 #endif
             const int q0 = COLS >= 2 ? (a.lead_swap & col & 1) * 2 : 0;   // (wave-uniform: `col` came through readfirstlane)
-            const cd8 *stab_f = stab + q0, *stab_g = stab + (2 - q0);
-            auto request_first = [&](const int i) {
-                fa = stab_f[trow(i)];
-                fb = stab_f[trow(i) + 1];
-                r = srec[i * 3];
+            // Addressing: the three bases are fixed per chunk, and ONE unsigned byte offset per array moves with the
+            // sample (ot: 256 bytes per table row, orc: 48 per record), so every table load is base + SGPR offset +
+            // immediate (s_load_dwordx16 s[..], s[base:base+1], s_off offset:0x0 | 0x40) and a sample costs two scalar
+            // adds.  (Rebuilt from the sample index, each of the three addresses took a 64-bit shift, add and
+            // add-with-carry per sample, most of them between the last fma of the first half and the request for the
+            // next sample.)  The offsets stay inside one chunk, under 64 KB: 32 bits hold them whatever the table's size.
+            using cbyte = __attribute__((address_space(4))) const char;
+            const cbyte *bf = reinterpret_cast<const cbyte *>(stab + q0), *bg = reinterpret_cast<const cbyte *>(stab + (2 - q0));
+            const cbyte *br = reinterpret_cast<const cbyte *>(srec);
+            uint32_t ot = (uint32_t)trow(i_beg) * 64u, orc = (uint32_t)i_beg * 48u;
+            auto request_first = [&](const int i) {   // (ot and orc are sample i's)
+                fa = *reinterpret_cast<const cd8 *>(bf + ot);
+                fb = *reinterpret_cast<const cd8 *>(bf + ot + 64);
+                r = *reinterpret_cast<const cd2 *>(br + orc);
                 qa = tab[i][slot_a];
                 qt = tab[i][slot_b];
             };
@@ -805,8 +814,8 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
                 request_first(i_beg);
                 for (int i = i_beg; i < i_last; ++i) {
                     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the first half, the record and the seed entries
-                    ga = stab_g[trow(i)];
-                    gb = stab_g[trow(i) + 1];
+                    ga = *reinterpret_cast<const cd8 *>(bg + ot);
+                    gb = *reinterpret_cast<const cd8 *>(bg + ot + 64);
                     __builtin_amdgcn_sched_barrier(0);
                     const double2 seed = rot2(qa, qt);
                     A1 = r[0] * seed.x;
@@ -819,6 +828,8 @@ __global__ __launch_bounds__(kBlock, (K >= 16 ? 2 : 1)) void gls_scan_kernel(Gls
                     pair_fmas(fb, 2);
                     __builtin_amdgcn_sched_barrier(0);
                     __builtin_amdgcn_s_waitcnt(0xc07f);  // the second half
+                    ot += (uint32_t)trow(1) * 64u;
+                    orc += 48u;
                     request_first(i + 1);
                     __builtin_amdgcn_sched_barrier(0);
                     pair_fmas(ga, 4);
