@@ -346,6 +346,56 @@ int64_t pdc_wwz_work_bytes(int64_t n, int64_t nf, int64_t ntau);
  * thread, rows per launch, launches of the scan kernel.  Any pointer may be NULL. */
 int pdc_wwz_last_dispatch(int *k, int *rows_per_launch, int64_t *launches);
 
+/* ---- WPS: the Morlet wavelet power spectrum of an evenly sampled curve -------------------------------------------------
+ * The reference's timefrequency.WPS calls PyWavelets, cwt(values - mean, scales, "cmor2.0-1.0", dt), squares and divides
+ * by the scale.  PyWavelets is not a dependency: its published algorithm is restated here - PARITY UNPINNED BY THE
+ * REFERENCE.  The caller tabulates the integrated wavelet, table[1024] complex (re, im interleaved), on 1024 points `step`
+ * apart over a support `span` wide (cmor2.0-1.0: np.linspace(-8, 8, 1024), conj(cumsum(psi) step), span 16).  With x the
+ * centred samples (x[N], the caller subtracts the mean), zero outside [0, N), and per scale s (samples per period):
+ *     j[m] = trunc(m / (s step)), m = 0 .. ceil(s span + 1) - 1, kept while j[m] < 1024: L entries (L >= 2);
+ *     h[k] = table[j[L-1-k]], h[-1] = h[L] = 0;
+ *     coef[n] = -sqrt(s) sum_{k = 0 .. L} (h[k] - h[k-1]) x[n + floor(L / 2) - k];   spectrum[n] = |coef[n]|^2 / s
+ * - np.convolve(x, h), np.diff, times -sqrt(s), the centred cut to N, as one sum.  The positions where h changes are those
+ * of numpy's rule bit for bit (every operation above rounds once, the division included).  h changes at no more than 1025
+ * positions whatever the scale (the TAPS), so a cell costs at most 1025 complex-by-real multiply-adds, summed in ascending
+ * filter position.  Cone of influence: cell (i, n) is inside where corr * periods[i] < min(t[n] - t_min, t_max - t[n])
+ * (each operation rounded once, as numpy's; corr = exp2(0.5) in the reference).  Outputs, any of them NULL, not all:
+ *     spectrum_out[n_scales][N], coefs_out[n_scales][N] complex (re, im interleaved)   the planes;
+ *     gwps_out[n_scales]   mean over time;   sav_out[N]   mean over the scales;
+ *     masked_gwps_out[n_scales], gwps_count_out[n_scales], masked_sav_out[N], sav_count_out[N]   the means over the cells
+ *         inside the cone, as np.nanmean of the masked plane gives them, NaN where the count is 0.
+ * Without the two planes no [n_scales][N] array exists anywhere.  The rows sum tiles of pdc_wps_tile() time indices in
+ * ascending order, the columns sum chunks of scales in ascending order (8 scales; more where PDC_WORK_BUDGET_GB or the
+ * 65535 chunks of a launch ask for fewer partials).  No atomics: the same bits from call to call, and a scale's row does
+ * not depend on the other scales.  Checked before any device is looked for: N >= 1, n_scales >= 1, step and span finite
+ * and > 0, not every output NULL, and in the host form finite x, t, periods, table and corr, and every scale with
+ * 2 <= L and s <= 2^24 (the `_dev` form cannot look: a scale it cannot serve gives NaN rows, and no value indexes memory
+ * out of bounds).  The `_dev` form takes device pointers and t_min, t_max, enqueues on `stream` and keeps its own
+ * workspace per (device, stream). */
+int pdc_wps_scan(const double *x, const double *t, int64_t n, const double *periods, const double *scales,
+                 int64_t n_scales, const double *table, double step, double span, double corr, double *spectrum_out,
+                 double *coefs_out, double *gwps_out, double *sav_out, double *masked_gwps_out, int64_t *gwps_count_out,
+                 double *masked_sav_out, int64_t *sav_count_out, int device);
+int pdc_wps_scan_dev(int device, void *stream, const double *d_x, const double *d_t, int64_t n, const double *d_periods,
+                     const double *d_scales, int64_t n_scales, const double *d_table, double step, double span,
+                     double corr, double t_min, double t_max, double *d_spectrum, double *d_coefs, double *d_gwps,
+                     double *d_sav, double *d_masked_gwps, int64_t *d_gwps_count, double *d_masked_sav,
+                     int64_t *d_sav_count);
+/* The taps of one scale as the device builds them, on the host (the same function): position_out[<= 1025] ascending,
+ * before_out / after_out the table entries on either side (-1: outside the filter), length_out[1] = L.  Returns the
+ * number of taps, or a negative status.  Any pointer may be NULL.  No GPU needed. */
+int64_t pdc_wps_taps(double scale, double step, double span, int64_t *position_out, int32_t *before_out,
+                     int32_t *after_out, int64_t *length_out);
+/* Time indices per workgroup of the scan.  No GPU needed. */
+int64_t pdc_wps_tile(void);
+/* Workspace bytes of a scan under the current PDC_WORK_BUDGET_GB; -1 for sizes out of range.  No GPU needed. */
+int64_t pdc_wps_work_bytes(int64_t n, int64_t n_scales);
+/* What the CALLING THREAD's last WPS scan launched (zeros before the first): tiles, chunks of scales, scales per chunk,
+ * and - host form only, -1 after a `_dev` call - the scales whose every filter position is a tap (L + 1 <= 1025) and those
+ * served from change points.  Any pointer may be NULL. */
+int pdc_wps_last_dispatch(int64_t *tiles, int64_t *chunks, int64_t *scales_per_chunk, int64_t *dense_scales,
+                          int64_t *sparse_scales);
+
 /* ---- the Keplerian periodogram (Zechmeister & Kurster 2009, A&A 496, 577, section 4) -----------------------------------
  * The reference has no such class - PARITY UNPINNED BY THE REFERENCE.  Per trial frequency the best weighted least-squares
  * fit of a Keplerian orbit over a grid of eccentricities ecc[ne], each in [0, 0.95], and mean anomalies at t[0] m0[nm],

@@ -66,6 +66,13 @@ PROTOTYPES = {
     "pdc_wwz_tile_bins": (_L, []),
     "pdc_wwz_work_bytes": (_L, [_L, _L, _L]),
     "pdc_wwz_last_dispatch": (_I, [C.POINTER(_I), C.POINTER(_I), c_int64_p]),
+    "pdc_wps_scan": (_I, [_VP, _VP, _L, _VP, _VP, _L, _VP, _D, _D, _D, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I]),
+    "pdc_wps_scan_dev": (_I, [_I, _VP, _VP, _VP, _L, _VP, _VP, _L, _VP, _D, _D, _D, _D, _D,
+                              _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pdc_wps_taps": (_L, [_D, _D, _D, _VP, _VP, _VP, c_int64_p]),
+    "pdc_wps_tile": (_L, []),
+    "pdc_wps_work_bytes": (_L, [_L, _L]),
+    "pdc_wps_last_dispatch": (_I, [c_int64_p, c_int64_p, c_int64_p, c_int64_p, c_int64_p]),
     "pdc_kepler_scan": (_I, [_VP, _VP, _VP, _L, _D, _D, _L, _VP, _L, _VP, _L, _I, _I, _VP, _VP, _VP, _VP, _VP, _I]),
     "pdc_kepler_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _D, _D, _L, _VP, _L, _VP, _L, _I, _I,
                                  _VP, _VP, _VP, _VP, _VP]),
@@ -470,6 +477,65 @@ def wwz_last_dispatch():
     k, rows, launches = C.c_int(0), C.c_int(0), C.c_int64(0)
     check(lib().pdc_wwz_last_dispatch(C.byref(k), C.byref(rows), C.byref(launches)))
     return k.value, rows.value, launches.value
+
+
+WPS_TABLE = 1024   # entries of the tabulated wavelet
+
+
+def wps_scan(x, t, periods, scales, table, step, span, corr, want_planes=True, want_coefs=False, device=None):
+    """Morlet wavelet power spectrum (``pdc_wps_scan``) of the centred, evenly sampled ``x`` at times ``t``, one row per
+    scale (samples per period; ``periods`` only feed the cone-of-influence mask, with ``corr``).  ``table``: the
+    integrated wavelet, complex ``[1024]``, ``step`` apart over ``span``.  Returns a dict: ``spectrum`` ``[n_scales][N]``
+    (None without ``want_planes``), ``coefs`` complex (None without ``want_coefs``), the marginals reduced on the device
+    ``gwps`` / ``masked_gwps`` / ``gwps_count`` (int64) ``[n_scales]`` and ``sav`` / ``masked_sav`` / ``sav_count``
+    ``[N]``."""
+    x, t, periods, scales = _f64(x, "x"), _f64(t, "t"), _f64(periods, "periods"), _f64(scales, "scales")
+    table = np.ascontiguousarray(table, dtype=np.complex128)
+    if t.size != x.size or periods.size != scales.size:
+        raise ValueError("Input arrays have incompatible lengths.")
+    if table.shape != (WPS_TABLE,):
+        raise ValueError(f"the wavelet table must have {WPS_TABLE} entries")
+    n, ns = x.size, scales.size
+    out = {"spectrum": np.empty((ns, n)) if want_planes else None,
+           "coefs": np.empty((ns, n), dtype=np.complex128) if want_coefs else None,
+           "gwps": np.empty(ns), "masked_gwps": np.empty(ns), "gwps_count": np.empty(ns, dtype=np.int64),
+           "sav": np.empty(n), "masked_sav": np.empty(n), "sav_count": np.empty(n, dtype=np.int64)}
+    dev = default_device() if device is None else device
+    check(lib().pdc_wps_scan(_ptr(x), _ptr(t), n, _ptr(periods), _ptr(scales), ns, _ptr(table), float(step), float(span),
+                             float(corr), _ptr(out["spectrum"]), _ptr(out["coefs"]), _ptr(out["gwps"]), _ptr(out["sav"]),
+                             _ptr(out["masked_gwps"]), _ptr(out["gwps_count"]), _ptr(out["masked_sav"]),
+                             _ptr(out["sav_count"]), dev))
+    return out
+
+
+def wps_taps(scale, step, span):
+    """``(position, before, after, L)``: the filter positions of one scale where the table entry changes, ascending,
+    with the entries on either side (-1: outside the filter), as the device builds them; no GPU needed."""
+    position = np.empty(WPS_TABLE + 1, dtype=np.int64)
+    before, after = np.empty(WPS_TABLE + 1, dtype=np.int32), np.empty(WPS_TABLE + 1, dtype=np.int32)
+    length = C.c_int64(0)
+    count = int(lib().pdc_wps_taps(float(scale), float(step), float(span), _ptr(position), _ptr(before), _ptr(after),
+                                   C.byref(length)))
+    if count < 0:
+        check(count)
+    return position[:count], before[:count], after[:count], length.value
+
+
+def wps_tile():
+    """Time indices per workgroup of the WPS scan; no GPU needed."""
+    return int(lib().pdc_wps_tile())
+
+
+def wps_work_bytes(n, n_scales):
+    """Workspace bytes of a WPS scan under the current ``PDC_WORK_BUDGET_GB`` (-1: sizes out of range); no GPU needed."""
+    return int(lib().pdc_wps_work_bytes(int(n), int(n_scales)))
+
+
+def wps_last_dispatch():
+    """``(tiles, chunks, scales_per_chunk, dense_scales, sparse_scales)`` of this thread's last WPS scan."""
+    vals = [C.c_int64(0) for _ in range(5)]
+    check(lib().pdc_wps_last_dispatch(*[C.byref(v) for v in vals]))
+    return tuple(v.value for v in vals)
 
 
 def kepler_scan(t, y, dy, f0, delta, nf, ecc, m0, fit_mean=True, psd=False, want_cube=False, want_bins=True,

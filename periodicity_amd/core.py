@@ -14,6 +14,10 @@ here, on plain numpy arrays:
   (``:938-942``), ``find_peaks`` (``:283-317``) and the peak pickers built on it
   (``:944-978``).
 
+* ``TFSeries`` — the 2-D ``[frequency][time]`` container of ``core.py:1030-1127`` that ``timefrequency.WPS`` returns:
+  coordinates, 2-D indexing that falls back to ``TFSeries`` / ``TSeries`` / ``FSeries`` / scalar (``:1062-1075``),
+  NaN-skipping means along either axis, ``median_dt``; no resampling, no plotting.
+
 Objects of the real ``periodicity.core`` classes are accepted anywhere these are: the scan
 classes only use the attributes named above (duck typing).
 """
@@ -22,7 +26,7 @@ from numbers import Number
 import numpy as np
 from scipy import signal as _sps
 
-__all__ = ["TSeries", "FSeries"]
+__all__ = ["TSeries", "FSeries", "TFSeries"]
 
 
 def _is_sorted(a):
@@ -360,3 +364,116 @@ class FSeries(Signal):
         hi = (left - half).find_zero_crossings()[-1]
         lo = (right - half).find_zero_crossings()[0]
         return right.period[lo], left.period[hi]
+
+
+class TFSeries(object):
+    """Values on a ``[frequency][time]`` grid, with the derived ``period`` coordinate (``core.py:1030-1127``).  The
+    coordinates are kept in the order given: nothing is sorted."""
+
+    def __init__(self, time=None, frequency=None, values=None):
+        values = np.asarray(values)
+        time = np.asarray(time)
+        frequency = np.asarray(frequency)
+        if values.ndim != 2 or time.ndim != 1 or frequency.ndim != 1:
+            raise ValueError("TFSeries takes one-dimensional coordinates and two-dimensional values.")
+        if time.size != values.shape[1] or frequency.size != values.shape[0]:
+            raise ValueError("Input arrays have incompatible lengths.")
+        self._time = time
+        self._frequency = frequency
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self._period = 1.0 / frequency
+        self._values = values
+        self.attrs = {}
+
+    @property
+    def time(self):
+        return self._time
+
+    @property
+    def frequency(self):
+        return self._frequency
+
+    @property
+    def period(self):
+        return self._period
+
+    @property
+    def values(self):
+        return self._values
+
+    @values.setter
+    def values(self, new):
+        new = np.asarray(new)
+        if new.shape != self._values.shape:
+            raise ValueError("replacement data must match the signal's shape")
+        self._values = new
+
+    @property
+    def dims(self):
+        return ("frequency", "time")
+
+    @property
+    def shape(self):
+        return self._values.shape
+
+    @property
+    def size(self):
+        return self._values.size
+
+    @property
+    def ndim(self):
+        return 2
+
+    @property
+    def dtype(self):
+        return self._values.dtype
+
+    def __len__(self):
+        return self._values.shape[0]
+
+    def __array__(self, dtype=None, copy=None):
+        return np.asarray(self._values, dtype=dtype)
+
+    def copy(self):
+        new = TFSeries(self._time.copy(), self._frequency.copy(), self._values.copy())
+        new.attrs.update(self.attrs)
+        return new
+
+    def __repr__(self):
+        return (f"<TFSeries (frequency: {self.shape[0]}, time: {self.shape[1]})>\n"
+                f"frequency: {self._frequency!r}\ntime: {self._time!r}\nvalues: {self._values!r}")
+
+    def __getitem__(self, key):
+        """``tf[k_frequency, k_time]``, a missing key taking the whole axis: two axes left give a ``TFSeries``, a scalar
+        time key an ``FSeries``, a scalar frequency key a ``TSeries``, two scalar keys the value."""
+        if not isinstance(key, tuple):
+            key = (key,)
+        if len(key) > 2 or any(k is Ellipsis or k is None for k in key):
+            raise IndexError("TFSeries takes at most one key per axis.")
+        k1, k2 = key + (slice(None),) * (2 - len(key))
+        frequency = self._frequency[k1]
+        time = self._time[k2]
+        if frequency.ndim == 1 and time.ndim == 1:   # (numpy would pair two index arrays up: take the grid instead)
+            rows = np.arange(self._frequency.size)[k1]
+            cols = np.arange(self._time.size)[k2]
+            return TFSeries(time, frequency, self._values[np.ix_(rows, cols)])
+        values = self._values[k1, k2]
+        if values.ndim < 1:
+            return values.item()
+        if time.ndim == 0:
+            return FSeries(frequency, values)
+        return TSeries(time, values)
+
+    def mean(self, dim=None):
+        """NaN-skipping mean: over ``"time"`` an ``FSeries``, over ``"frequency"`` a ``TSeries``, over both a scalar."""
+        if dim is None:
+            return np.nanmean(self._values)
+        if dim == "time":
+            return FSeries(self._frequency, np.nanmean(self._values, axis=1))
+        if dim == "frequency":
+            return TSeries(self._time, np.nanmean(self._values, axis=0))
+        raise ValueError("dim must be 'time', 'frequency' or None")
+
+    @property
+    def median_dt(self):
+        return np.median(np.diff(self._time))
