@@ -396,6 +396,56 @@ int64_t pdc_wps_work_bytes(int64_t n, int64_t n_scales);
 int pdc_wps_last_dispatch(int64_t *tiles, int64_t *chunks, int64_t *scales_per_chunk, int64_t *dense_scales,
                           int64_t *sparse_scales);
 
+/* ---- EMD and CEEMDAN: empirical mode decomposition --------------------------------------------------------------------
+ * The reference's decomposition.EMD (Rilling et al. 2003) and the ensemble stage of its CEEMDAN, restated from its calls
+ * (scipy.signal.find_peaks, np.pad, splrep / splev); its TSeries needs xarray, which is not a dependency: PARITY UNPINNED
+ * BY THE REFERENCE.  A row x[N] on the strictly increasing times t[N]; one sift evaluation of the working mode v:
+ *     M, D        interior maxima / minima as find_peaks(prominence=0) lists them (a flat top once, at (left + right) / 2;
+ *                 a plateau that touches an edge is none); n_zero = #{i : signbit(v[i]) != signbit(v[i + 1])};
+ *     monotonic   if |M| < p or |D| < p or |M| + 2 p < 4 or |D| + 2 p < 4 (p = pad_width);
+ *     knots       p extrema reflected about t[0] (time 2 t[0] - t[M[p-1-j]], value v[M[p-1-j]]), M itself, p reflected
+ *                 about t[N-1]; the envelope is the not-a-knot cubic spline through them, evaluated at every t[i];
+ *     mu = (U + L) / 2, amp = (U - L) / 2, sigma = |mu / amp|;
+ *     is_imf = count(sigma > theta_1) / N < alpha and all(sigma < theta_2) and |n_zero - (|M| + |D|)| <= 1 (ordered
+ *                 comparisons: a NaN sigma is neither);  if not, v -= mu, at most max_iter times.
+ * residue = x; while the residue is not monotonic and fewer than max_modes modes exist, the next mode is sifted from it
+ * and subtracted.  One workgroup per row, the sift loop inside the kernel; rows of at most pdc_emd_lds_samples() samples
+ * with pad_width <= 8 keep the mode in LDS, longer ones in a slab of the workspace - the same code, the same bits, and a
+ * row's bytes depend neither on its place in the batch nor on the call.  PDC_EMD_FORCE_GLOBAL=1 sends every row through
+ * the workspace route.  Outputs: modes_out[B][max_modes][N] (the host form writes a row's first n_modes, the `_dev` form
+ * too, the rest is left as it was), residue_out[B][N], n_modes_out[B], sifts_out[B][max_modes] (updates applied to mode k;
+ * the host form zeroes the rest), flags_out[B]: bit 0 a mode ran into max_iter, bit 1 max_modes reached with the residue
+ * not monotonic.  Checked before any device is looked for: 1 <= N <= 2^24, pad_width 0 .. 2^20, max_modes 1 .. 64,
+ * max_iter 1 .. 10^6, the thresholds finite, and - host forms - finite samples and strictly increasing finite times. */
+int pdc_emd_batch(const double *t, const double *x, int64_t n, int64_t n_rows, int64_t max_iter, int pad_width,
+                  double theta_1, double theta_2, double alpha, int max_modes, double *modes_out, double *residue_out,
+                  int64_t *n_modes_out, int64_t *sifts_out, int64_t *flags_out, int device);
+int pdc_emd_batch_dev(int device, void *stream, const double *d_t, const double *d_x, int64_t n, int64_t n_rows,
+                      int64_t max_iter, int pad_width, double theta_1, double theta_2, double alpha, int max_modes,
+                      double *d_modes, double *d_residue, int64_t *d_n_modes, int64_t *d_sifts, int64_t *d_flags);
+/* One sift evaluation of one row with the batch kernel's own device functions: upper_out[N], lower_out[N] (untouched,
+ * zero, when monotonic), idx_max_out / idx_min_out[N / 2 + 1] (the lists, zero beyond their counts), counts_out[4] =
+ * maxima, minima, n_zero, 1 if monotonic. */
+int pdc_emd_sift(const double *t, const double *x, int64_t n, int pad_width, double *upper_out, double *lower_out,
+                 int32_t *idx_max_out, int32_t *idx_min_out, int64_t *counts_out, int device);
+/* One stage of CEEMDAN on the device: noisy[e] = residue + beta[e] * noise_modes[e][k] where n_noise_modes[e] > k (the
+ * residue itself where not), the first mode of each noisy row, mu[N] = sum over e ascending of (noisy[e] - mode[e]) / E,
+ * a realisation whose noisy row is monotonic adding zero.  noise_modes[E][noise_max_modes][N] and n_noise_modes[E] are
+ * what pdc_emd_batch_dev left on the device; n_modes[E], sifts[E], flags[E] describe the stage's own decompositions.
+ * Nothing of size E N leaves the device. */
+int pdc_ceemdan_stage_dev(int device, void *stream, const double *d_t, const double *d_residue, int64_t n,
+                          const double *d_noise_modes, const int64_t *d_noise_n_modes, int64_t ensemble,
+                          int noise_max_modes, int k, const double *d_beta, int64_t max_iter, int pad_width,
+                          double theta_1, double theta_2, double alpha, double *d_mu, int64_t *d_n_modes,
+                          int64_t *d_sifts, int64_t *d_flags);
+/* Longest row the LDS route serves.  No GPU needed. */
+int64_t pdc_emd_lds_samples(void);
+/* Workspace bytes of a batch (the global route sized for 256 compute units); -1 for sizes out of range.  No GPU needed. */
+int64_t pdc_emd_work_bytes(int64_t n, int64_t n_rows, int pad_width);
+/* What the CALLING THREAD's last EMD call launched (zeros before the first): route (1 LDS, 2 workspace), threads per
+ * workgroup, rows, and - host batch form only, -1 otherwise - the sift evaluations of all rows.  Any pointer may be NULL. */
+int pdc_emd_last_dispatch(int64_t *route, int64_t *threads, int64_t *rows, int64_t *sift_evaluations);
+
 /* ---- the Keplerian periodogram (Zechmeister & Kurster 2009, A&A 496, 577, section 4) -----------------------------------
  * The reference has no such class - PARITY UNPINNED BY THE REFERENCE.  Per trial frequency the best weighted least-squares
  * fit of a Keplerian orbit over a grid of eccentricities ecc[ne], each in [0, 0.95], and mean anomalies at t[0] m0[nm],

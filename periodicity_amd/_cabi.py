@@ -73,6 +73,14 @@ PROTOTYPES = {
     "pdc_wps_tile": (_L, []),
     "pdc_wps_work_bytes": (_L, [_L, _L]),
     "pdc_wps_last_dispatch": (_I, [c_int64_p, c_int64_p, c_int64_p, c_int64_p, c_int64_p]),
+    "pdc_emd_batch": (_I, [_VP, _VP, _L, _L, _L, _I, _D, _D, _D, _I, _VP, _VP, _VP, _VP, _VP, _I]),
+    "pdc_emd_batch_dev": (_I, [_I, _VP, _VP, _VP, _L, _L, _L, _I, _D, _D, _D, _I, _VP, _VP, _VP, _VP, _VP]),
+    "pdc_emd_sift": (_I, [_VP, _VP, _L, _I, _VP, _VP, _VP, _VP, _VP, _I]),
+    "pdc_ceemdan_stage_dev": (_I, [_I, _VP, _VP, _VP, _L, _VP, _VP, _L, _I, _I, _VP, _L, _I, _D, _D, _D,
+                                   _VP, _VP, _VP, _VP]),
+    "pdc_emd_lds_samples": (_L, []),
+    "pdc_emd_work_bytes": (_L, [_L, _L, _I]),
+    "pdc_emd_last_dispatch": (_I, [c_int64_p, c_int64_p, c_int64_p, c_int64_p]),
     "pdc_kepler_scan": (_I, [_VP, _VP, _VP, _L, _D, _D, _L, _VP, _L, _VP, _L, _I, _I, _VP, _VP, _VP, _VP, _VP, _I]),
     "pdc_kepler_scan_dev": (_I, [_I, _VP, _VP, _VP, _VP, _L, _D, _D, _L, _VP, _L, _VP, _L, _I, _I,
                                  _VP, _VP, _VP, _VP, _VP]),
@@ -536,6 +544,141 @@ def wps_last_dispatch():
     vals = [C.c_int64(0) for _ in range(5)]
     check(lib().pdc_wps_last_dispatch(*[C.byref(v) for v in vals]))
     return tuple(v.value for v in vals)
+
+
+EMD_MAX_MODES = 64   # modes per row the device keeps
+
+
+def _emd_inputs(t, x):
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("x must be two-dimensional: one row per curve")
+    t = _f64(t, "t")
+    if t.size != x.shape[1]:
+        raise ValueError("t and the rows of x differ in length")
+    return t, x
+
+
+def emd_batch(t, x, max_iter=2000, pad_width=2, theta_1=0.05, theta_2=0.50, alpha=0.05, max_modes=EMD_MAX_MODES,
+              device=None):
+    """Empirical mode decomposition (``pdc_emd_batch``) of the rows ``x[B][N]`` on the shared times ``t[N]``.
+
+    Returns a dict: ``modes`` ``[B][max_modes][N]`` (row ``b`` holds ``n_modes[b]`` modes, zeros after them), ``residue``
+    ``[B][N]``, ``n_modes`` ``[B]``, ``sifts`` ``[B][max_modes]`` and ``flags`` ``[B]`` (bit 0: a mode ran into
+    ``max_iter``; bit 1: ``max_modes`` reached with the residue not monotonic)."""
+    t, x = _emd_inputs(t, x)
+    B, n = x.shape
+    max_modes = int(max_modes)
+    out = {"modes": np.zeros((B, max(max_modes, 0), n)), "residue": np.empty((B, n)),
+           "n_modes": np.zeros(B, dtype=np.int64), "sifts": np.zeros((B, max(max_modes, 0)), dtype=np.int64),
+           "flags": np.zeros(B, dtype=np.int64)}
+    device = default_device() if device is None else device
+    check(lib().pdc_emd_batch(_ptr(t), _ptr(x), n, B, int(max_iter), int(pad_width), float(theta_1), float(theta_2),
+                              float(alpha), max_modes, _ptr(out["modes"]), _ptr(out["residue"]), _ptr(out["n_modes"]),
+                              _ptr(out["sifts"]), _ptr(out["flags"]), device))
+    return out
+
+
+def emd_sift(t, x, pad_width=2, device=None):
+    """One sift evaluation (``pdc_emd_sift``) of the curve ``x`` at times ``t``: a dict with ``upper``, ``lower`` ``[N]``,
+    the index lists ``maxima``, ``minima``, ``n_zero`` and ``monotonic`` (then the envelopes are None)."""
+    t, x = _f64(t, "t"), _f64(x, "x")
+    if t.size != x.size:
+        raise ValueError("t and x differ in length")
+    n = x.size
+    upper, lower = np.empty(n), np.empty(n)
+    imax, imin = np.zeros(n // 2 + 1, dtype=np.int32), np.zeros(n // 2 + 1, dtype=np.int32)
+    counts = np.zeros(4, dtype=np.int64)
+    device = default_device() if device is None else device
+    check(lib().pdc_emd_sift(_ptr(t), _ptr(x), n, int(pad_width), _ptr(upper), _ptr(lower), _ptr(imax), _ptr(imin),
+                             _ptr(counts), device))
+    mono = bool(counts[3])
+    return {"upper": None if mono else upper, "lower": None if mono else lower,
+            "maxima": imax[:counts[0]].astype(np.int64), "minima": imin[:counts[1]].astype(np.int64),
+            "n_zero": int(counts[2]), "monotonic": mono}
+
+
+def emd_lds_samples():
+    """Longest row the LDS route of the decomposition serves; no GPU needed."""
+    return int(lib().pdc_emd_lds_samples())
+
+
+def emd_work_bytes(n, n_rows, pad_width=2):
+    """Workspace bytes of a decomposition (-1: sizes out of range); no GPU needed."""
+    return int(lib().pdc_emd_work_bytes(int(n), int(n_rows), int(pad_width)))
+
+
+def emd_last_dispatch():
+    """``(route, threads, rows, sift_evaluations)`` of this thread's last EMD call; route is "lds" or "global"."""
+    vals = [C.c_int64(0) for _ in range(4)]
+    check(lib().pdc_emd_last_dispatch(*[C.byref(v) for v in vals]))
+    route = {0: None, 1: "lds", 2: "global"}[vals[0].value]
+    return (route,) + tuple(v.value for v in vals[1:])
+
+
+class CeemdanPlan:
+    """The ensemble of one CEEMDAN run kept on the device: the noise realisations are decomposed once
+    (``pdc_emd_batch_dev``), then every stage (``pdc_ceemdan_stage_dev``) takes the current residue and ``beta[E]`` up and
+    brings ``mu[N]`` and the realisations' trajectories back."""
+
+    def __init__(self, t, noise, max_iter=2000, pad_width=2, theta_1=0.05, theta_2=0.50, alpha=0.05,
+                 max_modes=EMD_MAX_MODES, device=None):
+        t, noise = _emd_inputs(t, noise)
+        self.device = default_device() if device is None else device
+        self.E, self.n = noise.shape
+        self.max_modes = int(max_modes)
+        self.params = (int(max_iter), int(pad_width), float(theta_1), float(theta_2), float(alpha))
+        E, n, K = self.E, self.n, self.max_modes
+        self._bufs = []
+        new = lambda nbytes: self._keep(DeviceBuffer(nbytes, self.device))
+        self.d_t = self._keep(DeviceBuffer.from_array(t, self.device))
+        d_noise = self._keep(DeviceBuffer.from_array(noise, self.device))
+        self.d_modes, self.d_nm = new(E * K * n * 8), new(E * 8)
+        d_res, d_sifts, d_flags = new(E * n * 8), new(E * K * 8), new(E * 8)
+        self.d_residue, self.d_beta, self.d_mu = new(n * 8), new(E * 8), new(n * 8)
+        self.d_snm, self.d_ssf, self.d_sfl = new(E * 8), new(E * 8), new(E * 8)
+        check(lib().pdc_memset(self.device, d_sifts.ptr, 0, E * K * 8))
+        check(lib().pdc_emd_batch_dev(self.device, None, self.d_t.ptr, d_noise.ptr, n, E, *self.params, K,
+                                      self.d_modes.ptr, d_res.ptr, self.d_nm.ptr, d_sifts.ptr, d_flags.ptr))
+        check(lib().pdc_device_sync(self.device))
+        self.n_modes = self.d_nm.to_array(np.int64, E)
+        self.sifts = d_sifts.to_array(np.int64, E * K).reshape(E, K)
+        self.flags = d_flags.to_array(np.int64, E)
+
+    def _keep(self, buf):
+        self._bufs.append(buf)
+        return buf
+
+    def noise_mode(self, k):
+        """Mode ``k`` of every realisation, ``[E][N]`` (rows without one are zero): one copy of E N values."""
+        out = np.zeros((self.E, self.n))
+        for e in np.flatnonzero(self.n_modes > k):
+            src = self.d_modes.ptr + (int(e) * self.max_modes + int(k)) * self.n * 8
+            check(lib().pdc_memcpy_d2h(self.device, _ptr(out[e]), src, self.n * 8))
+        return out
+
+    def stage(self, residue, k, beta):
+        """``(mu[N], n_modes[E], sifts[E], flags[E])`` of stage ``k``."""
+        residue = _f64(residue, "residue")
+        beta = _f64(np.broadcast_to(np.asarray(beta, dtype=np.float64), (self.E,)), "beta")
+        if residue.size != self.n:
+            raise ValueError("the residue and the ensemble differ in length")
+        if not (np.all(np.isfinite(residue)) and np.all(np.isfinite(beta))):
+            raise ValueError("the residue and beta must be finite")
+        dev = self.device
+        check(lib().pdc_memcpy_h2d(dev, self.d_residue.ptr, _ptr(residue), residue.nbytes))
+        check(lib().pdc_memcpy_h2d(dev, self.d_beta.ptr, _ptr(beta), beta.nbytes))
+        check(lib().pdc_ceemdan_stage_dev(dev, None, self.d_t.ptr, self.d_residue.ptr, self.n, self.d_modes.ptr,
+                                          self.d_nm.ptr, self.E, self.max_modes, int(k), self.d_beta.ptr, *self.params,
+                                          self.d_mu.ptr, self.d_snm.ptr, self.d_ssf.ptr, self.d_sfl.ptr))
+        check(lib().pdc_device_sync(dev))
+        return (self.d_mu.to_array(np.float64, self.n), self.d_snm.to_array(np.int64, self.E),
+                self.d_ssf.to_array(np.int64, self.E), self.d_sfl.to_array(np.int64, self.E))
+
+    def close(self):
+        for buf in self._bufs:
+            buf.free()
+        self._bufs = []
 
 
 def kepler_scan(t, y, dy, f0, delta, nf, ecc, m0, fit_mean=True, psd=False, want_cube=False, want_bins=True,

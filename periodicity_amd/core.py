@@ -203,7 +203,7 @@ class Signal(np.lib.mixins.NDArrayOperatorsMixin):
         i = self.argmin()
         return self[i:i + 1]
 
-    def mean(self):
+    def mean(self, axis=None, dtype=None, out=None):   # (np.mean(signal) hands these over; one dimension: nothing to choose)
         return np.nanmean(self._values)
 
     def median(self):
